@@ -15,8 +15,14 @@ every rank owns its own boards; no collective on the data path).  Finished games
 from a pre-generated board pool (auto-reset).
 
 Rank 0 prints ONE JSON line.  `roofline` prices the step kernel against HBM bandwidth with
-SURVEY 8(d)'s algorithmic bytes per env-step; `cpu_baseline` times the CPU oracle (a C
-restatement of the Go engine: kind "port") on the host cores on a bounded sample.
+SURVEY 8(d)'s algorithmic bytes per env-step.  A plain run sets up, warms up, times the steps and
+prints the line; `--full` adds the figures that take runs of their own: `fused_rollout` (the same
+turns K per launch) and `cpu_baseline`, which times the CPU oracle (a C restatement of the Go
+engine: kind "port") on the host cores on a bounded sample.
+
+`--dump-outputs DIR` writes what the last timed step left a caller - board state and legal masks
+of a fixed, seeded sample of boards - as DIR/<name>.npy (dump_outputs).  The untimed prewarm plays
+a fixed number of turns, so the same arguments give the same outputs in every run.
 
 Scaling modes (N > 1): the default is weak scaling (--envs-per-gpu boards on every rank);
 `--total-envs T` is strong scaling - BASELINE.json configs[3] as stated, 262,144 boards sharded
@@ -155,6 +161,45 @@ def cpu_baseline(w, h, p, fog, seed, budget_s=15.0):
                       f"Engine.Step restatement + packed legal masks every turn (the GPU leg's work), OpenMP over boards; {dt:.1f} s of CPU work",
             "note": "C restatement of the Go engine (oracle/generals_oracle.c), never the Go engine itself",
             "go_reference": go_probe()}
+
+
+DUMP_SAMPLE_SEED = 20240613   # which boards --dump-outputs writes: fixed, so two builds are compared board for board
+DUMP_BLOCK = 64               # boards are sampled in runs of this many consecutive envs (one state read per run)
+DUMP_MAX_BOARDS = 2048
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the timed path leaves its caller after the last step - every GameState field
+    (VecEngine.game_state) and the packed legal masks the step kernel emitted (legal_action_mask_bits) - for a
+    fixed, seeded sample of whole boards, written as out_dir/<field>.npy with the sampled env indices in env_index.npy.
+    Int32 fields (army, army_count, ...) go out as float64, the byte fields as float32: both exact.  -> {name: shape}."""
+    import numpy as np
+    from generalsreinforcementlearning_amd._lib import check
+    B, P, mb = eng.B, eng.max_p, eng.mask_bytes
+    per_board = eng.stride * (8 + 6 * 4) + P * mb * 4 + 7 * 8 + P * 4 * 8   # bytes written per sampled board, at most
+    nblk = -(-B // DUMP_BLOCK)
+    k = max(1, min(nblk, DUMP_MAX_BOARDS // DUMP_BLOCK, DUMP_MAX_BYTES // (DUMP_BLOCK * per_board)))
+    blocks = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nblk, k, replace=False))
+    parts, envs = {}, []
+    for b in blocks:
+        lo = int(b) * DUMP_BLOCK
+        n = min(DUMP_BLOCK, B - lo)
+        st = eng.game_state(lo, n)
+        bits = np.zeros((n, P, mb), np.uint8)   # env-major like legal_action_mask_bits: the slice [lo, lo + n) of the buffer
+        check(eng.L.gvec_read_buffer(eng.h, 3, lo * P * mb, n * P * mb, bits.ctypes.data), "gvec_read_buffer")   # GVEC_BUF_LEGAL
+        st["legal_mask_bits"] = bits
+        for name, a in st.items():
+            parts.setdefault(name, []).append(a)
+        envs.append(np.arange(lo, lo + n))
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"env_index": np.concatenate(envs).astype(np.float64)}
+    for name, a in parts.items():
+        a = np.concatenate(a)
+        out[name] = a.astype(np.float64 if a.dtype.itemsize > 2 else np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def shard_plan(args, world, rank):
@@ -296,8 +341,10 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=262144, help="weak scaling: boards on every rank")
     ap.add_argument("--total-envs", type=int, default=0,
                     help="strong scaling: this many boards in total, sharded across the ranks (BASELINE configs[3]: 262144)")
-    ap.add_argument("--prewarm-s", type=float, default=0.75,
-                    help="untimed clock-settle phase before the counted warmup: step launches for at least this many seconds")
+    ap.add_argument("--prewarm-steps", type=int, default=3408,
+                    help="untimed clock-settle phase before the counted warmup: this many step launches.  A count, not a time, so "
+                         "that the timed steps start from the same boards in every run; 3,408 is how many the former 0.75-s phase "
+                         "played on an MI355X, so the timed boards stay near turn 3,400")
     ap.add_argument("--width", type=int, default=20)
     ap.add_argument("--height", type=int, default=20)
     ap.add_argument("--players", type=int, default=4)
@@ -322,12 +369,20 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and run the record-gather choreography even at world size 1: "
                          "exercises the N>1 code path (side stream, events, experience records, decode) on a single GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fused", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own after the timed steps: the fused "
+                         "rollout and the CPU baseline (off by default: a plain run only times its steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (board state and legal masks of a fixed, seeded "
+                         "sample of rank 0's boards) as DIR/<name>.npy, float32 / float64, under 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-fused", action="store_true", help="with --full: leave the fused rollout out")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="control-flow rehearsal of the multi-rank path on CPU (gloo, no GPU, no engine work): "
                          "used by tests/test_bench_distributed.py; prints a line marked \"rehearsal\": true, never a result")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.prewarm_steps < 0:
+        ap.error("--steps must be at least 1, --warmup and --prewarm-steps at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python bench.py --gpus N`: no launcher made the ranks, so this (GPU-less) process does
@@ -522,12 +577,14 @@ def main():
             torch.cuda.synchronize()
 
     # clock-settle phase (untimed, not counted as warmup): a cold MI355X needs a few hundred ms of load before its
-    # clocks and HBM settle - a 20-step run measured straight after the reset reads ~9 % slower than a 200-step one
+    # clocks and HBM settle - a 20-step run measured straight after the reset reads ~9 % slower than a 200-step one.
+    # It plays a fixed number of turns: a time-bound phase left the timed steps a different starting turn in every run
     prewarm_steps, tp = 0, time.perf_counter()
-    while time.perf_counter() - tp < args.prewarm_s:
-        for _ in range(16):
+    while prewarm_steps < args.prewarm_steps:
+        n_ = min(16, args.prewarm_steps - prewarm_steps)
+        for _ in range(n_):
             eng.rollout(1, seed + 7, 0, fused=False, want_stats=False)
-        prewarm_steps += 16
+        prewarm_steps += n_
         torch.cuda.synchronize()
     prewarm_s = time.perf_counter() - tp
     for k in range(args.warmup):
@@ -555,8 +612,13 @@ def main():
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         played = dict(zip(("env_steps", "aborted_turns", "games_finished"), (int(v) for v in c.tolist())))
 
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the boards (the fused rollout of --full does)
+        shapes = dump_outputs(eng, args.dump_outputs)
+        print(f"[bench] wrote {len(shapes)} arrays of the last timed step to {args.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
+
     fused = None
-    if not args.no_fused:
+    if args.full and not args.no_fused:
         kf = max(1, min(args.steps, 64))
         eng.rollout(kf, seed + 1, 0, fused=True, want_stats=False)
         torch.cuda.synchronize()
@@ -682,7 +744,7 @@ def main():
                                                  "snapshot and record kernels of the sampled slice (about 26 us per step at 4,096 records)")
         if fused:
             out["fused_rollout"] = fused
-        if n == 1 and not args.no_cpu_baseline:
+        if n == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, H, P, bool(args.fog), args.seed)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -106,7 +106,7 @@ def test_bench_two_ranks_with_real_engines_on_one_gpu():
     check, not a measurement: the line says so."""
     env = dict(_plain_env(), GVEC_BENCH_SAME_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4",
-                        "--envs-per-gpu", "8192", "--gather-envs", "512", "--gather-every", "3", "--pool", "256", "--prewarm-s", "0.05",
+                        "--envs-per-gpu", "8192", "--gather-envs", "512", "--gather-every", "3", "--pool", "256", "--prewarm-steps", "64",
                         "--no-cpu-baseline", "--no-fused"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -124,7 +124,7 @@ def test_bench_three_ranks_strong_scaling_with_real_engines_on_one_gpu():
     5,462 / 5,461 / 5,461 boards, equal gather slabs, records tagged with global env ids of all three shards."""
     env = dict(_plain_env(), GVEC_BENCH_SAME_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "8", "--warmup", "2",
-                        "--total-envs", "16384", "--gather-envs", "8192", "--gather-every", "2", "--pool", "256", "--prewarm-s", "0.05",
+                        "--total-envs", "16384", "--gather-envs", "8192", "--gather-every", "2", "--pool", "256", "--prewarm-steps", "64",
                         "--no-cpu-baseline", "--no-fused"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
@@ -142,7 +142,7 @@ def test_bench_overlapped_record_chain_changes_nothing_but_the_time():
     outs = []
     for overlap in ("1", "0"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "30", "--warmup", "6",
-                            "--envs-per-gpu", "20000", "--gather-envs", "1500", "--gather-every", "3", "--pool", "64", "--prewarm-s", "0",
+                            "--envs-per-gpu", "20000", "--gather-envs", "1500", "--gather-every", "3", "--pool", "64", "--prewarm-steps", "0",
                             "--width", "12", "--height", "12", "--players", "3", "--record-overlap", overlap, "--fingerprint",
                             "--no-cpu-baseline", "--no-fused"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=_plain_env())
         assert r.returncode == 0, r.stderr[-3000:]

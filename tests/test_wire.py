@@ -1,11 +1,12 @@
 """generalsreinforcementlearning_amd.wire: the reference's proto surface served from the batched engine.
 
-In the build container the reference's committed stubs (python/generals_pb) are importable: the schema declared in
-wire.py must describe the same wire format (field tables) and messages must cross-parse.  Everywhere (also on the
-GPU box, where the reference does not exist) the adapters are checked against a scalar restatement of
-convertGameStateToProto / createStreamUpdate (internal/grpc/gameserver/server.go:526-777) on oracle states."""
+The schema declared in wire.py must describe the reference's wire format (the field tables of its committed stubs,
+python/generals_pb) and messages must cross-parse with those stubs: both are pinned by tests/golden/wire_fixtures.json,
+which tests/golden/make_wire_fixtures.py records from the reference's stubs and client.  The adapters are also checked
+against a scalar restatement of convertGameStateToProto / createStreamUpdate (internal/grpc/gameserver/server.go:526-777)
+on oracle states."""
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -16,35 +17,62 @@ from generalsreinforcementlearning_amd import wire
 from generalsreinforcementlearning_amd.experience import ExperienceBatcher
 from generalsreinforcementlearning_amd.vec_engine import unpack_legal_bits
 
-REF = os.environ.get("GRL_REFERENCE_DIR", "/root/reference")
-HAVE_REF = os.path.exists(os.path.join(REF, "python", "generals_pb"))
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wire_fixtures.json")
+# the times the cross-parse messages carry instead of the time of the call (they are stamped with GetCurrentTime)
+STAMP_NS = {"update": 1_760_000_000_123_456_789, "collected": 1_760_000_001_000_000_001, "created": 1_760_000_002_500_000_000}
 
 
-def _ref_modules():
-    sys.path.insert(0, os.path.join(REF, "python"))
-    from generals_pb.common.v1 import common_pb2
-    from generals_pb.experience.v1 import experience_pb2
-    from generals_pb.game.v1 import game_pb2
-    return common_pb2, game_pb2, experience_pb2
+def _field_table(d):
+    """field number -> (name, type, repeated, message type, enum type, oneof) of a message descriptor."""
+    return {f.number: (f.name, f.type, f.is_repeated if hasattr(f, 'is_repeated') else None, f.message_type.full_name if f.message_type else None,
+                       f.enum_type.full_name if f.enum_type else None,
+                       f.containing_oneof.name if f.containing_oneof else None) for f in d.fields}
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="the reference's stubs exist in the build container only")
+def _cross_parse_messages():
+    """What the reference's stubs parsed when the fixture was recorded: the GameUpdates of envs 1 and 4 for viewer 1 after
+    30 oracle turns, and a batch of two experiences; their timestamps set to STAMP_NS (each builder must have set one)."""
+    ora, per, _ = _rollout()
+    for _ in range(30):
+        ora.step(ora.agent_actions(3))
+    st, vis, fog = _oracle_views(ora, 1)
+    bits = ora.legal_mask()
+    ups = []
+    for e in (1, 4):
+        w, h, P = per[e]
+        up = wire.stream_update(st, vis, fog, unpack_legal_bits(bits[e, 1], w, h), e, 1, game_id="x")
+        assert up.HasField("timestamp")
+        up.timestamp.FromNanoseconds(STAMP_NS["update"])
+        ups.append(up)
+    rng = np.random.default_rng(0)
+    d = {"experience_id": "id-1", "game_id": "g", "player_id": 1, "turn": 9, "state": rng.random((9, 5, 6), np.float32),
+         "action": 17, "reward": float(np.float32(0.123)), "next_state": rng.random((9, 5, 6), np.float32), "done": False,
+         "action_mask": rng.random(5 * 6 * 4) < 0.3}
+    batch = wire.experience_batch([wire.experience(d), wire.experience(d)], batch_id=3, stream_id="s1")
+    assert batch.HasField("created_at") and all(x.HasField("collected_at") for x in batch.experiences)
+    batch.created_at.FromNanoseconds(STAMP_NS["created"])
+    for x in batch.experiences:
+        x.collected_at.FromNanoseconds(STAMP_NS["collected"])
+    return ups, d, batch
+
+
+def _decode_value(v):
+    """A value of the fixture's client_processed dict (make_wire_fixtures.encode_value) back in the client's types."""
+    if "dtype" in v:
+        return np.array(v["data"], dtype=v["dtype"]).reshape(v["shape"])
+    return {"str": str, "int": int, "float": float, "bool": bool}[v["type"]](v["value"])
+
+
 def test_schema_is_the_references_wire_format():
-    common_pb2, game_pb2, experience_pb2 = _ref_modules()
-    mods = {"generals.common.v1": common_pb2, "generals.game.v1": game_pb2, "generals.experience.v1": experience_pb2}
+    fx = json.load(open(FIXTURE))["schema"]
     checked = 0
     for spec in wire._SCHEMA.values():
-        ref = mods[spec["package"]]
+        ref = fx[spec["package"]]
         for ename, values in spec["enums"].items():
-            rd = ref.DESCRIPTOR.enum_types_by_name[ename]
-            assert [(v.name, v.number) for v in rd.values] == [(v, i) for i, v in enumerate(values)], ename
+            assert [tuple(v) for v in ref["enums"][ename]] == [(v, i) for i, v in enumerate(values)], ename
         for mname in spec["messages"]:
             mine = wire.POOL.FindMessageTypeByName(f"{spec['package']}.{mname}")
-            theirs = ref.DESCRIPTOR.message_types_by_name[mname]
-            tab = lambda d: {f.number: (f.name, f.type, f.is_repeated if hasattr(f, 'is_repeated') else None, f.message_type.full_name if f.message_type else None,
-                                        f.enum_type.full_name if f.enum_type else None,
-                                        f.containing_oneof.name if f.containing_oneof else None) for f in d.fields}
-            a, b = tab(mine), tab(theirs)
+            a, b = _field_table(mine), {int(k): tuple(v) for k, v in ref["messages"][mname].items()}
             if mname == "GameUpdate":
                 b.pop(3)          # GameUpdate.event (game events): not produced by the turn engine, not declared
             assert a == b, (mname, a, b)
@@ -161,31 +189,23 @@ def test_delta_threshold_boundaries():
             assert len(up.delta.tile_updates) == max(nc, nv)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="the reference's stubs exist in the build container only")
 def test_messages_cross_parse_with_the_references_stubs():
-    common_pb2, game_pb2, experience_pb2 = _ref_modules()
-    from experience_stream_client import ExperienceConfig, ExperienceStreamClient
+    """Our bytes are the bytes the reference's stubs parsed and re-serialised, the stubs read the same message from them
+    (MessageToDict), and the reference's client (ExperienceStreamClient._process_experience) decoded the experience back
+    into the dict it was built from."""
     from google.protobuf.json_format import MessageToDict
-    ora, per, _ = _rollout()
-    for _ in range(30):
-        ora.step(ora.agent_actions(3))
-    st, vis, fog = _oracle_views(ora, 1)
-    bits = ora.legal_mask()
-    for e in (1, 4):
-        w, h, P = per[e]
-        up = wire.stream_update(st, vis, fog, unpack_legal_bits(bits[e, 1], w, h), e, 1, game_id="x")
-        theirs = game_pb2.GameUpdate.FromString(up.SerializeToString())
-        assert MessageToDict(theirs) == MessageToDict(up)
-        assert theirs.SerializeToString(deterministic=True) == up.SerializeToString(deterministic=True)
-    rng = np.random.default_rng(0)
-    d = {"experience_id": "id-1", "game_id": "g", "player_id": 1, "turn": 9, "state": rng.random((9, 5, 6), np.float32),
-         "action": 17, "reward": float(np.float32(0.123)), "next_state": rng.random((9, 5, 6), np.float32), "done": False,
-         "action_mask": rng.random(5 * 6 * 4) < 0.3}
-    batch = wire.experience_batch([wire.experience(d), wire.experience(d)], batch_id=3, stream_id="s1")
-    tb = experience_pb2.ExperienceBatch.FromString(batch.SerializeToString())
-    assert tb.batch_id == 3 and tb.stream_id == "s1" and tb.metadata["batch_size"] == "2" and len(tb.experiences) == 2
-    assert tb.experiences[0].metadata["collector_version"] == "1.0.0"
-    back = ExperienceStreamClient(ExperienceConfig())._process_experience(tb.experiences[1])   # the reference's client code
+    fx = json.load(open(FIXTURE))
+    ups, d, batch = _cross_parse_messages()
+    assert len(ups) == len(fx["game_updates"]) == 2
+    for up, theirs in zip(ups, fx["game_updates"]):
+        assert MessageToDict(up) == theirs["json"]
+        assert up.SerializeToString(deterministic=True).hex() == theirs["wire_hex"]
+    tb = fx["experience_batch"]
+    assert MessageToDict(batch) == tb["json"]
+    assert batch.SerializeToString(deterministic=True).hex() == tb["wire_hex"]
+    assert batch.batch_id == 3 and batch.stream_id == "s1" and batch.metadata["batch_size"] == "2" and len(batch.experiences) == 2
+    assert batch.experiences[0].metadata["collector_version"] == "1.0.0"
+    back = {k: _decode_value(v) for k, v in tb["client_processed"].items()}   # the reference's client on experiences[1]
     for k, v in d.items():
         if isinstance(v, np.ndarray):
             assert back[k].dtype == v.dtype and np.array_equal(back[k], v.reshape(back[k].shape)), k
