@@ -90,6 +90,8 @@ SYMBOLS = {
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_step": (_i32, [_vp, _i32, _u64] + [_vp] * 3 + [_i32] + [_vp] * 11),
+    "gvec_gym_observe_players": (_i32, [_vp, C.c_uint32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gvec_gym_step_players": (_i32, [_vp, C.c_uint32, _u64] + [_vp] * 3 + [_i32] + [_vp] * 11),
     "gvec_stream_delta_cap": (_i32, [_vp]),
     "gvec_stream_deltas": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32]),
     "gvec_stream_deltas_packed": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),

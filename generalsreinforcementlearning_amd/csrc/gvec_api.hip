@@ -1508,6 +1508,91 @@ int32_t gvec_gym_step(gvec_handle* h, int32_t player, uint64_t agent_seed, const
   return GVEC_OK;
 }
 
+// the checks both self-play calls share (each failure names itself in gvec_last_error); allocates the stored player stats
+// on first use.  `ptrs_ok`: every required pointer is non-null
+static int32_t gym_players_prepare(gvec_handle* h, uint32_t learners, bool ptrs_ok, int32_t max_turns, const char* what) {
+  if (learners == 0u || (learners >> GVEC_MAX_PLAYERS) != 0u || (h && !h->sharded() && (learners >> h->maxp) != 0u)) {
+    set_err("%s: learners must be a non-empty set of player ids below max_players", what);
+    return GVEC_E_INVALID;
+  }
+  if (!h || !ptrs_ok || max_turns < 1) {
+    set_err("%s: null handle, a required pointer is null, or max_turns < 1", what);
+    return GVEC_E_INVALID;
+  }
+  if (h->sharded()) return sharded::unsupported(what);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!h->d_gym_prev) {
+    HIPCHK(hipMalloc(&h->d_gym_prev, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4));
+    HIPCHK(hipMemsetAsync(h->d_gym_prev, 0, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4, h->stream));
+  }
+  return GVEC_OK;
+}
+
+int32_t gvec_gym_observe_players(gvec_handle* h, uint32_t learners, const int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask,
+                                 double* reward, uint8_t* done, int8_t* winner) {
+  RET_IF(gym_players_prepare(h, learners, turn_count && obs && mask, max_turns, "gvec_gym_observe_players"));
+  GymArgs a;
+  memset(&a, 0, sizeof a);
+  a.hdr = h->d_hdr;
+  a.rows = h->d_rows;
+  a.army16 = h->d_army16;
+  a.army32 = h->d_army32;
+  a.turn_count = turn_count;
+  a.obs = obs;
+  a.mask = mask;
+  a.reward = reward;
+  a.done = done;
+  a.winner = winner;
+  a.prev_stats = h->d_gym_prev;
+  a.num_envs = h->cfg.num_envs;
+  a.fd = h->fd;
+  a.row_dw = h->row_dw;
+  a.stride = h->stride;
+  a.player = -1;
+  a.max_turns = max_turns;
+  HIPCHK(launch_gym_observe_players(h->var, a, learners, h->stream));
+  return GVEC_OK;
+}
+
+int32_t gvec_gym_step_players(gvec_handle* h, uint32_t learners, uint64_t agent_seed, const int64_t* gym_actions, const uint8_t* resetting,
+                              int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask, double* reward, uint8_t* terminated,
+                              uint8_t* truncated, int8_t* winner, uint8_t* needs_reset, int64_t* turn_out, uint8_t* invalid, uint8_t* error,
+                              uint8_t* alive) {
+  RET_IF(gym_players_prepare(h, learners, gym_actions && resetting && turn_count && obs && mask, max_turns, "gvec_gym_step_players"));
+  if (!(h->cfg.auto_reset && h->pool_size > 0)) {
+    set_err("gvec_gym_step_players needs auto_reset and a board pool (gvec_build_board_pool): episodes end by re-dealing");
+    return GVEC_E_INVALID;
+  }
+  StepArgs a = base_args(h);
+  a.seed_lo = (uint32_t)agent_seed;
+  a.seed_hi = (uint32_t)(agent_seed >> 32);
+  a.invalid_permille = 0;
+  GymPlayersArgs g;
+  memset(&g, 0, sizeof g);
+  g.gym_actions = gym_actions;
+  g.resetting = resetting;
+  g.turn_io = turn_count;
+  g.turn_out = turn_out;
+  g.obs = obs;
+  g.mask = mask;
+  g.reward = reward;
+  g.invalid = invalid;
+  g.error = error;
+  g.alive = alive;
+  g.terminated = terminated;
+  g.truncated = truncated;
+  g.winner = winner;
+  g.needs_reset = needs_reset;
+  g.prev_stats = h->d_gym_prev;
+  g.learners = learners;
+  g.nl = __builtin_popcount(learners);
+  g.stride = h->stride;
+  g.max_turns = max_turns;
+  HIPCHK(launch_gym_step_players(h->var, a, g, h->stream));
+  h->legal_valid = false;  // the engine's own mask buffer was not refreshed
+  return GVEC_OK;
+}
+
 int32_t gvec_stream_delta_cap(const gvec_handle* h) { return h ? (h->stride / 5 > 1 ? h->stride / 5 : 1) : GVEC_E_INVALID; }
 
 int32_t gvec_stream_deltas(gvec_handle* h, int32_t player, uint8_t* kind, int32_t* count, uint64_t* updates, int32_t mem) {

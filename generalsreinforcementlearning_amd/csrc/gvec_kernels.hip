@@ -8,6 +8,14 @@
 namespace gvec {
 
 constexpr int WAVES_PER_BLOCK = 4;
+// waves per SIMD asked of gym_step_players_kernel, per tile slot count, from a same-process A/B of 5 / 4 / 3 waves at 65,536
+// envs: four up to 448 tiles (20x20 4P 0.86 ms against 0.93 with three, 1.17 with five), three above;
+// -DGYM_PLAYERS_WAVES=n forces one value for A/B builds
+#ifdef GYM_PLAYERS_WAVES
+#define GYM_PLAYERS_WAVES_OF(NSLOT) GYM_PLAYERS_WAVES
+#else
+#define GYM_PLAYERS_WAVES_OF(NSLOT) ((NSLOT) <= 7 ? 4 : 3)
+#endif
 
 // All turn logic runs on PBoard (players packed into register rows, gvec_packed.hpp); Board is the plain
 // layout of the conversion / experience kernels.
@@ -1304,6 +1312,270 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) __attribute__((amdgpu_waves_p
                         G.prev_stats + (size_t)env * 3 * MAXP, true, rs, played, turns, G.max_turns, O);
 }
 
+// =========================================================================================
+// self-play: every learner of a bit set in one launch (gvec_gym_observe_players / gvec_gym_step_players)
+// =========================================================================================
+// gym_bookkeeping's reward for player `pl` alone (the same float64 operations in the same order), against the stats the
+// previous call stored; the caller stores the new stats (gym_store_stats) only after every learner's reward is computed.
+// Lane 0 calls it.
+template <int MAXP>
+__device__ __forceinline__ double gym_player_reward(int pl, int P, uint32_t alive, bool over, int winner, int32_t cur_tc, int32_t cur_ac,
+                                                    const int32_t* prev) {
+  double r = 0.0;
+  r += (double)(cur_tc - prev[pl]) * 1.0;                                         // :540-542
+  r += (double)(cur_ac - prev[MAXP + pl]) * 0.01;                                 // :544-546
+  for (int q = 0; q < P; ++q)                                                     // :548-555
+    if (q != pl && prev[2 * MAXP + q] != 0 && !((alive >> q) & 1u)) r += 50.0;
+  if (over) r = (winner == pl) ? 100.0 : -100.0;                                  // :520-524
+  return r;
+}
+// every player's stats as gym_bookkeeping stores them (tcl / acl: lane p < MAXP holds player p's); every lane calls it
+template <int MAXP>
+__device__ __forceinline__ void gym_store_stats(int32_t* prev, uint32_t tcl, uint32_t acl, uint32_t alive) {
+  const int lane = lane_id();
+  if (lane < MAXP) {
+    prev[lane] = (int32_t)tcl;
+    prev[MAXP + lane] = (int32_t)acl;
+    prev[2 * MAXP + lane] = (int32_t)((alive >> lane) & 1u);
+  }
+}
+__device__ __forceinline__ int gym_winner(bool over, int P, uint32_t alive) {   // Engine.GetWinner
+  return (over && P > 1 && __builtin_popcount(alive) == 1) ? (31 - __builtin_clz(alive)) : -1;
+}
+
+// gvec_gym_observe_players: gym_observe_kernel for every learner of A.player's bit set `learners` (A.player unused):
+// observation [B][L][9][stride], mask [B][L][stride*5], reward [B][L], done / winner [B], then every player's stats.
+template <int MAXP, int NSLOT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_players_kernel(GymArgs A, uint32_t learners) {
+  using B = Board<MAXP, NSLOT>;
+  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  if (env >= A.num_envs) return;
+  B b;
+  load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
+  const bool fog_on = (b.hflags & HF_FOG) != 0u;
+  const int nl = __builtin_popcount(learners);
+  uint32_t own_any = 0u, tcl = 0u;
+#pragma unroll
+  for (int p = 0; p < MAXP; ++p) {
+    own_any |= b.own[p];
+    const uint32_t cnt = (uint32_t)b.count(b.lst[p]);   // PlayerState.tile_count = len(OwnedTiles) (server.go:536): a wave-wide
+    tcl = (lane == p) ? cnt : tcl;                       // reduction, so every lane computes it before the per-lane select
+  }
+  const uint32_t acl = bperm((H_ARMYCNT + (lane & (MAXP - 1))) << 2, b.hv);
+  __shared__ uint32_t mask_stage[WAVES_PER_BLOCK][(NSLOT * 64 * 5 + 15) / 16 * 4];
+  double tcn = (double)A.turn_count[env] / (double)A.max_turns;
+  tcn = tcn < 1.0 ? tcn : 1.0;
+  const bool over = (b.hflags & HF_DONE) != 0u;
+  const int winner = gym_winner(over, b.P, b.alive);
+  const int32_t* prev = A.prev_stats + (size_t)env * 3 * MAXP;
+  int k = 0;
+#pragma unroll 1
+  for (int pl = 0; pl < MAXP; ++pl) {
+    if (!((learners >> pl) & 1u)) continue;                  // wave-uniform
+    uint32_t own_p = 0u, vis_p = 0u;
+#pragma unroll
+    for (int p = 0; p < MAXP; ++p) {
+      own_p = (p == pl) ? b.own[p] : own_p;
+      vis_p = (p == pl) ? b.vis[p] : vis_p;
+    }
+    const uint32_t seen = fog_on ? vis_p : b.valid;
+    const uint32_t src = own_p & seen & b.gt1;
+    const uint32_t m0 = src & b.ok[0], m1 = src & b.ok[1], m2 = src & b.ok[2], m3 = src & b.ok[3], many = m0 | m1 | m2 | m3;
+    const size_t slot = (size_t)env * nl + k;
+    wave_lds_fence();  // the previous learner's mask copy has read the stage
+    gym_emit<NSLOT>(b, seen, own_p, own_any, m0, m1, m2, m3, many, (float)tcn, A.obs + slot * 9 * (size_t)A.stride,
+                    A.mask + slot * 5 * (size_t)A.stride, reinterpret_cast<uint8_t*>(mask_stage[wave]), A.stride);
+    const int32_t cur_tc = (int32_t)rdlane(tcl, pl), cur_ac = (int32_t)rdlane(acl, pl);
+    if (A.reward && lane == 0) A.reward[slot] = gym_player_reward<MAXP>(pl, b.P, b.alive, over, winner, cur_tc, cur_ac, prev);
+    ++k;
+  }
+  if (lane == 0) {
+    if (A.done) A.done[env] = (uint8_t)(over ? 1 : 0);
+    if (A.winner) A.winner[env] = (int8_t)winner;
+  }
+  gym_store_stats<MAXP>(A.prev_stats + (size_t)env * 3 * MAXP, tcl, acl, b.alive);
+}
+
+// gvec_gym_step_players: gym_step_kernel for every learner of a bit set at once.  Each learner's Discrete(N*5) action is
+// decoded against its own proto view exactly as gym_step_kernel decodes the one learner's; the players outside the set are
+// the on-device agent.  A refused action puts NO move in the learner's lane and the env still plays its turn (with several
+// learners one policy's mistake must not freeze the others): always a turn or a re-deal, never a skipped env.  The
+// observation / mask / reward / alive of every learner leave while the board is in registers; every learner's reward is
+// measured before the stats are rewritten (one gym_bookkeeping per learner would measure the second against the first's).
+// With learners = 1 << p this equals gvec_agent_actions + gvec_gym_actions(p) + gvec_step + gvec_gym_finish_step(p) with
+// the refusal rule above (tests/test_selfplay_env.py).
+// (Waves per SIMD: see DESIGN.md §4.6, measured per register layout.)
+template <int MAXP, int NSLOT, bool ODD>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) __attribute__((amdgpu_waves_per_eu(GYM_PLAYERS_WAVES_OF(NSLOT), GYM_PLAYERS_WAVES_OF(NSLOT))))
+void gym_step_players_kernel(StepArgs A, GymPlayersArgs G) {
+  constexpr int FD = 2 * NSLOT - (ODD ? 1 : 0);
+  constexpr int ROW_DW = (Planes<MAXP>::COUNT * FD + 3) / 4 * 4;
+  constexpr int STAGE_DW = (NSLOT * 64 * 5 + 15) / 16 * 4;
+  static_assert(STAGE_DW >= NSLOT * 64, "the stage also serves as the action phase's army shadow");
+  using B = Turn<MAXP, NSLOT>;
+  constexpr int PPR = B::PPR, ROWL = B::ROWL, NR = B::NR;
+  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][STAGE_DW];
+  __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
+  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  if (env >= A.num_envs) return;
+  B b;
+  b.larmy = army_shadow[wave];
+  b.lscr = act_scratch[wave];
+  const ArmyRef army_env = army_ref<NSLOT>(A.army16, A.army32, env);
+  load_turn<true>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
+  b.small = !(b.hflags & HF_WIDE);
+  const uint32_t learners = G.learners;
+  const int nl = G.nl;
+  // player pl's planes, replicated into every row: row pl % PPR of register pl / PPR (pl wave-uniform)
+  auto view = [&](int pl, const uint32_t (&reg)[NR]) {
+    uint32_t out = 0u;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const uint32_t g = bperm((((pl % PPR) * ROWL) + B::col()) << 2, reg[k]);
+      out = (pl / PPR == k) ? g : out;
+    }
+    return out;
+  };
+  const bool rs = uni((int)G.resetting[env]) != 0;
+  const uint32_t alive0 = b.alive;
+  const int P0 = b.P;
+  // ---- every learner's action (gym_step_kernel's decoding, once per learner) ---------------------------------------
+  // lane pl ends up with learner pl's move; refused / invalid / error: bit pl, for learners alive at the start of the step
+  uint32_t l_meta = 0u;
+  int l_ft = 0, l_tt = 0;
+  uint32_t refused = 0u, invalid = 0u, error = 0u;
+  {
+    int k = 0;
+#pragma unroll 1
+    for (int pl = 0; pl < MAXP; ++pl) {
+      if (!((learners >> pl) & 1u)) continue;                // wave-uniform
+      const long long a = (long long)uni64((uint64_t)G.gym_actions[(size_t)env * nl + k]);
+      ++k;
+      const uint32_t seen = (b.hflags & HF_FOG) ? view(pl, b.vis) : b.valid;
+      const uint32_t src = view(pl, b.own) & seen & b.gt1;
+      const long long n5 = 5ll * G.stride;
+      const bool in_range = a >= 0 && a < n5;
+      const int from = in_range ? (int)(a / 5) : 0;
+      const int info = in_range ? (int)(a % 5) : 0;
+      const int fy = (int)(__umul24((uint32_t)from, (uint32_t)b.recipW) >> 16), fx = from - (int)__umul24((uint32_t)fy, (uint32_t)b.W);
+      const bool half = info == 4;
+      int d = half ? 3 : info;
+      if (half) {  // the FIRST of up / right / down / left whose target is on the board (mountains are not checked there)
+        if (fx - 1 >= 0) d = 3;
+        if (fy + 1 < b.H) d = 2;
+        if (fx + 1 < b.W) d = 1;
+        if (fy - 1 >= 0) d = 0;
+      }
+      const uint32_t wsrc = rdlane(src, from >> 5);
+      const uint32_t o0 = rdlane(b.ok[0], from >> 5), o1 = rdlane(b.ok[1], from >> 5), o2 = rdlane(b.ok[2], from >> 5), o3 = rdlane(b.ok[3], from >> 5);
+      const uint32_t bit = 1u << (from & 31);
+      const bool s_ok = (wsrc & bit) != 0u;
+      const bool k0 = s_ok && (o0 & bit), k1 = s_ok && (o1 & bit), k2 = s_ok && (o2 & bit), k3 = s_ok && (o3 & bit);
+      const bool kinfo = (info == 0) ? k0 : (info == 1) ? k1 : (info == 2) ? k2 : (info == 3) ? k3 : (k0 || k1 || k2 || k3);
+      const bool valid = in_range && kinfo;
+      const bool kd = (d == 0) ? k0 : (d == 1) ? k1 : (d == 2) ? k2 : k3;
+      const bool accepted = valid && kd;   // the server validates the move it received (action_validator.go:114-139)
+      const int tt = from + ((d == 0) ? -b.W : (d == 1) ? 1 : (d == 2) ? b.W : -1);
+      l_meta = (lane == pl) ? (accepted ? (16u | (half ? 32u : 0u)) : 0u) : l_meta;
+      l_ft = (lane == pl) ? from : l_ft;
+      l_tt = (lane == pl) ? tt : l_tt;
+      const bool counted = !rs && pl < P0 && ((alive0 >> pl) & 1u) != 0u;
+      if (counted && !accepted) refused |= 1u << pl;
+      if (counted && !valid) invalid |= 1u << pl;
+      if (counted && valid && !accepted) error |= 1u << pl;
+    }
+  }
+  // ---- the turn: always played (or the env re-dealt) ------------------------------------------------------------------
+  {
+    uint32_t err = 0u;
+    bool types_dirty = false;
+    if ((b.hflags & HF_DONE) || rs) {
+      redeal<MAXP, NSLOT>(b, A, env, FD, ROW_DW);
+      types_dirty = true;
+    } else {
+      uint32_t m[NR][4];
+      b.template legal_planes<false>(m);
+      const uint32_t mine = agent_sample<MAXP, NSLOT>(b, m, env_key_of(A.seed_base, (uint32_t)env), A);
+      typename B::ActVec av = agent_actvec<MAXP, NSLOT>(b, mine, A.invalid_permille > 0);
+      const bool is_learner = lane < MAXP && ((learners >> (lane & 31)) & 1u) != 0u;
+      av.meta = is_learner ? l_meta : av.meta;
+      av.ft = is_learner ? l_ft : av.ft;
+      av.tt = is_learner ? l_tt : av.tt;
+      bool aborted;
+      err = b.turn_step(av, A, aborted);
+      b.refresh_gt1();
+      b.hdr_set(H_CNT_STEPS, b.hdr_get(H_CNT_STEPS) + 1u);
+      if (aborted) b.hdr_set(H_CNT_ABORT, b.hdr_get(H_CNT_ABORT) + 1u);
+      if (b.hflags & HF_DONE) b.hdr_set(H_CNT_DONE, b.hdr_get(H_CNT_DONE) + 1u);
+    }
+    b.store_army_staged(army_env);
+    b.settle_lists();
+    b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
+    if (types_dirty) b.store_planes(A.rows + (size_t)env * ROW_DW, FD, ROW_DW, true);
+    else b.store_planes_staged(A.rows + (size_t)env * ROW_DW, FD);
+    if (A.err && lane == 0) A.err[env] = (int32_t)err;
+  }
+  // ---- every learner's observation, mask, reward, alive; the env's flags -------------------------------------------------
+  uint32_t own_any = 0u;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) own_any |= b.own[k];
+  own_any = B::or_rows(own_any);
+  uint32_t tcl = 0u;   // per-player len(OwnedTiles): row totals in the rows' last lanes, handed to lane p
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const uint32_t sc = row_scan_add<ROWL>((uint32_t)__builtin_popcount(b.lst[k]));
+    const uint32_t got = bperm((((lane % PPR) * ROWL) + ROWL - 1) << 2, sc);
+    tcl = (lane / PPR == k) ? got : tcl;
+  }
+  const uint32_t acl = bperm((H_ARMYCNT + (lane & (MAXP - 1))) << 2, b.hv);
+  const bool over = (b.hflags & HF_DONE) != 0u;
+  const int winner = gym_winner(over, b.P, b.alive);
+  const int64_t turns = rs ? 0 : G.turn_io[env] + 1;
+  double tcn = (double)turns / (double)G.max_turns;
+  tcn = tcn < 1.0 ? tcn : 1.0;
+  const int32_t* prev = G.prev_stats + (size_t)env * 3 * MAXP;
+  {
+    int k = 0;
+#pragma unroll 1
+    for (int pl = 0; pl < MAXP; ++pl) {
+      if (!((learners >> pl) & 1u)) continue;                // wave-uniform
+      const uint32_t own_p = view(pl, b.own);
+      const uint32_t seen = (b.hflags & HF_FOG) ? view(pl, b.vis) : b.valid;
+      const uint32_t src = own_p & seen & b.gt1;
+      const uint32_t m0 = src & b.ok[0], m1 = src & b.ok[1], m2 = src & b.ok[2], m3 = src & b.ok[3], many = m0 | m1 | m2 | m3;
+      const size_t slot = (size_t)env * nl + k;
+      wave_lds_fence();  // the staged state stores above / the previous learner's mask copy have read the stage
+      gym_emit<NSLOT>(b, seen, own_p, own_any, m0, m1, m2, m3, many, (float)tcn, G.obs + slot * 9 * (size_t)G.stride,
+                      G.mask + slot * 5 * (size_t)G.stride, reinterpret_cast<uint8_t*>(army_shadow[wave]), G.stride);
+      const int32_t cur_tc = (int32_t)rdlane(tcl, pl), cur_ac = (int32_t)rdlane(acl, pl);
+      if (lane == 0) {
+        const bool ref = ((refused >> pl) & 1u) != 0u;
+        if (G.reward) {
+          const double r = gym_player_reward<MAXP>(pl, b.P, b.alive, over, winner, cur_tc, cur_ac, prev);
+          G.reward[slot] = rs ? 0.0 : (ref ? r - 0.1 : r);    // :226-241: a refused action costs -0.1
+        }
+        if (G.invalid) G.invalid[slot] = (uint8_t)((invalid >> pl) & 1u);
+        if (G.error) G.error[slot] = (uint8_t)((error >> pl) & 1u);
+        if (G.alive) G.alive[slot] = (uint8_t)((b.alive >> pl) & 1u);
+      }
+      ++k;
+    }
+  }
+  if (lane == 0) {
+    // :243-259 terminated = game over, truncated = turn limit; the turn counts as played whenever the env was not re-dealt
+    const bool term = over && !rs, trunc = turns >= (int64_t)G.max_turns && !rs;
+    if (G.winner) G.winner[env] = (int8_t)(term ? winner : -1);
+    G.turn_io[env] = turns;
+    if (G.turn_out) G.turn_out[env] = turns;
+    if (G.terminated) G.terminated[env] = (uint8_t)(term ? 1 : 0);
+    if (G.truncated) G.truncated[env] = (uint8_t)(trunc ? 1 : 0);
+    if (G.needs_reset) G.needs_reset[env] = (uint8_t)((term || trunc) ? 1 : 0);
+  }
+  gym_store_stats<MAXP>(G.prev_stats + (size_t)env * 3 * MAXP, tcl, acl, b.alive);
+}
+
 // GeneralsEnv.step's action handling for player `player` of every env (one thread per env):
 // :226-241 an action the mask rejects is not submitted (the env sits the call out: GVEC_ACT_SKIP_ENV);
 // _action_index_to_game_action :389-441 (a half move, index 4, takes the FIRST of up / right / down / left whose
@@ -2328,6 +2600,25 @@ hipError_t launch_gym_step(const Variant& v, const StepArgs& in, const GymStepAr
     const dim3 grid = wave_grid(a.num_envs), block(64 * WAVES_PER_BLOCK);
     if (odd) hipLaunchKernelGGL((gym_step_kernel<P, S, true>), grid, block, 0, s, a, g);
     else hipLaunchKernelGGL((gym_step_kernel<P, S, false>), grid, block, 0, s, a, g);
+    return hipGetLastError();
+  });
+}
+hipError_t launch_gym_observe_players(const Variant& v, const GymArgs& a, uint32_t learners, hipStream_t s) {
+  return dispatch(v, [&](auto P_, auto S_) {
+    hipLaunchKernelGGL((gym_observe_players_kernel<decltype(P_)::value, decltype(S_)::value>), wave_grid(a.num_envs),
+                       dim3(64 * WAVES_PER_BLOCK), 0, s, a, learners);
+    return hipGetLastError();
+  });
+}
+hipError_t launch_gym_step_players(const Variant& v, const StepArgs& in, const GymPlayersArgs& g, hipStream_t s) {
+  const StepArgs a = with_seed_bases(in);
+  return dispatch(v, [&](auto P_, auto S_) {
+    constexpr int P = decltype(P_)::value, S = decltype(S_)::value;
+    const bool odd = a.fd == 2 * S - 1;
+    if ((!odd && a.fd != 2 * S) || a.row_dw != (Planes<P>::COUNT * a.fd + 3) / 4 * 4) return hipErrorInvalidValue;
+    const dim3 grid = wave_grid(a.num_envs), block(64 * WAVES_PER_BLOCK);
+    if (odd) hipLaunchKernelGGL((gym_step_players_kernel<P, S, true>), grid, block, 0, s, a, g);
+    else hipLaunchKernelGGL((gym_step_players_kernel<P, S, false>), grid, block, 0, s, a, g);
     return hipGetLastError();
   });
 }

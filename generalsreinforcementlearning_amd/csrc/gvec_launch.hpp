@@ -187,6 +187,27 @@ struct GymStepArgs {
   int32_t* prev_stats;         // [B][3*MAXP], as GymArgs
   int32_t stride, player, max_turns;
 };
+// gvec_gym_step_players: gym_step_kernel for every learner of a bit set (gym_step_players_kernel).  L = popcount(learners);
+// per-learner arrays hold the learners in ascending player id
+struct GymPlayersArgs {
+  const int64_t* gym_actions;  // [B][L] indices into Discrete(board_size * 5)
+  const uint8_t* resetting;    // [B] needs_reset of the previous step
+  int64_t* turn_io;            // [B] in / out: GeneralsEnv.turn_count
+  int64_t* turn_out;           // [B] out or null
+  float* obs;                  // [B][L][9][stride]
+  uint8_t* mask;               // [B][L][stride*5]
+  double* reward;              // [B][L] outputs, any may be null
+  uint8_t* invalid;            // [B][L]
+  uint8_t* error;              // [B][L]
+  uint8_t* alive;              // [B][L]
+  uint8_t* terminated;         // [B]
+  uint8_t* truncated;          // [B]
+  int8_t* winner;              // [B]
+  uint8_t* needs_reset;        // [B]
+  int32_t* prev_stats;         // [B][3*MAXP], as GymArgs
+  uint32_t learners;
+  int32_t nl, stride, max_turns;
+};
 // gvec_stream_deltas: createStreamUpdate's delta for one player's stream (server.go:636-777)
 struct StreamDeltaArgs {
   const uint32_t* hdr;
@@ -211,6 +232,9 @@ hipError_t launch_pool_collect(const gvec_collect_args& a, hipStream_t s);
 size_t pool_collect_scratch_bytes(int32_t num_envs);
 hipError_t launch_gym_step(const Variant& v, const StepArgs& a, const GymStepArgs& g, hipStream_t s);
 hipError_t launch_gym_observe(const Variant& v, const GymArgs& a, hipStream_t s);
+hipError_t launch_gym_step_players(const Variant& v, const StepArgs& a, const GymPlayersArgs& g, hipStream_t s);
+// gym_observe for every learner of `learners` (a.player unused): obs / mask / reward [B][L], done / winner [B]
+hipError_t launch_gym_observe_players(const Variant& v, const GymArgs& a, uint32_t learners, hipStream_t s);
 hipError_t launch_gym_actions(const GymActArgs& a, hipStream_t s);
 hipError_t launch_snapshot(const Variant& v, const ExperienceArgs& a, hipStream_t s);
 hipError_t launch_rewards(const Variant& v, const ExperienceArgs& a, hipStream_t s);

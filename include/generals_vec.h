@@ -447,6 +447,30 @@ int32_t gvec_gym_step(gvec_handle* h, int32_t player, uint64_t agent_seed, const
                       uint8_t* truncated, int8_t* winner, uint8_t* needs_reset, int64_t* turn_out, uint8_t* played,
                       uint8_t* invalid, uint8_t* error);
 
+/* Self-play: the gym calls for every learner of the bit set `learners` at once (bits below max_players; L = popcount,
+ * per-learner arrays hold the learners in ascending player id: gym_actions / reward / invalid / error / alive [B][L],
+ * obs [B][L][9][tile_stride], mask [B][L][tile_stride*5], every other array [B]).
+ * gvec_gym_observe_players: gvec_gym_observe for each learner (the observation after a reset): obs, mask and reward per
+ *   learner, done / winner per env, then every player's stats; plays no turn.  reward / done / winner may be NULL.
+ * gvec_gym_step_players: gvec_gym_step for every learner in ONE launch.  Each learner's action is decoded against its own
+ *   proto view as gvec_gym_step decodes the one learner's; the other players move like the on-device agent.  A refused
+ *   action puts NO move in the learner's slot and the env still plays its turn (gvec_gym_step makes the env sit the call
+ *   out instead): invalid / error [B][L] flag it and the learner's reward is _calculate_reward - 0.1.  A learner that is
+ *   eliminated at the start of the step, or whose id is not below the env's player count, keeps invalid / error 0 and no
+ *   penalty.  turn_count := resetting ? 0 : turn_count + 1; terminated / truncated / needs_reset / winner as gvec_gym_step
+ *   with the turn played; reward 0 in a re-dealt (resetting) env; alive [B][L] = the learner's Player.Alive after the
+ *   step.  With learners = 1 << p and every action accepted this equals gvec_gym_step(p) output for output.  Needs
+ *   auto_reset and a board pool; plain handles only.  gym_actions / resetting / turn_count / obs / mask are required,
+ *   every other output may be NULL.
+ * Both share the stored player stats with gvec_gym_observe / gvec_gym_step: mixing single-learner and self-play calls on
+ * one handle is consistent, because every one of them stores every player's stats. */
+int32_t gvec_gym_observe_players(gvec_handle* h, uint32_t learners, const int64_t* turn_count, int32_t max_turns,
+                                 float* obs, uint8_t* mask, double* reward, uint8_t* done, int8_t* winner);
+int32_t gvec_gym_step_players(gvec_handle* h, uint32_t learners, uint64_t agent_seed, const int64_t* gym_actions,
+                              const uint8_t* resetting, int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask,
+                              double* reward, uint8_t* terminated, uint8_t* truncated, int8_t* winner, uint8_t* needs_reset,
+                              int64_t* turn_out, uint8_t* invalid, uint8_t* error, uint8_t* alive);
+
 /* The collection loop around GeneralsEnv.step, resident on the device: one iteration of every worker's
  * ParallelEnvPool._run_episode (python/generals_gym/vector_env.py:164-192) plus ReplayBuffer.push
  * (python/generals_gym/replay_buffer.py:31-36) for num_envs workers, on the outputs of one gvec_gym_step, without a byte
