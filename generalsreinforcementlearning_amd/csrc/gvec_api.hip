@@ -1761,6 +1761,87 @@ int32_t gvec_import_records(gvec_handle* h, int32_t env_begin, int32_t n, const 
   return check_status(h, "gvec_import_records");
 }
 
+int32_t gvec_copy_envs(gvec_handle* dst, const int32_t* dst_ids, gvec_handle* src, const int32_t* src_ids, int32_t n) {
+  if (!dst) return GVEC_E_INVALID;
+  if (!src) src = dst;
+  if (n < 0) {
+    set_err("gvec_copy_envs: n = %d", n);
+    return GVEC_E_INVALID;
+  }
+  if (dst->sharded() || src->sharded()) return sharded::unsupported("gvec_copy_envs");
+  if (n == 0) return GVEC_OK;
+  // the same variant, plane stride and army block on both sides, and the same rules for the state to play under
+  const gvec_config &dc = dst->cfg, &sc = src->cfg;
+  const char* field = dc.device != sc.device ? "device"
+                      : dc.max_width != sc.max_width ? "max_width"
+                      : dc.max_height != sc.max_height ? "max_height"
+                      : dc.max_players != sc.max_players ? "max_players"
+                      : dc.prod_general != sc.prod_general ? "prod_general"
+                      : dc.prod_city != sc.prod_city ? "prod_city"
+                      : dc.prod_normal != sc.prod_normal ? "prod_normal"
+                      : dc.normal_growth_interval != sc.normal_growth_interval ? "normal_growth_interval"
+                      : nullptr;
+  if (field) {
+    set_err("gvec_copy_envs: the handles differ in %s", field);
+    return GVEC_E_INVALID;
+  }
+  HIPCHK(hipSetDevice(dc.device));
+  const size_t prev_bytes = (size_t)dc.num_envs * 3 * dst->var.maxp * 4;
+  if (src->d_gym_prev && !dst->d_gym_prev) {
+    HIPCHK(hipMalloc(&dst->d_gym_prev, prev_bytes));
+    HIPCHK(hipMemsetAsync(dst->d_gym_prev, 0, prev_bytes, dst->stream));
+  }
+  if (src->d_snap && !dst->d_snap) RET_IF(ensure_snapshots(dst));
+  int snap_dw = 0, record_dw = 0;
+  experience_layout(dst->var, dst->fd, &snap_dw, &record_dw);
+  CopyArgs a;
+  memset(&a, 0, sizeof a);
+  a.d_hdr = dst->d_hdr;
+  a.d_rows = dst->d_rows;
+  a.d_army16 = dst->d_army16;
+  a.d_army32 = dst->d_army32;
+  a.d_prev = dst->d_gym_prev;
+  a.d_snap = dst->d_snap;
+  a.s_hdr = src->d_hdr;
+  a.s_rows = src->d_rows;
+  a.s_army16 = src->d_army16;
+  a.s_army32 = src->d_army32;
+  a.s_prev = src->d_gym_prev;
+  a.s_snap = src->d_snap;
+  a.dst_ids = dst_ids;
+  a.src_ids = src_ids;
+  a.n = n;
+  a.dst_envs = dc.num_envs;
+  a.src_envs = sc.num_envs;
+  a.row_dw = dst->row_dw;
+  a.army_dw = dst->army_dw;
+  a.prev_dw = 3 * dst->var.maxp;
+  a.snap_dw = snap_dw;
+  a.status = dst->d_status;
+  // ordered after the work already enqueued on src's stream; src's next call waits for the copy in turn
+  const bool cross = src != dst && src->stream != dst->stream;
+  hipEvent_t ev = nullptr;
+  if (cross) {
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, src->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
+    if (e != hipSuccess) {
+      (void)hipEventDestroy(ev);
+      HIPCHK(e);
+    }
+  }
+  hipError_t e = launch_copy_envs(a, dst->stream);
+  if (cross) {
+    if (e == hipSuccess) e = hipEventRecord(ev, dst->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev, 0);
+    (void)hipEventDestroy(ev);  // released once the recorded work completes
+  }
+  HIPCHK(e);
+  // the per-turn agent samples from d_legal: the copied rows of it are stale
+  dst->legal_valid = false;
+  return check_status(dst, "gvec_copy_envs");
+}
+
 int32_t gvec_read_buffer(gvec_handle* h, int32_t which, uint64_t byte_offset, uint64_t bytes, void* host_dst) {
   if (!h || !host_dst) return GVEC_E_INVALID;
   if (h->sharded()) return sharded::unsupported("gvec_read_buffer");

@@ -2194,6 +2194,62 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void records_kernel(RecordArg
 }
 
 // =========================================================================================
+// gvec_copy_envs: env dst_ids[i] of one handle becomes env src_ids[i] of another (or of the same) handle, one wave per
+// pair.  Every block of the resident layout is moved as it is stored, in 16-byte pieces: the 96-byte header (less the
+// slot's lifetime counters), the planes block (row_dw is a multiple of 4), the army block in the form the source header
+// names (narrow NSLOT*128 bytes or wide NSLOT*256 bytes, the destination's block of the same form), then the small
+// per-env rows of the gym reward baseline and the experience snapshot in dwords.  Plain stores: the destination lines
+// stay in L2 for the step that usually follows.
+// =========================================================================================
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void copy_envs_kernel(CopyArgs A) {
+  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  if (i >= A.n) return;
+  const int d = uni(A.dst_ids ? A.dst_ids[i] : i), s = uni(A.src_ids ? A.src_ids[i] : i);
+  if (d < 0 || d >= A.dst_envs || s < 0 || s >= A.src_envs) {
+    if (lane == 0) atomicExch(A.status, GVEC_E_RANGE);
+    return;
+  }
+  // header: six pieces; the last one holds H_RECIPW and the three H_CNT_* words, which stay the destination's
+  static_assert(HDR_DW == 24 && H_RECIPW == 20 && H_CNT_STEPS == 21 && H_CNT_DONE == 23, "copy_envs_kernel: header layout");
+  const u32x4* sh = reinterpret_cast<const u32x4*>(A.s_hdr + (size_t)s * HDR_DW);
+  u32x4* dh = reinterpret_cast<u32x4*>(A.d_hdr + (size_t)d * HDR_DW);
+  const bool wide = ((A.s_hdr[(size_t)s * HDR_DW + H_DIMS] >> 24) & HF_WIDE) != 0u;
+  if (lane < HDR_DW / 4) {
+    u32x4 v = sh[lane];
+    if (lane == HDR_DW / 4 - 1) {
+      const u32x4 keep = dh[lane];
+      v.y = keep.y;
+      v.z = keep.z;
+      v.w = keep.w;
+    }
+    dh[lane] = v;
+  }
+  {
+    const u32x4* sr = reinterpret_cast<const u32x4*>(A.s_rows + (size_t)s * A.row_dw);
+    u32x4* dr = reinterpret_cast<u32x4*>(A.d_rows + (size_t)d * A.row_dw);
+    for (int k = lane; k < A.row_dw / 4; k += 64) dr[k] = sr[k];
+  }
+  if (wide) {
+    const u32x4* sa = reinterpret_cast<const u32x4*>(A.s_army32 + (size_t)s * A.army_dw);
+    u32x4* da = reinterpret_cast<u32x4*>(A.d_army32 + (size_t)d * A.army_dw);
+    for (int k = lane; k < A.army_dw / 4; k += 64) da[k] = sa[k];
+  } else {
+    const u32x4* sa = reinterpret_cast<const u32x4*>(A.s_army16 + (size_t)s * (A.army_dw / 2));
+    u32x4* da = reinterpret_cast<u32x4*>(A.d_army16 + (size_t)d * (A.army_dw / 2));
+    for (int k = lane; k < A.army_dw / 8; k += 64) da[k] = sa[k];
+  }
+  if (A.d_prev) {  // a source without the row reads as zeros
+    int32_t* dp = A.d_prev + (size_t)d * A.prev_dw;
+    for (int k = lane; k < A.prev_dw; k += 64) dp[k] = A.s_prev ? A.s_prev[(size_t)s * A.prev_dw + k] : 0;
+  }
+  if (A.d_snap) {
+    uint32_t* dsn = A.d_snap + (size_t)d * A.snap_dw;
+    for (int k = lane; k < A.snap_dw; k += 64) dsn[k] = A.s_snap ? A.s_snap[(size_t)s * A.snap_dw + k] : 0u;
+  }
+}
+
+// =========================================================================================
 // map generator: algorithm and ratios of mapgen/generator.go:25-253 on the counter RNG.
 // One thread per board (reset-time work, sequential by nature); mirrored by ora_mapgen.
 // =========================================================================================
@@ -2704,6 +2760,11 @@ hipError_t launch_records(const Variant& v, const RecordArgs& a, bool import, hi
     else hipLaunchKernelGGL((records_kernel<P, S, false>), wave_grid(a.n), dim3(64 * WAVES_PER_BLOCK), 0, s, a);
     return hipGetLastError();
   });
+}
+hipError_t launch_copy_envs(const CopyArgs& a, hipStream_t s) {
+  if (a.row_dw % 4 != 0 || a.army_dw % 8 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(copy_envs_kernel, wave_grid(a.n), dim3(64 * WAVES_PER_BLOCK), 0, s, a);
+  return hipGetLastError();
 }
 hipError_t launch_mapgen(const MapgenArgs& a, hipStream_t s) {
   if (a.go_seeds) hipLaunchKernelGGL(mapgen_go_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);

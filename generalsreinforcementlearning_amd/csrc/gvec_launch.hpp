@@ -89,6 +89,26 @@ struct RecordArgs {
   int32_t* status;
 };
 
+// gvec_copy_envs: env dst_ids[i] of the destination arrays <- env src_ids[i] of the source arrays, i < n
+struct CopyArgs {
+  uint32_t* d_hdr;
+  uint32_t* d_rows;
+  uint32_t* d_army16;
+  int32_t* d_army32;
+  int32_t* d_prev;   // [dst_envs][prev_dw] gym reward baseline, or null (the destination has none)
+  uint32_t* d_snap;  // [dst_envs][snap_dw] experience snapshots, or null
+  const uint32_t* s_hdr;
+  const uint32_t* s_rows;
+  const uint32_t* s_army16;
+  const int32_t* s_army32;
+  const int32_t* s_prev;   // null: the source has none (the destination row gets zeros)
+  const uint32_t* s_snap;
+  const int32_t* dst_ids;  // [n] device, or null = 0..n-1
+  const int32_t* src_ids;
+  int32_t n, dst_envs, src_envs, row_dw, army_dw, prev_dw, snap_dw;
+  int32_t* status;  // GVEC_E_RANGE when a pair names an env outside its handle (that pair is skipped)
+};
+
 struct MapgenArgs {
   int32_t* army;   // [n][stride]
   int8_t* owner;
@@ -244,6 +264,7 @@ hipError_t launch_import(const Variant& v, const ImportArgs& a, hipStream_t s);
 hipError_t launch_setup(const Variant& v, const ImportArgs& a, hipStream_t s);
 hipError_t launch_export(const Variant& v, const ExportArgs& a, hipStream_t s);
 hipError_t launch_records(const Variant& v, const RecordArgs& a, bool import, hipStream_t s);
+hipError_t launch_copy_envs(const CopyArgs& a, hipStream_t s);
 hipError_t launch_mapgen(const MapgenArgs& a, hipStream_t s);
 // sums the H_CNT_* counters of all envs into out[3] (u64, device)
 hipError_t launch_counter_sum(const uint32_t* hdr, int32_t num_envs, unsigned long long* out, hipStream_t s);

@@ -16,13 +16,15 @@ as in GeneralsVecEnv.
 """
 import numpy as np
 
+from .env_state import EnvStateMixin
 from .vec_engine import VecEngine
 from ._lib import check
 
 
-class GeneralsSelfPlayVecEnv:
+class GeneralsSelfPlayVecEnv(EnvStateMixin):
     """B boards with L learners each behind the (gymnasium-style) vector API:
-    reset() -> (obs [B, L, 9, H, W], info);  step(actions [B, L]) -> (obs, reward [B, L], terminated [B], truncated [B], info)."""
+    reset() -> (obs [B, L, 9, H, W], info);  step(actions [B, L]) -> (obs, reward [B, L], terminated [B], truncated [B], info).
+    copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, learners=None, fog_of_war=True, max_turns=500,
                  seed=0, device=0, board_pool=1024, device_outputs=False):
@@ -89,6 +91,12 @@ class GeneralsSelfPlayVecEnv:
         self._d_turn.zero_()
         for b in self._d_step:
             b["needs_reset"].zero_()
+        return self._observe_info()
+
+    def _learner_ids(self):
+        return list(self.player_ids)
+
+    def _observe_info(self):
         self._obs_flip ^= 1
         obs, mask = self._d_obs[self._obs_flip], self._d_mask[self._obs_flip]
         e = self.engine
@@ -155,6 +163,7 @@ class GeneralsSelfPlayVecEnv:
             self._seed = seed
         self.engine.reset_generated(self._seed * 1000003 + 17)
         self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
+        self._pool_key = (self._pool, self._seed * 7919 + 5)
         obs, info = self._reset_device()
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 

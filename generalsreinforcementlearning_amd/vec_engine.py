@@ -84,6 +84,7 @@ class VecEngine:
             check(self.L.gvec_create(C.byref(cfg), C.byref(self.h)), "gvec_create")
         self.B, self.max_w, self.max_h, self.max_p = num_envs, width, height, players
         self.device = int(device)          # the device of a plain handle (a sharded one: see `devices`)
+        self.fog_of_war, self.production, self.normal_growth_interval = bool(fog_of_war), tuple(production), normal_growth_interval
         self.stride = self.L.gvec_tile_stride(self.h)
         self.mask_bytes = self.L.gvec_mask_bytes(self.h)
         if stream is not None:
@@ -110,6 +111,7 @@ class VecEngine:
         v = object.__new__(VecEngine)
         v.L, v.h, v._owned = self.L, child, False
         v.B, v.max_w, v.max_h, v.max_p, v.stride, v.mask_bytes = n.value, self.max_w, self.max_h, self.max_p, self.stride, self.mask_bytes
+        v.device = dev.value
         return v, begin.value, n.value, dev.value
 
     def gather_experience_records(self, n, shard_env_begin=0, env_id_base=0, dst_device_ptr=None, dst_device=0):
@@ -130,6 +132,7 @@ class VecEngine:
 
     def set_stream(self, hip_stream):
         check(self.L.gvec_set_stream(self.h, C.c_void_p(int(hip_stream))))
+        self._stream = int(hip_stream)
 
     def synchronize(self):
         check(self.L.gvec_synchronize(self.h))
@@ -382,6 +385,41 @@ class VecEngine:
     def import_records(self, src_device_ptr, env_begin=0, n=None):
         n = self.B - env_begin if n is None else n
         check(self.L.gvec_import_records(self.h, env_begin, n, C.c_void_p(int(src_device_ptr))), "gvec_import_records")
+
+    def _device_ids(self, ids):
+        """ids -> (contiguous int32 CUDA tensor on this engine's device, or None; its length)."""
+        if ids is None:
+            return None, None
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype not in (torch.int32, torch.int64):
+                raise GvecError(-1, f"copy_envs: env ids must be int32 or int64, not {ids.dtype}")
+            t = ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            if t is not ids and getattr(self, "_stream", None):
+                t.record_stream(torch.cuda.ExternalStream(self._stream, device=dev))   # a temporary the launch still reads
+        else:
+            t = torch.as_tensor(np.ascontiguousarray(ids, np.int32).reshape(-1)).to(dev)
+            if getattr(self, "_stream", None):
+                t.record_stream(torch.cuda.ExternalStream(self._stream, device=dev))
+        return t, t.numel()
+
+    def copy_envs(self, dst_ids=None, src_ids=None, n=None, src=None):
+        """Env dst_ids[i] of this engine becomes exactly what env src_ids[i] of `src` (another VecEngine with the same
+        max size, players and production constants on the same device; None = this engine) is, for i < n
+        (gvec_copy_envs).  ids: CUDA int32 / int64 tensors, numpy arrays, lists, or None = 0..n-1; n defaults to the ids'
+        length, else to the smaller batch.  src_ids may repeat (fan-out); dst_ids must be distinct and, within one engine,
+        disjoint from src_ids.  The slot keeps its lifetime counters.  Enqueued on this engine's stream."""
+        other = self if src is None else src
+        d, nd = self._device_ids(dst_ids)
+        s, ns = self._device_ids(src_ids)
+        if n is None:
+            n = nd if nd is not None else ns if ns is not None else min(self.B, other.B)
+        n = int(n)
+        for name, k in (("dst_ids", nd), ("src_ids", ns)):
+            if k is not None and k < n:
+                raise GvecError(-1, f"copy_envs: {name} holds {k} ids, fewer than n = {n}")
+        check(self.L.gvec_copy_envs(self.h, _ptr(d), None if src is None else other.h, _ptr(s), n), "gvec_copy_envs")
 
     def device_buffer(self, which):
         return self.L.gvec_device_buffer(self.h, which)

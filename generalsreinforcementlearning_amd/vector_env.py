@@ -27,13 +27,15 @@ because a vector env cannot wait for a per-env reset() call.
 """
 import numpy as np
 
+from .env_state import EnvStateMixin
 from .vec_engine import VecEngine
 from ._lib import check
 
 
-class GeneralsVecEnv:
+class GeneralsVecEnv(EnvStateMixin):
     """B GeneralsEnv instances behind the (gymnasium-style) vector API:
-    reset() -> (obs, info);  step(actions[B]) -> (obs, reward, terminated, truncated, info)."""
+    reset() -> (obs, info);  step(actions[B]) -> (obs, reward, terminated, truncated, info).
+    copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, fog_of_war=True, max_turns=500,
                  seed=0, device=0, board_pool=1024, device_outputs=False):
@@ -102,8 +104,14 @@ class GeneralsVecEnv:
         self._d_turn.zero_()
         for b in self._d_step:
             b["needs_reset"].zero_()
-        obs = self._gym_observe()          # also stores the stats the first step's reward is measured against
+        return self._observe_info()        # also stores the stats the first step's reward is measured against
+
+    def _observe_info(self):
+        obs = self._gym_observe()
         return obs, {"player_id": self.player_id, "valid_actions_mask": self.valid_actions_mask, "turn": self._d_turn.clone()}
+
+    def _learner_ids(self):
+        return [self.player_id]
 
     def _step_args(self, k, flip):
         """The pointer arguments of gvec_gym_step for step number k (mod 3) writing observation buffer `flip`: computed once
@@ -196,6 +204,7 @@ class GeneralsVecEnv:
             self._seed = seed
         self.engine.reset_generated(self._seed * 1000003 + 17)
         self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
+        self._pool_key = (self._pool, self._seed * 7919 + 5)
         obs, info = self._reset_device()
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 

@@ -515,6 +515,26 @@ int32_t gvec_export_records(gvec_handle* h, int32_t env_begin, int32_t n,
                             void* dst_device);
 int32_t gvec_import_records(gvec_handle* h, int32_t env_begin, int32_t n,
                             const void* src_device);
+/* Env dst_ids[i] of dst becomes exactly what env src_ids[i] of src is, for i < n: on-device clone / save / restore of env
+ * states (search fan-out, checkpoints, rewinds) by one gather/scatter launch over the resident blocks.
+ *   - src == NULL means src = dst.  dst_ids / src_ids are DEVICE int32 arrays on the handles' device; NULL = 0..n-1.
+ *   - n == 0 is a no-op; n < 0 or dst == NULL: GVEC_E_INVALID.
+ *   - Both handles must be plain (a sharded handle: GVEC_E_INVALID - copy between gvec_shard children; no call moves board
+ *     state between devices), on the same device, with the same max_width, max_height, max_players and the same four
+ *     production constants (prod_general, prod_city, prod_normal, normal_growth_interval).  Otherwise GVEC_E_INVALID, a
+ *     gvec_last_error message naming the field, and nothing is launched.
+ *   - Copied per pair: the header except the slot's lifetime counters (H_CNT_*: gvec_counters keeps counting the turns
+ *     played in THIS handle), the whole planes block, the armies in the source's form, the gym reward baseline row
+ *     (zeros when src never made one; allocated in dst when src has one and dst not) and the experience snapshot row
+ *     (same rule).  Afterwards every call on dst behaves as if env dst_ids[i] had always held the state.  Draws keyed by
+ *     env index stay keyed by the DESTINATION index (the on-device agent, the board pool's re-deal).
+ *   - A pair naming an env outside [0, num_envs) of its handle is skipped and the call returns GVEC_E_RANGE (checked on
+ *     the device, like gvec_import_records).
+ *   - src_ids may repeat (fan-out); dst_ids must be distinct; with src == dst no env may be both a source and a destination
+ *     of one call.  Neither is checked: the result is undefined otherwise.
+ *   - Enqueued on dst's stream, after the work already enqueued on src's stream; src's stream then waits for the copy, so
+ *     src's next call cannot overwrite a source mid-copy.  Synchronises dst's stream (the range check). */
+int32_t gvec_copy_envs(gvec_handle* dst, const int32_t* dst_ids, gvec_handle* src, const int32_t* src_ids, int32_t n);
 /* Zero-copy access for device consumers (torch-ROCm): the handle's resident device
  * arrays.  which: 0 header [B][24] u32, 1 bit-planes (the OwnedTiles planes at the end of an env's block are
  * meaningful only while its header flag bit 7 is set; otherwise the lists are the ownership planes - DESIGN.md
