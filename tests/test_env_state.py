@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _harness as H
+import _state_forms as F
 
 B = 64
 HF_WIDE, HF_LDIFF = 4, 128
@@ -59,18 +60,6 @@ def test_env_state_methods_exist_and_envs_still_need_a_gpu():
 
 
 # ---- engine level -----------------------------------------------------------------------------------------------------
-class _RawDeviceArray:
-    def __init__(self, ptr, n_u32):
-        self.__cuda_array_interface__ = {"shape": (n_u32,), "typestr": "<u4", "data": (int(ptr), False), "version": 2}
-
-
-def _header_flags(eng):
-    import torch
-    eng.synchronize()
-    t = torch.as_tensor(_RawDeviceArray(eng.device_buffer(0), eng.B * 24), device="cuda")
-    return t.cpu().numpy().view(np.uint32).reshape(eng.B, 24)[:, 1] >> 24
-
-
 def _source(g, w, h, P, fog, mixed, seed, n=B):
     """n envs that have played: wide armies planted in every third env, 40 per-turn agent turns with invalid moves so
     that some envs' OwnedTiles lists differ from ownership (HF_LDIFF)."""
@@ -99,7 +88,7 @@ def test_copy_equals_import_and_plays_on_in_lockstep(w, h, P, fog, mixed):
     import torch
     import generalsreinforcementlearning_amd as g
     src = _source(g, w, h, P, fog, mixed, seed=5 + w)
-    fl = _header_flags(src)
+    fl = F.header_flags(src)
     assert (fl & HF_WIDE).any() and (fl & HF_LDIFF).any(), "the sources must include wide-army and HF_LDIFF envs"
     nb = src.state_bytes_per_env()
     slab = torch.empty(B * nb, dtype=torch.uint8, device="cuda")

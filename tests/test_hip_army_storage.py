@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _harness as H
+import _state_forms as F
 import _oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -18,22 +19,6 @@ def g():
     import generalsreinforcementlearning_amd as g
     g.load()
     return g
-
-
-class _RawDeviceArray:
-    """Zero-copy view of a raw device pointer for torch.as_tensor (the __cuda_array_interface__ protocol)."""
-
-    def __init__(self, ptr, n_u32):
-        self.__cuda_array_interface__ = {"shape": (n_u32,), "typestr": "<u4", "data": (int(ptr), False), "version": 2}
-
-
-def _header_flags(eng):
-    """Header dword H_DIMS >> 24 of every env, read through the zero-copy header buffer (GVEC_BUF_HEADER)."""
-    import torch
-    eng.synchronize()
-    t = torch.as_tensor(_RawDeviceArray(eng.device_buffer(0), eng.B * 24), device="cuda")
-    h = t.cpu().numpy().view(np.uint32).reshape(eng.B, 24)
-    return h[:, 1] >> 24
 
 
 @pytest.mark.parametrize("w,h,P", [(6, 6, 2), (10, 10, 2), (20, 20, 4), (25, 25, 4), (32, 32, 8)],
@@ -58,14 +43,14 @@ def test_lockstep_across_the_16_bit_boundary(g, w, h, P):
     eng.reset(army, owner, typ, ws, hs, ps)
     ora.reset(army, owner, typ, ws, hs, ps)
     H.assert_states_equal(eng.game_state(), ora.read_state(), "reset")
-    fl = _header_flags(eng)
+    fl = F.header_flags(eng)
     big = (army > 65535).any(1)
     assert np.array_equal((fl & HF_WIDE) != 0, big), "an env is WIDE exactly when one of its armies exceeds 65,535"
     saw = set()
     for k in range(6):
         H.run_lockstep(eng, ora, 25, seed=11 + k, invalid_permille=5, check_every=1, ctx=f"{w}x{h} block {k}")
         st = ora.read_state()
-        fl = _header_flags(eng)
+        fl = F.header_flags(eng)
         big = (st["army"].astype(np.int64) > 65535).any(1)
         assert np.array_equal((fl & HF_WIDE) != 0, big)
         saw |= {bool(b) for b in big}
@@ -85,13 +70,13 @@ def test_env_returns_to_narrow_when_it_fits_again(g):
     ora = O.OracleBatch(1, w, h, 2, prod=(0, 0, 0))
     eng.reset(army[None], owner[None], typ[None])
     ora.reset(army[None], owner[None], typ[None], [w], [h], [2])
-    assert _header_flags(eng)[0] & HF_WIDE
+    assert F.header_flags(eng)[0] & HF_WIDE
     acts = g.make_actions(1, 2, [(0, 0, 0, 0, 1, 0, True)])      # 69,999 attack 69,999: tie, defender keeps 0 (movement.go:85)
     assert eng.step(acts)[0] == ora.step(acts)[0] == 0
     st = eng.game_state()
     H.assert_states_equal(st, ora.read_state(), "after the attack")
     assert st["army"][0, 0] == 1 and st["army"][0, 1] == 0 and st["owner"][0, 1] == 1
-    assert not (_header_flags(eng)[0] & HF_WIDE), "every army fits 16 bits again: back to the narrow form"
+    assert not (F.header_flags(eng)[0] & HF_WIDE), "every army fits 16 bits again: back to the narrow form"
 
 
 def test_negative_and_huge_armies_survive_state_round_trip(g):
@@ -106,7 +91,7 @@ def test_negative_and_huge_armies_survive_state_round_trip(g):
     a[2, 5] = -2 ** 31
     eng.write_state({"army": a})
     assert np.array_equal(eng.game_state(fields=("army",))["army"], a)
-    fl = _header_flags(eng)
+    fl = F.header_flags(eng)
     assert list((fl & HF_WIDE) != 0) == [True, True, True, False]
 
 
@@ -128,7 +113,7 @@ def test_record_slab_carries_wide_envs_and_rejects_foreign_headers(g):
     for f in sa:
         assert np.array_equal(sa[f], sb[f]), f
     # game over / fog / wide armies travel; the turn engine's bookkeeping flags (HF_SYNC, HF_VSMALL) restart on import
-    assert np.array_equal(_header_flags(a) & 7, _header_flags(b) & 7)
+    assert np.array_equal(F.header_flags(a) & 7, F.header_flags(b) & 7)
     assert np.array_equal(a.legal_action_mask_bits(), b.legal_action_mask_bits())
     # a slab from an engine with other limits (or a corrupted one) is refused on the device, env by env
     hdr = buf[: B * 96].view(torch.int32).reshape(B, 24)

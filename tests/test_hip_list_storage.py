@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _harness as H
+import _state_forms as F
 import _oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -18,18 +19,6 @@ def g():
     import generalsreinforcementlearning_amd as g
     g.load()
     return g
-
-
-class _RawDeviceArray:
-    def __init__(self, ptr, n_u32):
-        self.__cuda_array_interface__ = {"shape": (n_u32,), "typestr": "<u4", "data": (int(ptr), False), "version": 2}
-
-
-def _header_flags(eng):
-    import torch
-    eng.synchronize()
-    t = torch.as_tensor(_RawDeviceArray(eng.device_buffer(0), eng.B * 24), device="cuda")
-    return t.cpu().numpy().view(np.uint32).reshape(eng.B, 24)[:, 1] >> 24
 
 
 def _desynced(st):
@@ -58,7 +47,7 @@ def test_flag_is_set_exactly_where_lists_differ_from_ownership(g, w, h, P):
         H.assert_states_equal(st, ora.read_state(), f"turn {k}")
         want = np.zeros(eng.B, bool)
         want[_desynced(st)] = True
-        assert np.array_equal((_header_flags(eng) & HF_LDIFF) != 0, want), f"turn {k}: HF_LDIFF <=> listed != owner"
+        assert np.array_equal((F.header_flags(eng) & HF_LDIFF) != 0, want), f"turn {k}: HF_LDIFF <=> listed != owner"
         seen += int(want.sum())
     assert seen > 20, "the scenario must actually produce envs whose lists differ (aborted turns, H5/H6)"
 
@@ -77,7 +66,7 @@ def test_desynced_envs_travel_in_record_slabs_and_play_on(g):
     sb = b.game_state()
     for f in st:
         assert np.array_equal(st[f], sb[f]), f
-    assert np.array_equal(_header_flags(a) & HF_LDIFF, _header_flags(b) & HF_LDIFF)
+    assert np.array_equal(F.header_flags(a) & HF_LDIFF, F.header_flags(b) & HF_LDIFF)
     # both copies keep following the oracle, through turns that heal some lists and break others
     for k in range(30):
         acts = ora.agent_actions(33, 80)
@@ -110,7 +99,7 @@ def test_write_state_pokes_of_the_lists_are_kept_and_healed_like_the_reference(g
     want = np.zeros(B, bool)
     want[_desynced(got)] = True
     assert want[::2].all() and not want[1::2].any()
-    assert np.array_equal((_header_flags(eng) & HF_LDIFF) != 0, want)
+    assert np.array_equal((F.header_flags(eng) & HF_LDIFF) != 0, want)
     H.run_lockstep(eng, ora, 40, 5, invalid_permille=30, check_every=1, ctx="after the poke")
 
 
@@ -125,4 +114,4 @@ def test_fused_rollout_carries_flagged_envs(g):
     H.assert_states_equal(st, ora.read_state(), "after 25 fused turns")
     want = np.zeros(B, bool)
     want[_desynced(st)] = True
-    assert np.array_equal((_header_flags(eng) & HF_LDIFF) != 0, want)
+    assert np.array_equal((F.header_flags(eng) & HF_LDIFF) != 0, want)

@@ -23,6 +23,7 @@ import pytest
 
 import _harness as H
 import _oracle as O
+import _state_forms as F
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +51,9 @@ def _pair(g, B, sub, w, h, p, fog, seed, pool):
     return eng, ora
 
 
-def _lockstep(eng, ora, sub, seed, permille, every, mask_every, ctx):
+def _lockstep(eng, ora, sub, seed, permille, every, mask_every, ctx, after_turn=None):
     """BASELINE.md's parity gate: state AND error code identical after every compared turn - and the moves the device
-    agent played are the oracle agent's."""
+    agent played are the oracle agent's.  after_turn(k): called after every turn, once the turn has been compared."""
     eng.record_agent_actions(True)          # the launch also stores the agent's moves and the per-env error codes
     for k in range(TURNS):
         eng.rollout(1, seed, permille, fused=False, want_stats=False)      # ONE step-kernel launch over all B envs
@@ -66,17 +67,21 @@ def _lockstep(eng, ora, sub, seed, permille, every, mask_every, ctx):
             H.assert_states_equal(eng.game_state(0, sub), ora.read_state(), f"{ctx} seed {seed} after turn {k + 1}")
         if mask_every and ((k + 1) % mask_every == 0 or k == TURNS - 1):
             assert np.array_equal(eng.legal_action_mask_bits()[:sub], ora.legal_mask(threads=THREADS)), f"{ctx} seed {seed} masks after turn {k + 1}"
+        if after_turn is not None:
+            after_turn(k)
     eng.record_agent_actions(False)
     c = eng.counters()
     assert c["aborted_turns"] > 0, "no turn was aborted: H5 was not exercised"
     return c
 
 
-def _fused_equals_per_turn(g, eng, B, w, h, p, fog, seed, permille, pool):
+def _fused_equals_per_turn(g, eng, B, w, h, p, fog, seed, permille, pool, age=None):
     """A second engine plays the same 500 turns inside ONE launch (board in registers / LDS): every env must match."""
     fus = g.VecEngine(B, w, h, p, fog_of_war=fog, auto_reset=True)
     fus.reset_generated(1000 + seed)
     fus.build_board_pool(pool, 7000 + seed)
+    if age is not None:
+        age(fus)
     fus.rollout(TURNS, seed, permille, fused=True, want_stats=False)
     for lo in range(0, B, 32768):
         n = min(32768, B - lo)
@@ -147,4 +152,39 @@ def test_config4_mixed_padded_batch_with_turn_offsets(g, seed):
     H.assert_states_equal(eng.game_state(), ora.read_state(), "configs[4] after reset")
     c = _lockstep(eng, ora, B, seed, permille=10, every=5, mask_every=100, ctx="configs[4]")
     assert c["games_finished"] > 0, "no game finished: the mixed pool was never dealt"
+    eng.close()
+
+
+# ---- aged boards at BASELINE sizes (tests/_state_forms.py) -------------------------------------------------------------
+AGED_PERIOD = 13  # env id % 13 < 4 planted: 31 % of the envs, evenly spread, so the oracle subset holds its share
+
+
+@pytest.mark.parametrize("cfg,B,w,h,p,pool,every", [("configs[2]", 65536, 15, 15, 2, 1024, 1), ("configs[3]", 262144, 20, 20, 4, 4096, 5)],
+                         ids=["config2_65536x15x15", "config3_262144x20x20_4p"])
+def test_aged_boards_at_baseline_size(g, cfg, B, w, h, p, pool, every):
+    """A batch that has drifted into the wide-army form and out of it, with lists that differ from ownership, through the
+    benchmarked per-turn path: the subset against the oracle (every turn or every 5), its header flags every 25 turns, then
+    fused == per-turn over all envs."""
+    seed, sub, permille = 4, 4096, 6
+    age = lambda target: F.age_batch(target, 50 + seed, period=AGED_PERIOD)
+    eng, ora = _pair(g, B, sub, w, h, p, True, seed, pool)
+    age(eng)
+    age(ora)
+    first = eng.game_state(0, sub)
+    H.assert_states_equal(first, ora.read_state(), f"{cfg} after aging")
+    F.check_flag_invariants(eng, first, f"{cfg} after aging")
+    assert F.wide_envs(first).mean() > 0.15
+    tally = F.FormsTally()
+    tally.add(first)
+
+    def after_turn(k):
+        st = ora.read_state(fields=("army", "owner", "listed"))
+        tally.add(st)
+        if (k + 1) % 25 == 0:
+            F.check_flag_invariants(eng, eng.game_state(0, sub), f"{cfg} after turn {k + 1}")
+
+    _lockstep(eng, ora, sub, seed, permille=permille, every=every, mask_every=25 if every == 1 else 0, ctx=f"{cfg} aged",
+              after_turn=after_turn)
+    tally.assert_all_seen(f"{cfg} aged")
+    _fused_equals_per_turn(g, eng, B, w, h, p, True, seed, permille, pool, age=age)
     eng.close()
