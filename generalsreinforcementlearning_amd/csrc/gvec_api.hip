@@ -1210,6 +1210,44 @@ int32_t gvec_agent_actions(gvec_handle* h, uint64_t seed, int32_t invalid_permil
   return GVEC_OK;
 }
 
+int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_t random_permille, gvec_action* actions, int32_t mem) {
+  if (!h || !actions) return GVEC_E_INVALID;
+  if (random_permille < 0 || random_permille > 1000) {
+    set_err("gvec_bot_actions: random_permille must be in [0, 1000]");
+    return GVEC_E_INVALID;
+  }
+  if (h->maxp < 32 && (players >> h->maxp) != 0u) {
+    set_err("gvec_bot_actions: players names a seat at or above max_players");
+    return GVEC_E_INVALID;
+  }
+  if (h->sharded()) {
+    RET_IF(sharded::host_only(mem, "gvec_bot_actions"));
+    const size_t mp = (size_t)h->maxp;
+    return sharded::fan(h, [=](gvec_handle* c, int begin, int) {
+      return gvec_bot_actions(c, players, seed, random_permille, actions + begin * mp, GVEC_MEM_HOST);
+    });
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  StepArgs a = base_args(h);
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  a.invalid_permille = 0;
+  const size_t bytes = (size_t)h->cfg.num_envs * h->maxp * sizeof(gvec_action);
+  // host memory: the caller's array goes through the staging buffer both ways, so the slots the kernel leaves alone come
+  // back as they were
+  if (mem == GVEC_MEM_HOST) HIPCHK(hipMemcpyAsync(h->d_actions, actions, bytes, hipMemcpyHostToDevice, h->stream));
+  a.actions_out = (mem == GVEC_MEM_HOST) ? h->d_actions : actions;
+  BotArgs g;
+  g.players = players;
+  g.random_permille = random_permille;
+  HIPCHK(launch_bot(h->var, a, g, h->stream));
+  if (mem == GVEC_MEM_HOST) {
+    HIPCHK(hipMemcpyAsync(actions, h->d_actions, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return GVEC_OK;
+}
+
 static ExperienceArgs exp_args(gvec_handle* h) {
   ExperienceArgs a;
   memset(&a, 0, sizeof a);

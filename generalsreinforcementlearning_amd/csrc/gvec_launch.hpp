@@ -135,6 +135,12 @@ hipError_t launch_rollout(const Variant& v, const StepArgs& a, hipStream_t s);
 hipError_t launch_agent(const Variant& v, const StepArgs& a, hipStream_t s);
 hipError_t launch_legal(const Variant& v, const StepArgs& a, hipStream_t s);
 hipError_t launch_serializer_mask(const Variant& v, const StepArgs& a, hipStream_t s);
+// the scripted opponent (gvec_bot_actions): players = seats to move, random_permille = share of the random agent's moves
+struct BotArgs {
+  uint32_t players;
+  int32_t random_permille;
+};
+hipError_t launch_bot(const Variant& v, const StepArgs& a, const BotArgs& g, hipStream_t s);
 
 // internal/experience side channel
 struct ExperienceArgs {

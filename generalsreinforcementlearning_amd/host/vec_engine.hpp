@@ -139,6 +139,13 @@ class VecEngine {
     return st;
   }
 
+  // The scripted opponent's moves (gvec_bot_actions) for the seats in `players` (a bit mask), written into `actions`
+  // ([NumEnvs][Players]); the other slots keep what they hold.
+  void BotActions(uint32_t players, std::vector<gvec_action>* actions, uint64_t seed = 0, int random_permille = 0) {
+    actions->resize(static_cast<size_t>(cfg_.NumEnvs) * cfg_.Players);
+    check(gvec_bot_actions(h_, players, seed, random_permille, actions->data(), GVEC_MEM_HOST), "gvec_bot_actions");
+  }
+
   gvec_handle* handle() { return h_; }
 
  private:

@@ -316,6 +316,32 @@ class VecEngine:
         check(self.L.gvec_agent_actions(self.h, seed, invalid_permille, _ptr(acts), MEM_HOST), "gvec_agent_actions")
         return acts
 
+    def _players_mask(self, players):
+        """a bit mask of seats from an int mask or an iterable of seat ids"""
+        if isinstance(players, (int, np.integer)):
+            return int(players)
+        mask = 0
+        for p in players:
+            if not 0 <= int(p) < self.max_p:
+                raise ValueError(f"seat {p} is not below max_players = {self.max_p}")
+            mask |= 1 << int(p)
+        return mask
+
+    def bot_actions(self, players, seed=0, random_permille=0, actions=None):
+        """The scripted opponent's moves (gvec_bot_actions; rule in DESIGN.md section 6) for the seats in `players` (seat
+        ids or a bit mask) -> [B, P] ACTION_DTYPE.  `actions` given: filled in place, its other slots kept."""
+        acts = np.zeros((self.B, self.max_p), ACTION_DTYPE) if actions is None else actions
+        if acts.dtype != ACTION_DTYPE or acts.shape != (self.B, self.max_p) or not acts.flags.c_contiguous:
+            raise ValueError(f"actions must be a C-contiguous [{self.B}, {self.max_p}] ACTION_DTYPE array")
+        check(self.L.gvec_bot_actions(self.h, self._players_mask(players), int(seed), int(random_permille), _ptr(acts), MEM_HOST),
+              "gvec_bot_actions")
+        return acts
+
+    def bot_actions_device(self, players_mask, seed, random_permille, actions_ptr):
+        """gvec_bot_actions into device memory ([B][P] gvec_action at actions_ptr): enqueued on the engine's stream."""
+        check(self.L.gvec_bot_actions(self.h, int(players_mask), int(seed), int(random_permille), C.c_void_p(int(actions_ptr)), MEM_DEVICE),
+              "gvec_bot_actions")
+
     def rollout(self, turns, seed, invalid_permille=0, fused=True, want_stats=True):
         st = RolloutStats()
         check(self.L.gvec_rollout(self.h, turns, seed, invalid_permille, int(bool(fused)), C.byref(st) if want_stats else None),

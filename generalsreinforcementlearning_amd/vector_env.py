@@ -38,12 +38,21 @@ class GeneralsVecEnv(EnvStateMixin):
     copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, fog_of_war=True, max_turns=500,
-                 seed=0, device=0, board_pool=1024, device_outputs=False):
+                 seed=0, device=0, board_pool=1024, device_outputs=False, opponent="random", opponent_random_permille=0):
         """device_outputs=True  observation / mask / reward / flags are torch tensors on the GPU; `step` takes a CUDA int64
                              tensor of actions: no board state crosses PCIe, a step is one kernel launch.  Every tensor a
                              step returns lives in a buffer that the step AFTER NEXT reuses.
         default              numpy arrays in, numpy arrays out - the same kernel, its outputs copied to pinned host
-                             buffers (one D2H of the observation per step)."""
+                             buffers (one D2H of the observation per step).
+        opponent="random"    the other seats are the on-device random agent (one launch per step).
+        opponent="bot"       the other seats are the scripted opponent (gvec_bot_actions), computed on
+                             the device into the step's action buffer, then the composed step (_step_composed);
+                             opponent_random_permille of its moves are the random agent's instead.
+        step(actions, other_actions=...) overrides either choice for that step."""
+        if opponent not in ("random", "bot"):
+            raise ValueError(f"opponent must be 'random' or 'bot', not {opponent!r}")
+        if not 0 <= int(opponent_random_permille) <= 1000:
+            raise ValueError("opponent_random_permille must be in [0, 1000]")
         import torch
         if not torch.cuda.is_available():
             from ._lib import GvecError
@@ -64,6 +73,7 @@ class GeneralsVecEnv(EnvStateMixin):
         self.engine = VecEngine(num_envs, board_width, board_height, max_players, fog_of_war=fog_of_war, device=device,
                                 auto_reset=True)
         self._pool = board_pool
+        self.opponent, self.opponent_random_permille = opponent, int(opponent_random_permille)
         self.valid_actions_mask = None
         self._obs_flip = 0
         self.device_outputs = bool(device_outputs)
@@ -150,6 +160,17 @@ class GeneralsVecEnv(EnvStateMixin):
         self.valid_actions_mask = info["valid_actions_mask"]
         return obs, out["reward"], out["terminated"], out["truncated"], dict(info)
 
+    def _step_bot(self, actions):
+        """The other seats played by the scripted opponent: gvec_bot_actions writes their moves into the step's action buffer
+        on the device (seeded like the random agent's draw of a one-launch step), then the composed step runs on it."""
+        B, P = self.num_envs, self.max_players
+        if self._acts is None:
+            self._acts = self._t.zeros((B, P, 8), dtype=self._t.uint8, device=self._dev)
+        others = ((1 << P) - 1) & ~(1 << self.player_id)
+        self.engine.bot_actions_device(others, self._seed + 1000 * self._episode + 1, self.opponent_random_permille, self._acts.data_ptr())
+        self._episode += 1
+        return self._step_composed(actions, None)
+
     def _step_composed(self, actions, others):
         """The same step with the OTHER players' moves supplied by the caller - an opponent policy, self-play - instead of
         drawn by the on-device agent: `others` is [num_envs][max_players] gvec_action (numpy ACTION_DTYPE, or a CUDA uint8
@@ -167,7 +188,8 @@ class GeneralsVecEnv(EnvStateMixin):
         if isinstance(others, np.ndarray):
             from .vec_engine import ACTION_DTYPE
             others = t.from_numpy(np.ascontiguousarray(others, ACTION_DTYPE).reshape(B, P).view(np.uint8).reshape(B, P, 8))
-        self._acts.copy_(others.reshape(B, P, 8))
+        if others is not None:                                          # None: _acts already holds them (_step_bot)
+            self._acts.copy_(others.reshape(B, P, 8))
         self.last_actions = actions
         k = self._step_no
         self._step_no += 1
@@ -209,9 +231,13 @@ class GeneralsVecEnv(EnvStateMixin):
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 
     def step(self, actions, other_actions=None):
-        """other_actions: None = the other players are the on-device random agent (ONE launch); else their moves for this
-        step ([num_envs][max_players] gvec_action, see _step_composed)."""
-        run = self._step_device if other_actions is None else (lambda a: self._step_composed(a, other_actions))
+        """other_actions: None = the other players are the env's opponent (the on-device random agent in ONE launch, or the
+        scripted opponent with opponent="bot"); else their moves for this step ([num_envs][max_players] gvec_action, see
+        _step_composed)."""
+        if other_actions is not None:
+            run = lambda a: self._step_composed(a, other_actions)
+        else:
+            run = self._step_bot if self.opponent == "bot" else self._step_device
         if self.device_outputs:
             return run(actions)
         obs, reward, terminated, truncated, info = run(np.asarray(actions, np.int64))

@@ -306,6 +306,16 @@ int32_t gvec_step_traffic_bytes(const gvec_handle* h, int64_t* out4);
 /* The agent alone: fills actions[B][max_players] for the current state/turn. */
 int32_t gvec_agent_actions(gvec_handle* h, uint64_t seed, int32_t invalid_permille,
                            gvec_action* actions, int32_t mem);
+/* Scripted opponent: for every env, the move of each player whose bit is set in `players` (bits below max_players),
+ * written into actions[B][max_players]; the other slots are left untouched (host memory included).  The rule (DESIGN.md
+ * section 6 "Scripted opponent") reads the player's own view only - what fog lets it see - and plays MoveAll: the best
+ * capture by target tier (enemy general > city > enemy tile > neutral tile), then margin, else one step of the largest
+ * army towards the nearest target.  A slot plays gvec_agent_actions(seed, 0)'s move instead (under the current
+ * gvec_set_agent_mix) with probability random_permille / 1000, drawn per (seed, env, turn, player); 0 = the pure rule,
+ * 1000 = the random agent.  random_permille outside [0, 1000] or a bit at or above max_players: GVEC_E_INVALID.
+ * Sharded handles: host memory only. */
+int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_t random_permille,
+                         gvec_action* actions, int32_t mem);
 
 /* ---- internal/experience side channel ------------------------------
  * gvec_experience_begin   = TurnProcessor.captureStateForExperience
