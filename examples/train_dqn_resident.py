@@ -9,7 +9,7 @@ The network, loss and exploration scheme follow the reference's choices in outli
 observation, Huber loss, gradient clipping at 1.0, a hard target update, fixed per-worker exploration rates spread
 geometrically over the workers); the code is this repo's own.  An example, not part of the measured hot path.
 
-    python examples/train_dqn_resident.py --num-envs 4096 --updates 200
+    python examples/train_dqn_resident.py --num-envs 4096 --updates 200 [--prioritized]
 """
 import argparse
 import json
@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from generalsreinforcementlearning_amd.env_pool import DeviceReplayBuffer, ParallelVecEnvPool
+from generalsreinforcementlearning_amd.env_pool import DeviceReplayBuffer, ParallelVecEnvPool, PrioritizedDeviceReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 
@@ -54,6 +54,9 @@ def main(argv=None):
     ap.add_argument("--max-steps-per-episode", type=int, default=200)
     ap.add_argument("--eps-base", type=float, default=0.4)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--prioritized", action="store_true", help="prioritized replay: weighted loss, priorities from the batch's TD errors")
+    ap.add_argument("--per-alpha", type=float, default=0.6)
+    ap.add_argument("--per-beta", type=float, default=0.4)
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
@@ -72,7 +75,7 @@ def main(argv=None):
             explore = (masks * torch.rand(masks.shape, device=dev, generator=gen)).argmax(1)      # a uniform valid action
             return torch.where(torch.rand(B, device=dev, generator=gen) < eps, explore, greedy)
 
-    buf = DeviceReplayBuffer(a.buffer_size)
+    buf = PrioritizedDeviceReplayBuffer(a.buffer_size, alpha=a.per_alpha, beta=a.per_beta) if a.prioritized else DeviceReplayBuffer(a.buffer_size)
     pool = ParallelVecEnvPool(B, lambda n: GeneralsVecEnv(n, board_width=a.board, board_height=a.board, max_players=2, max_turns=a.max_steps_per_episode,
                                                          seed=a.seed, device_outputs=True),
                               policy, buf, max_steps_per_episode=a.max_steps_per_episode, seed=a.seed, batched_actions=True)
@@ -80,10 +83,18 @@ def main(argv=None):
     losses, t0 = [], time.perf_counter()
     for u in range(a.updates):
         pool.collect(a.collect_per_update)
-        s, act, r, ns, d = buf.sample_arrays(a.batch_size)
+        if a.prioritized:
+            s, act, r, ns, d, slots, weights = buf.sample_prioritized(a.batch_size)
+        else:
+            s, act, r, ns, d = buf.sample_arrays(a.batch_size)
         with torch.no_grad():
             tq = r.float() + a.gamma * target(ns).max(1).values * (~d).float()
-        loss = F.smooth_l1_loss(q(s).gather(1, act[:, None]).squeeze(1), tq)
+        qsa = q(s).gather(1, act[:, None]).squeeze(1)
+        if a.prioritized:
+            loss = (weights * F.smooth_l1_loss(qsa, tq, reduction="none")).mean()
+            buf.update_priorities(slots, (qsa.detach() - tq))
+        else:
+            loss = F.smooth_l1_loss(qsa, tq)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         nn.utils.clip_grad_norm_(q.parameters(), 1.0)

@@ -41,6 +41,9 @@ class CollectArgs(C.Structure):
                                              "pool_counters", "scratch")])
 
 
+# header words of a prioritized-replay tree (GVEC_PER_* in include/generals_vec.h)
+PER_HEADER_WORDS, PER_HDR_MAX, PER_HDR_REJECTED, PER_HDR_DRAWS = 64, 0, 1, 2
+
 # every symbol include/generals_vec.h declares: (restype, argtypes)
 _vp, _i32, _u64 = C.c_void_p, C.c_int32, C.c_uint64
 SYMBOLS = {
@@ -87,6 +90,12 @@ SYMBOLS = {
     "gvec_expand_experience_records": (_i32, [_i32, _vp, C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _vp]),
     "gvec_pool_collect": (_i32, [_i32, _vp, C.POINTER(CollectArgs)]),
     "gvec_pool_collect_scratch_bytes": (_u64, [_i32]),
+    "gvec_per_tree_bytes": (_u64, [C.c_int64]),
+    "gvec_per_tree_layout": (_i32, [C.c_int64, C.POINTER(C.c_int64)]),
+    "gvec_per_init": (_i32, [_i32, _vp, _vp, C.c_int64]),
+    "gvec_per_push": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64]),
+    "gvec_per_update": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_float, C.c_float]),
+    "gvec_per_sample": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_float, _vp, _u64, _vp, _vp]),
     "gvec_gym_observe": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

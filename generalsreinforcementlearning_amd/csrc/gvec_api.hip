@@ -1411,6 +1411,100 @@ int32_t gvec_pool_collect(int32_t device, void* hip_stream, const gvec_collect_a
   return GVEC_OK;
 }
 
+// ---- prioritized replay (gvec_per.hip) ----
+static constexpr int64_t PER_MAX_CAPACITY = (int64_t)1 << 36;   // six levels above the leaves: PerLayout::off holds them
+static int32_t per_check(const char* fn, const void* tree, int64_t capacity) {
+  if (!tree) {
+    set_err("%s: tree is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  if (capacity < 1 || capacity > PER_MAX_CAPACITY) {
+    set_err("%s: capacity %lld outside [1, 2^36]", fn, (long long)capacity);
+    return GVEC_E_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(tree) & 255) {
+    set_err("%s: tree must be 256-byte aligned (a node's 64 children are one 256-byte read)", fn);
+    return GVEC_E_INVALID;
+  }
+  return GVEC_OK;
+}
+
+uint64_t gvec_per_tree_bytes(int64_t capacity) {
+  return capacity >= 1 && capacity <= PER_MAX_CAPACITY ? (uint64_t)per_layout(capacity).total * 4 : 0;
+}
+
+int32_t gvec_per_tree_layout(int64_t capacity, int64_t* out10) {
+  if (!out10 || capacity < 1 || capacity > PER_MAX_CAPACITY) {
+    set_err("gvec_per_tree_layout: capacity %lld outside [1, 2^36] or out is NULL", (long long)capacity);
+    return GVEC_E_INVALID;
+  }
+  const PerLayout y = per_layout(capacity);
+  for (int i = 0; i < 10; ++i) out10[i] = 0;
+  out10[0] = y.levels;
+  out10[1] = y.total;
+  for (int l = 0; l <= y.levels; ++l) out10[2 + l] = y.off[l];
+  return GVEC_OK;
+}
+
+int32_t gvec_per_init(int32_t device, void* hip_stream, void* tree, int64_t capacity) {
+  RET_IF(per_check("gvec_per_init", tree, capacity));
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_per_init(static_cast<float*>(tree), per_layout(capacity), reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_per_push(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* counters_before,
+                      const int64_t* counters_after, int64_t max_count) {
+  RET_IF(per_check("gvec_per_push", tree, capacity));
+  if (!counters_before || !counters_after || max_count < 1) {
+    set_err("gvec_per_push: counters_before / counters_after NULL or max_count %lld < 1", (long long)max_count);
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_per_push(static_cast<float*>(tree), per_layout(capacity), reinterpret_cast<const long long*>(counters_before),
+                         reinterpret_cast<const long long*>(counters_after), max_count, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_per_update(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* idx, const float* td_error,
+                        int64_t n, float alpha, float eps) {
+  RET_IF(per_check("gvec_per_update", tree, capacity));
+  if (n < 0 || !(alpha >= 0.0f) || !(eps > 0.0f)) {
+    set_err("gvec_per_update: n %lld < 0, alpha %g < 0 or eps %g <= 0", (long long)n, (double)alpha, (double)eps);
+    return GVEC_E_INVALID;
+  }
+  if (n == 0) return GVEC_OK;
+  if (!idx || !td_error) {
+    set_err("gvec_per_update: idx or td_error is NULL");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_per_update(static_cast<float*>(tree), per_layout(capacity), reinterpret_cast<const long long*>(idx), td_error, n, alpha, eps,
+                           reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* ring_counters, int64_t k,
+                        float beta, const double* u, uint64_t seed, int64_t* idx, float* weight) {
+  RET_IF(per_check("gvec_per_sample", tree, capacity));
+  if (k < 1 || !(beta >= 0.0f)) {
+    set_err("gvec_per_sample: k %lld < 1 or beta %g < 0", (long long)k, (double)beta);
+    return GVEC_E_INVALID;
+  }
+  if (!ring_counters || !idx || !weight) {
+    set_err("gvec_per_sample: ring_counters, idx or weight is NULL");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_per_sample(static_cast<float*>(tree), per_layout(capacity), reinterpret_cast<const long long*>(ring_counters), k, beta, u, seed,
+                           reinterpret_cast<long long*>(idx), weight, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
 int32_t gvec_record_agent_actions(gvec_handle* h, int32_t on) {
   if (!h) return GVEC_E_INVALID;
   if (h->sharded()) {

@@ -277,4 +277,18 @@ hipError_t launch_counter_sum(const uint32_t* hdr, int32_t num_envs, unsigned lo
 // device self-test of the wave primitives; out[0] = 0 on success else a failing check id
 hipError_t launch_selftest(int32_t* out, hipStream_t s);
 
+// prioritized replay (gvec_per.hip; generals_vec.h "prioritized experience replay"): the tree's float offsets for a ring of
+// `capacity` slots - off[l] = first node of level l (0 = leaves), `levels` = levels above the leaves (the root is level `levels`)
+struct PerLayout {
+  long long capacity, total;
+  long long off[8];
+  int levels;
+};
+PerLayout per_layout(long long capacity);
+hipError_t launch_per_init(float* tree, const PerLayout& y, hipStream_t s);
+hipError_t launch_per_push(float* tree, const PerLayout& y, const long long* before, const long long* after, long long max_count, hipStream_t s);
+hipError_t launch_per_update(float* tree, const PerLayout& y, const long long* idx, const float* td, long long n, float alpha, float eps, hipStream_t s);
+hipError_t launch_per_sample(float* tree, const PerLayout& y, const long long* ring_counters, long long k, float beta, const double* u,
+                             unsigned long long seed, long long* idx, float* weight, hipStream_t s);
+
 }  // namespace gvec

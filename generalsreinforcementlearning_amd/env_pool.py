@@ -206,6 +206,137 @@ class DeviceReplayBuffer:
         return int(self.counters[1])
 
 
+class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
+    """`DeviceReplayBuffer` with prioritized experience replay (Schaul et al. 2016) on the device: a radix-64 float32 sum tree
+    over the ring's slots, kept and sampled by the gvec_per_* kernels.  A slot's priority is
+    `(|td_error| + eps) ** alpha`; a new transition - pushed here or appended by the pool's `gvec_pool_collect` - gets the
+    largest priority ever written (1.0 at the start); a slot that holds no transition has priority 0 and is never drawn.
+    `sample_prioritized` makes `batch_size` stratified draws WITH replacement and returns the importance weights
+    `(len * P(i)) ** -beta` over the batch's largest; `sample_arrays` / `sample` are that draw without indices and weights, so
+    a learner or pool written for the uniform buffer runs unchanged.  `update_priorities(indices, td_errors)` takes the
+    indices of an earlier draw: a slot the collector has overwritten in between simply takes the stale priority, as in
+    standard prioritized replay (there is no generation check).  Nothing here synchronises except `len()`."""
+
+    def __init__(self, capacity, device=0, alpha=0.6, beta=0.4, eps=1e-6):
+        super().__init__(capacity, device)
+        if alpha < 0 or beta < 0 or not eps > 0:
+            raise ValueError(f"alpha {alpha} and beta {beta} must be >= 0 and eps {eps} > 0")
+        import ctypes
+        from ._lib import check, load
+        self.alpha, self.beta, self.eps = float(alpha), float(beta), float(eps)
+        self._C, self._check, self._L = ctypes, check, load()
+        layout = (ctypes.c_int64 * 10)()
+        check(self._L.gvec_per_tree_layout(self.capacity, layout), "gvec_per_tree_layout")
+        self.tree_levels, self._tree_words = int(layout[0]), int(layout[1])
+        self.tree_offsets = [int(layout[2 + l]) for l in range(self.tree_levels + 1)]     # in floats; level 0 = the leaves
+        self.tree = None
+        self._before = self._t.zeros(4, dtype=self._t.int64, device=self.device)           # the counters ahead of a push
+        self._guard = threading.RLock()          # push_batch holds it round the parent's push (which takes it too) and the tree's
+        self._seed = 0
+
+    def allocate(self, obs_shape):
+        super().allocate(obs_shape)
+        if self.tree is None:
+            t = self._t
+            self.tree = t.empty(self._tree_words, dtype=t.float32, device=self.device)
+            self._check(self._L.gvec_per_init(self.device.index, self._stream(), self.tree.data_ptr(), self.capacity), "gvec_per_init")
+        return self
+
+    def _stream(self):
+        return self._t.cuda.current_stream(self.device).cuda_stream
+
+    def _header(self):
+        from ._lib import PER_HEADER_WORDS
+        return self.tree[:PER_HEADER_WORDS].view(self._t.int32)
+
+    def manual_seed(self, seed):
+        """Seeds the draw: the same seed over the same ring gives the same indices (the sequence restarts)."""
+        from ._lib import PER_HDR_DRAWS
+        super().manual_seed(seed)
+        with self._guard:
+            self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            if self.tree is not None:
+                self._header()[PER_HDR_DRAWS:PER_HDR_DRAWS + 2].zero_()
+
+    def mark_before_push(self):
+        """The counters' "before" copy of gvec_per_push (32 bytes, device to device); the caller holds `_guard`."""
+        self._before.copy_(self.counters)
+
+    def push_priorities(self, max_count):
+        """The rows appended since `mark_before_push` get the maximum priority; the caller holds `_guard`."""
+        self._check(self._L.gvec_per_push(self.device.index, self._stream(), self.tree.data_ptr(), self.capacity, self._before.data_ptr(),
+                                          self.counters.data_ptr(), int(max_count)), "gvec_per_push")
+
+    def push_batch(self, states, actions, rewards, next_states, dones):
+        k = int(self._t.as_tensor(actions).numel())
+        if k == 0:
+            return
+        with self._guard:                        # one acquisition: no collector step or update lands between the rows and their leaves
+            self.mark_before_push()
+            super().push_batch(states, actions, rewards, next_states, dones)
+            self.push_priorities(min(k, self.capacity))
+
+    def update_priorities(self, indices, td_errors):
+        """priority[indices[i]] = (|td_errors[i]| + eps) ** alpha; duplicates: one of the values wins; an index outside the
+        ring or a non-finite error is skipped on the device and counted in `rejected_updates`."""
+        t = self._t
+        idx = t.as_tensor(indices, device=self.device).to(t.int64).reshape(-1).contiguous()
+        td = t.as_tensor(td_errors, device=self.device).detach().to(t.float32).reshape(-1).contiguous()
+        if idx.numel() != td.numel():
+            raise ValueError(f"{idx.numel()} indices, {td.numel()} td errors")
+        if idx.numel() == 0 or self.tree is None:
+            return
+        with self._guard:
+            self._check(self._L.gvec_per_update(self.device.index, self._stream(), self.tree.data_ptr(), self.capacity, idx.data_ptr(),
+                                                td.data_ptr(), idx.numel(), self.alpha, self.eps), "gvec_per_update")
+
+    @property
+    def rejected_updates(self):
+        from ._lib import PER_HDR_REJECTED
+        return 0 if self.tree is None else int(self._header()[PER_HDR_REJECTED])
+
+    def _draw(self, batch_size, beta, u):
+        """(indices, weights) of one call of gvec_per_sample; the caller holds `_guard`."""
+        t = self._t
+        idx = t.empty(batch_size, dtype=t.int64, device=self.device)
+        w = t.empty(batch_size, dtype=t.float32, device=self.device)
+        if u is not None:
+            u = t.as_tensor(u, device=self.device).to(t.float64).reshape(-1).contiguous()
+            if u.numel() != batch_size:
+                raise ValueError(f"u has {u.numel()} entries for {batch_size} draws")
+        self._check(self._L.gvec_per_sample(self.device.index, self._stream(), self.tree.data_ptr(), self.capacity, self.counters.data_ptr(),
+                                            batch_size, self.beta if beta is None else float(beta), None if u is None else u.data_ptr(),
+                                            self._seed, idx.data_ptr(), w.data_ptr()), "gvec_per_sample")
+        return idx, w
+
+    def sample_prioritized(self, batch_size, beta=None, u=None):
+        """(states, actions, rewards, next_states, dones, indices, weights) as CUDA tensors: `batch_size` stratified draws
+        with replacement, draw j aimed at (j + u[j]) / batch_size of the total priority; `u` (float64 in [0, 1), for
+        reproducible tests) defaults to the kernel's counter RNG under `manual_seed`.  The draw and its gathers are enqueued
+        under the collector's lock, like `sample_arrays`.  ValueError when the buffer is empty or holds fewer than
+        batch_size transitions (the uniform buffer's contract)."""
+        batch_size = self._checked(batch_size)
+        with self._guard:
+            idx, w = self._draw(batch_size, beta, u)
+            return self.state[idx], self.action[idx], self.reward[idx], self.next_state[idx], self.done[idx], idx, w
+
+    def _checked(self, batch_size):
+        batch_size = int(batch_size)
+        held = len(self)
+        if batch_size < 1 or batch_size > held or self.tree is None:
+            raise ValueError("Sample larger than population or is negative" if held else "the replay buffer is empty")
+        return batch_size
+
+    def sample_indices(self, batch_size):
+        """Prioritized, with replacement (the uniform buffer's are distinct); ValueError like `sample_prioritized`."""
+        batch_size = self._checked(batch_size)
+        with self._guard:
+            return self._draw(batch_size, None, None)[0]
+
+    def sample_arrays(self, batch_size):
+        return self.sample_prioritized(batch_size)[:5]
+
+
 class _DeviceCollector:
     """The device-side state of a pool whose env, policy and buffer all live on the GPU, and the one call per vector step
     that advances it (gvec_pool_collect)."""
@@ -246,6 +377,7 @@ class _DeviceCollector:
                              ("pool_counters", self.counters), ("scratch", self.scratch)):
             setattr(a, name, tensor.data_ptr())
         self._device_index = dev.index
+        self._prioritized = isinstance(buffer, PrioritizedDeviceReplayBuffer)
 
     def restart(self):
         self.episode_reward.zero_()
@@ -257,7 +389,11 @@ class _DeviceCollector:
         a.terminated, a.truncated, a.was_reset, a.needs_reset = terminated.data_ptr(), truncated.data_ptr(), was_reset.data_ptr(), needs_reset.data_ptr()
         stream = self._t.cuda.current_stream(self.env._dev).cuda_stream
         with self.buffer._guard:                  # ordered against a learner's sample_arrays / push_batch on the same stream
+            if self._prioritized:                 # the counters ahead of the step: the tree learns on the device how many rows came
+                self.buffer.mark_before_push()
             self._check(self.L.gvec_pool_collect(self._device_index, stream, self._C.byref(a)), "gvec_pool_collect")
+            if self._prioritized:
+                self.buffer.push_priorities(a.num_envs)
 
     def pop_results(self):
         held = int(self.counters[1])

@@ -514,6 +514,56 @@ typedef struct gvec_collect_args {
 int32_t gvec_pool_collect(int32_t device, void* hip_stream, const gvec_collect_args* args);
 uint64_t gvec_pool_collect_scratch_bytes(int32_t num_envs);
 
+/* ---- prioritized experience replay over a ring in HBM (Schaul et al. 2016; the "Prioritized sampling support" of the
+ * reference's documentation/MASTER_PLAN.md phase 3, which it never built) ----------------------------------------------
+ * A radix-64 sum tree over the slots of a replay ring (the one gvec_pool_collect fills, or any other): float32, resident in
+ * device memory, 256-byte aligned, gvec_per_tree_bytes(capacity) bytes.  Handle-free like gvec_pool_collect: every pointer
+ * is DEVICE memory on `device`, work is enqueued on hip_stream, nothing synchronises.
+ * Layout (gvec_per_tree_layout, in 4-byte words from the start of the tree): out[0] = L, the levels above the leaves;
+ *   out[1] = the tree's size in words; out[2 + l] = first node of level l, l = 0 (one leaf per ring slot) .. L (the root).
+ *   Node i of level l + 1 is the sum of nodes [64 i, 64 i + 64) of level l; levels are padded with zeros to a multiple of 64.
+ *   The first GVEC_PER_HEADER_WORDS words are a header of uint32 words: GVEC_PER_HDR_MAX the running maximum of every leaf
+ *   value ever written (a float's bits; starts at 1.0), _REJECTED how many updates were skipped (see below), _DRAWS the
+ *   number of gvec_per_sample calls so far (the draw counter of its RNG; zero it to restart a seed's sequence - nothing
+ *   else depends on it; the word after it is the kernels' own copy), _MIN0 two words and _SEQ two words of the kernels' own
+ *   (the batch's smallest leaf, alternating by a call count a caller must leave alone).
+ * A node is always recomputed from its 64 children, as the last term of the left-to-right float32 prefix the descent uses,
+ *   so a slot whose leaf is 0 (no transition there) is never drawn and the tree cannot drift.
+ * gvec_per_init: all leaves 0, maximum 1.0, counters 0.  One launch.
+ * gvec_per_push: the rows appended to the ring between two copies of its counters {cursor, size, total pushed, 0} -
+ *   `before` and `after`, device int64[4]; take `before` with a 32-byte device-to-device copy ahead of gvec_pool_collect and
+ *   pass the live counters as `after` - get the running maximum as their leaf: slots [before.cursor, + after.pushed -
+ *   before.pushed) mod capacity, all of them when the ring went round.  max_count sizes the launch (the host does not
+ *   know the count): rows beyond it keep their leaves and _REJECTED goes up by one.  Two launches.
+ * gvec_per_update: leaf[idx[i]] = (|td[i]| + eps) ** alpha for i < n (float32), the maximum moves, every ancestor is
+ *   refreshed.  Duplicate indices: one of the supplied values wins.  An index outside [0, capacity), or an error that is
+ *   NaN or infinite, is skipped and counted in _REJECTED (checked on the device).  A slot the ring has overwritten since it
+ *   was drawn simply takes the stale priority, as in standard prioritized replay.  1 + (levels of more than 64 nodes) + 1
+ *   launches: 4 for 16 M slots.
+ * gvec_per_sample: k stratified draws with replacement: draw j aims at (j + u[j]) / k * total, formed in float64, and
+ *   descends in float32.  u: k float64 in [0, 1), or NULL for the build's counter RNG keyed by (seed, _DRAWS, j), 53 bits a
+ *   draw.  idx[k] int64, weight[k] float32 = (size * leaf / total) ** -beta over the batch's largest such value (= (leaf /
+ *   the batch's smallest leaf) ** -beta: size and total cancel); ring_counters (the ring's live counters) says whether the
+ *   ring holds anything: an empty ring or tree gives idx -1 and weight 0.  Two launches.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: tree NULL or not 256-byte aligned,
+ *   capacity < 1 or > 2^36, n < 0, k < 1, max_count < 1, alpha < 0, beta < 0, eps <= 0 (NaN included), another required
+ *   pointer NULL.  n == 0 is a no-op that needs no device. */
+#define GVEC_PER_HEADER_WORDS 64
+#define GVEC_PER_HDR_MAX      0
+#define GVEC_PER_HDR_REJECTED 1
+#define GVEC_PER_HDR_DRAWS    2
+#define GVEC_PER_HDR_MIN0     4
+#define GVEC_PER_HDR_SEQ      6
+uint64_t gvec_per_tree_bytes(int64_t capacity);
+int32_t gvec_per_tree_layout(int64_t capacity, int64_t* out10);
+int32_t gvec_per_init(int32_t device, void* hip_stream, void* tree, int64_t capacity);
+int32_t gvec_per_push(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* counters_before,
+                      const int64_t* counters_after, int64_t max_count);
+int32_t gvec_per_update(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* idx, const float* td_error,
+                        int64_t n, float alpha, float eps);
+int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* ring_counters, int64_t k,
+                        float beta, const double* u, uint64_t seed, int64_t* idx, float* weight);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
