@@ -41,6 +41,32 @@ class CollectArgs(C.Structure):
                                              "pool_counters", "scratch")])
 
 
+class TrajRecordArgs(C.Structure):
+    """gvec_traj_record_args (include/generals_vec.h): every pointer is device memory."""
+    _fields_ = ([("T", C.c_int64), ("t", C.c_int64), ("num_envs", C.c_int32), ("num_learners", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("step_action", "step_logp", "step_value", "step_reward", "reset", "terminated", "truncated",
+                                             "alive", "alive_state", "action", "logp", "value", "reward", "flags")])
+
+
+class TrajGaeArgs(C.Structure):
+    _fields_ = ([("T", C.c_int64), ("N", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double)]
+                + [(n, C.c_void_p) for n in ("reward", "value", "flags", "adv", "ret", "stats", "scratch")])
+
+
+class TrajCompactArgs(C.Structure):
+    _fields_ = [("T", C.c_int64), ("N", C.c_int64)] + [(n, C.c_void_p) for n in ("flags", "idx", "count", "scratch")]
+
+
+class TrajGatherArgs(C.Structure):
+    _fields_ = ([("T", C.c_int64), ("N", C.c_int64), ("M", C.c_int64), ("obs_floats", C.c_int32), ("mask_bytes", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("pos", "obs", "mask", "action", "logp", "value", "ret", "adv", "flags", "stats", "out_obs",
+                                             "out_mask", "out_action", "out_logp", "out_value", "out_ret", "out_adv", "out_weight",
+                                             "rejected")])
+
+
+# flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
+TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
+
 # header words of a prioritized-replay tree (GVEC_PER_* in include/generals_vec.h)
 PER_HEADER_WORDS, PER_HDR_MAX, PER_HDR_REJECTED, PER_HDR_DRAWS = 64, 0, 1, 2
 
@@ -96,6 +122,11 @@ SYMBOLS = {
     "gvec_per_push": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64]),
     "gvec_per_update": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_float, C.c_float]),
     "gvec_per_sample": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_float, _vp, _u64, _vp, _vp]),
+    "gvec_traj_scratch_bytes": (_u64, [C.c_int64, C.c_int64]),
+    "gvec_traj_record": (_i32, [_i32, _vp, C.POINTER(TrajRecordArgs)]),
+    "gvec_traj_gae": (_i32, [_i32, _vp, C.POINTER(TrajGaeArgs)]),
+    "gvec_traj_compact": (_i32, [_i32, _vp, C.POINTER(TrajCompactArgs)]),
+    "gvec_traj_gather": (_i32, [_i32, _vp, C.POINTER(TrajGatherArgs)]),
     "gvec_gym_observe": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1505,6 +1505,93 @@ int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t ca
   return GVEC_OK;
 }
 
+// ---- on-policy rollouts (gvec_traj.hip) ----
+static int32_t traj_shape(const char* fn, int64_t T, int64_t N) {
+  if (T < 1 || N < 1 || T > ((int64_t)1 << 40) / N) {
+    set_err("%s: T %lld, N %lld: both must be >= 1 (and T * N <= 2^40)", fn, (long long)T, (long long)N);
+    return GVEC_E_INVALID;
+  }
+  return GVEC_OK;
+}
+static int32_t traj_null(const char* fn) {
+  set_err("%s: args or a required pointer is NULL", fn);
+  return GVEC_E_INVALID;
+}
+
+uint64_t gvec_traj_scratch_bytes(int64_t T, int64_t N) {
+  return traj_shape("gvec_traj_scratch_bytes", T, N) == GVEC_OK ? (uint64_t)traj_scratch_bytes(T, N) : 0;
+}
+
+int32_t gvec_traj_record(int32_t device, void* hip_stream, const gvec_traj_record_args* a) {
+  if (!a) return traj_null("gvec_traj_record");
+  if (a->num_envs < 1 || a->num_learners < 1) {
+    set_err("gvec_traj_record: num_envs %d, num_learners %d: N = num_envs * num_learners must be >= 1", a->num_envs, a->num_learners);
+    return GVEC_E_INVALID;
+  }
+  RET_IF(traj_shape("gvec_traj_record", a->T, (int64_t)a->num_envs * a->num_learners));
+  if (a->t < 0 || a->t >= a->T) {
+    set_err("gvec_traj_record: t %lld outside [0, T = %lld)", (long long)a->t, (long long)a->T);
+    return GVEC_E_INVALID;
+  }
+  if (!a->step_action || !a->step_logp || !a->step_value || !a->step_reward || !a->reset || !a->terminated || !a->truncated || !a->alive ||
+      !a->alive_state || !a->action || !a->logp || !a->value || !a->reward || !a->flags)
+    return traj_null("gvec_traj_record");
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_traj_record(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_traj_gae(int32_t device, void* hip_stream, const gvec_traj_gae_args* a) {
+  if (!a) return traj_null("gvec_traj_gae");
+  RET_IF(traj_shape("gvec_traj_gae", a->T, a->N));
+  if (!(a->gamma >= 0.0 && a->gamma <= 1.0) || !(a->lambda >= 0.0 && a->lambda <= 1.0)) {
+    set_err("gvec_traj_gae: gamma %g or lambda %g outside [0, 1]", a->gamma, a->lambda);
+    return GVEC_E_INVALID;
+  }
+  if (!a->reward || !a->value || !a->flags || !a->adv || !a->ret || !a->stats || !a->scratch) return traj_null("gvec_traj_gae");
+  if (reinterpret_cast<uintptr_t>(a->scratch) & 15) {
+    set_err("gvec_traj_gae: scratch must be 16-byte aligned");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_traj_gae(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_traj_compact(int32_t device, void* hip_stream, const gvec_traj_compact_args* a) {
+  if (!a) return traj_null("gvec_traj_compact");
+  RET_IF(traj_shape("gvec_traj_compact", a->T, a->N));
+  if (!a->flags || !a->idx || !a->count || !a->scratch) return traj_null("gvec_traj_compact");
+  if (reinterpret_cast<uintptr_t>(a->scratch) & 15) {
+    set_err("gvec_traj_compact: scratch must be 16-byte aligned");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_traj_compact(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_traj_gather(int32_t device, void* hip_stream, const gvec_traj_gather_args* a) {
+  if (!a) return traj_null("gvec_traj_gather");
+  RET_IF(traj_shape("gvec_traj_gather", a->T, a->N));
+  if (a->M < 0 || a->obs_floats < 1 || a->mask_bytes < 0) {
+    set_err("gvec_traj_gather: M %lld < 0, obs_floats %d < 1 or mask_bytes %d < 0", (long long)a->M, a->obs_floats, a->mask_bytes);
+    return GVEC_E_INVALID;
+  }
+  if (a->M == 0) return GVEC_OK;
+  if (!a->pos || !a->obs || !a->action || !a->logp || !a->value || !a->ret || !a->adv || !a->flags || !a->out_obs || !a->out_action ||
+      !a->out_logp || !a->out_value || !a->out_ret || !a->out_adv || !a->out_weight || !a->rejected ||
+      (a->mask_bytes > 0 && (!a->mask || !a->out_mask)))
+    return traj_null("gvec_traj_gather");
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_traj_gather(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
 int32_t gvec_record_agent_actions(gvec_handle* h, int32_t on) {
   if (!h) return GVEC_E_INVALID;
   if (h->sharded()) {

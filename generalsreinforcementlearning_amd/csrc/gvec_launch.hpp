@@ -291,4 +291,11 @@ hipError_t launch_per_update(float* tree, const PerLayout& y, const long long* i
 hipError_t launch_per_sample(float* tree, const PerLayout& y, const long long* ring_counters, long long k, float beta, const double* u,
                              unsigned long long seed, long long* idx, float* weight, hipStream_t s);
 
+// on-policy rollouts (gvec_traj.hip; generals_vec.h "on-policy self-play rollouts")
+size_t traj_scratch_bytes(long long T, long long N);
+hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s);
+hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s);
+hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s);
+hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s);
+
 }  // namespace gvec

@@ -1,0 +1,345 @@
+// gvec_traj.hip — on-policy self-play rollouts in HBM: the per-step record, generalized advantage estimation, the compaction
+// of the valid rows and the minibatch gather (gvec_traj_* in generals_vec.h).
+//
+// A rollout is T rows of N = B * L streams, learner-minor as gvec_gym_step_players emits them; row t, stream n sits at
+// position p = t * N + n of every store.  flags[p] carries the episode protocol (GVEC_TRAJ_VALID / _TERMINAL / _CUT), so the
+// recurrence and the gather never look at the env's own arrays again.
+#include "gvec_launch.hpp"
+
+namespace gvec {
+
+namespace {
+
+constexpr int TRAJ_WAVES = 4;          // wavefronts per workgroup of the row mover
+constexpr int GAE_ROWS = 32;           // rows a lane has in flight: the loads do not depend on the recurrence
+constexpr int COMPACT_BLOCK = 1024;    // positions per workgroup of the compaction (256 threads, four each)
+
+__device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63u); }
+__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ long long uni_ll(long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// ---- record: one thread per stream ----
+__global__ __launch_bounds__(256) void traj_record_kernel(gvec_traj_record_args A) {
+  const long long N = (long long)A.num_envs * A.num_learners;
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const long long b = n / A.num_learners, p = A.t * N + n;
+  const bool was_alive = A.alive_state[n] != 0, alive = A.alive[n] != 0;
+  const bool reset = A.reset[b] != 0, term = A.terminated[b] != 0, trunc = A.truncated[b] != 0;
+  const bool valid = !reset && was_alive;
+  uint32_t f = 0;
+  if (valid) f = GVEC_TRAJ_VALID | ((term || !alive) ? GVEC_TRAJ_TERMINAL : 0) | ((term || trunc || !alive) ? GVEC_TRAJ_CUT : 0);
+  A.action[p] = A.step_action[n];
+  A.logp[p] = A.step_logp[n];
+  A.value[p] = A.step_value[n];
+  A.reward[p] = A.step_reward[n];
+  A.flags[p] = (uint8_t)f;
+  A.alive_state[n] = alive ? 1 : 0;
+}
+
+// ---- GAE: one lane per stream walks t = T-1 .. 0; a wavefront's loads of a row are one coalesced line per array ----
+__device__ __forceinline__ double wave_sum(double x) {   // a fixed butterfly: the same bits on every run
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+  return x;
+}
+__global__ __launch_bounds__(64) void traj_gae_kernel(gvec_traj_gae_args A) {
+  const long long N = A.N, T = A.T;
+  const long long n0 = (long long)blockIdx.x * 64 + lane();
+  const bool act = n0 < N;
+  const long long n = act ? n0 : N - 1;             // the tail lanes of the last wavefront read a real stream and store nothing
+  const double* __restrict__ reward = A.reward;
+  const float* __restrict__ value = A.value;
+  const uint8_t* __restrict__ flags = A.flags;
+  float* __restrict__ adv = A.adv;
+  float* __restrict__ ret = A.ret;
+  const double g = A.gamma, gl = A.gamma * A.lambda;
+  double carry = 0.0, next_v = (double)value[T * N + n];
+  double cnt = 0.0, s1 = 0.0, s2 = 0.0;
+  for (long long hi = T; hi > 0; hi -= GAE_ROWS) {  // rows hi-1 .. hi-GAE_ROWS: all their loads first, then the recurrence
+    double r[GAE_ROWS];
+    float v[GAE_ROWS];
+    uint32_t f[GAE_ROWS];
+#pragma unroll
+    for (int i = 0; i < GAE_ROWS; ++i) {
+      const long long t = hi - 1 - i, o = (t < 0 ? 0 : t) * N + n;
+      r[i] = reward[o];
+      v[i] = value[o];
+      f[i] = flags[o];
+    }
+#pragma unroll
+    for (int i = 0; i < GAE_ROWS; ++i) {
+      const long long t = hi - 1 - i;
+      if (t < 0) continue;                          // the same in every lane
+      const double vt = (double)v[i];
+      double a = 0.0, rt = vt;
+      if (f[i] & GVEC_TRAJ_VALID) {
+        const double delta = (r[i] + g * ((f[i] & GVEC_TRAJ_TERMINAL) ? 0.0 : next_v)) - vt;
+        a = delta + gl * ((f[i] & GVEC_TRAJ_CUT) ? 0.0 : carry);
+        rt = a + vt;
+      }
+      carry = a;                                    // an invalid row clears it
+      next_v = vt;
+      const float a32 = (float)a;
+      if (act) {
+        adv[t * N + n] = a32;
+        ret[t * N + n] = (float)rt;
+        if (f[i] & GVEC_TRAJ_VALID) {               // the statistics describe adv as stored
+          const double x = (double)a32;
+          cnt += 1.0;
+          s1 += x;
+          s2 += x * x;
+        }
+      }
+    }
+  }
+  cnt = wave_sum(cnt);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  if (lane() == 0) {
+    double* part = static_cast<double*>(A.scratch) + (size_t)blockIdx.x * 3;
+    part[0] = cnt;
+    part[1] = s1;
+    part[2] = s2;
+  }
+}
+// second stage, one workgroup: thread i adds partials i, i + 256, ... in that order, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(256) void traj_stats_kernel(const double* part, long long groups, double* stats) {
+  __shared__ double sh[3][256];
+  const int tid = (int)threadIdx.x;
+  double c = 0.0, s1 = 0.0, s2 = 0.0;
+  for (long long gi = tid; gi < groups; gi += 256) {
+    c += part[gi * 3];
+    s1 += part[gi * 3 + 1];
+    s2 += part[gi * 3 + 2];
+  }
+  sh[0][tid] = c;
+  sh[1][tid] = s1;
+  sh[2][tid] = s2;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (tid < off) {
+      sh[0][tid] += sh[0][tid + off];
+      sh[1][tid] += sh[1][tid + off];
+      sh[2][tid] += sh[2][tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid < 4) stats[tid] = tid < 3 ? sh[tid][0] : 0.0;
+}
+
+// ---- compaction: the ascending positions of the VALID rows ----
+// scratch: cnt[G] valid rows per COMPACT_BLOCK positions, base[G] their exclusive prefix
+__host__ __device__ inline long long compact_groups(long long total) { return (total + COMPACT_BLOCK - 1) / COMPACT_BLOCK; }
+// thread `tid` of workgroup `blk` owns positions blk * 1024 + k * 256 + tid, k < 4: sub-run q = k * 4 + wave is 64 consecutive positions
+__device__ __forceinline__ void compact_ballots(const uint8_t* flags, long long total, long long blk, unsigned long long m[4], int* runs) {
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long p = blk * COMPACT_BLOCK + k * 256 + tid;
+    const bool v = p < total && (flags[p < total ? p : 0] & GVEC_TRAJ_VALID);
+    m[k] = __ballot(v);
+    if (lane() == 0) runs[k * 4 + wave] = __popcll(m[k]);
+  }
+  __syncthreads();
+}
+__global__ __launch_bounds__(256) void traj_compact_count_kernel(gvec_traj_compact_args A) {
+  __shared__ int runs[16];
+  unsigned long long m[4];
+  compact_ballots(A.flags, A.T * A.N, blockIdx.x, m, runs);
+  if (threadIdx.x == 0) {
+    long long c = 0;
+    for (int q = 0; q < 16; ++q) c += runs[q];
+    static_cast<long long*>(A.scratch)[blockIdx.x] = c;
+  }
+}
+// one workgroup: exclusive prefix of cnt[G] (a thread owns a run of consecutive groups), and the total
+__global__ __launch_bounds__(1024) void traj_compact_scan_kernel(gvec_traj_compact_args A) {
+  __shared__ long long part[1024];
+  const long long G = compact_groups(A.T * A.N);
+  const long long* cnt = static_cast<const long long*>(A.scratch);
+  long long* base = static_cast<long long*>(A.scratch) + G;
+  const int tid = (int)threadIdx.x;
+  const long long per = (G + 1023) / 1024;
+  const long long lo = tid * per < G ? tid * per : G, hi = lo + per < G ? lo + per : G;
+  long long mine = 0;
+  for (long long gi = lo; gi < hi; ++gi) mine += cnt[gi];
+  part[tid] = mine;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {        // Hillis-Steele inclusive scan of the 1,024 partial sums
+    const long long a = tid >= off ? part[tid - off] : 0;
+    __syncthreads();
+    part[tid] += a;
+    __syncthreads();
+  }
+  long long run = part[tid] - mine;
+  for (long long gi = lo; gi < hi; ++gi) {
+    base[gi] = run;
+    run += cnt[gi];
+  }
+  if (tid == 1023) *reinterpret_cast<long long*>(A.count) = part[1023];
+}
+__global__ __launch_bounds__(256) void traj_compact_write_kernel(gvec_traj_compact_args A) {
+  __shared__ int runs[16];
+  unsigned long long m[4];
+  const long long total = A.T * A.N, G = compact_groups(total);
+  compact_ballots(A.flags, total, blockIdx.x, m, runs);
+  const long long base = (static_cast<const long long*>(A.scratch) + G)[blockIdx.x];
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+  long long* idx = reinterpret_cast<long long*>(A.idx);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int before = 0;
+    for (int q = 0; q < k * 4 + wave; ++q) before += runs[q];
+    if ((m[k] >> lane()) & 1) idx[base + before + __popcll(m[k] & ((1ull << lane()) - 1))] = blockIdx.x * (long long)COMPACT_BLOCK + k * 256 + tid;
+  }
+}
+
+// ---- gather: the row mover ----
+// A row of n floats from s to d, both only dword-aligned (a row is 9 * W * H floats: 8,100 bytes at 15x15) and not alike: the
+// scheme of gvec_pool_collect's copy_row (gvec_kernels.hip), restated here so that no existing kernel's code changes.
+// Sixteen bytes per lane with BOTH sides on 16-byte boundaries: destination quad j (floats [kd + 4j, kd + 4j + 4) of the row)
+// is cut out of the aligned source quads j and j + 1 counted from s + kd - a, a = the floats by which the two sides differ.
+// Only quads that lie inside the row are read; the floats before / after that body go one by one (part 0).
+template <int D>
+__device__ __forceinline__ void move_quads(const float4* __restrict__ sq, float4* __restrict__ dq, int jlo, int jhi, int first, int stride) {
+#pragma unroll 4
+  for (int j = jlo + first; j < jhi; j += stride) {
+    const float4 lo = sq[j];
+    float4 o;
+    if (D == 0) {
+      o = lo;
+    } else {
+      const float4 hi = sq[j + 1];
+      if (D == 1) o = make_float4(lo.y, lo.z, lo.w, hi.x);
+      if (D == 2) o = make_float4(lo.z, lo.w, hi.x, hi.y);
+      if (D == 3) o = make_float4(lo.w, hi.x, hi.y, hi.z);
+    }
+    dq[j] = o;
+  }
+}
+__device__ __forceinline__ void move_row_f32(const float* __restrict__ s, float* __restrict__ d, int n, int part, int shift) {
+  const int kd = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(d) & 15u)) & 15u) >> 2);   // floats before d is 16-byte aligned
+  const int a = uni_i((int)((reinterpret_cast<uintptr_t>(s + kd) >> 2) & 3u));                   // s + kd sits a floats into its quad
+  // source quad j spans floats [kd - a + 4j, + 4) of the row; j and (a != 0) j + 1 must lie in [0, n)
+  const int jlo = a > kd ? 1 : 0;
+  const int room = a ? n - 8 - kd + a : n - 4 - kd;
+  const int jhi = room < 0 ? jlo : (room / 4 + 1 > jlo ? room / 4 + 1 : jlo);                    // exclusive
+  const float4* sq = reinterpret_cast<const float4*>(s + kd - a);
+  float4* dq = reinterpret_cast<float4*>(d + kd);
+  const int first = part * 64 + lane(), stride = 64 << shift;
+  switch (a) {
+    case 0: move_quads<0>(sq, dq, jlo, jhi, first, stride); break;
+    case 1: move_quads<1>(sq, dq, jlo, jhi, first, stride); break;
+    case 2: move_quads<2>(sq, dq, jlo, jhi, first, stride); break;
+    default: move_quads<3>(sq, dq, jlo, jhi, first, stride); break;
+  }
+  if (part == 0) {
+    int head = kd + 4 * jlo, tail = kd + 4 * jhi;       // [0, head) and [tail, n): a few floats each (all of a very short row)
+    if (jhi == jlo) head = tail = 0;
+    for (int k = lane(); k < head && k < n; k += 64) d[k] = s[k];
+    for (int k = tail + lane(); k < n; k += 64) d[k] = s[k];
+  }
+}
+// The same for a row of n BYTES (a mask row is 5 * W * H bytes: 1,125 at 15x15, aligned to nothing): four bytes per lane, the
+// stores on dword boundaries, a destination dword cut out of two aligned source dwords by v_alignbyte.
+__device__ __forceinline__ void move_row_u8(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int n, int part, int shift) {
+  const int kd = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(d) & 3u)) & 3u);
+  const int a = uni_i((int)(reinterpret_cast<uintptr_t>(s + kd) & 3u));
+  const int jlo = a > kd ? 1 : 0;
+  const int room = a ? n - 8 - kd + a : n - 4 - kd;
+  const int jhi = room < 0 ? jlo : (room / 4 + 1 > jlo ? room / 4 + 1 : jlo);
+  const uint32_t* __restrict__ sw = reinterpret_cast<const uint32_t*>(s + kd - a);
+  uint32_t* __restrict__ dw = reinterpret_cast<uint32_t*>(d + kd);
+  const int first = part * 64 + lane(), stride = 64 << shift;
+  if (a == 0) {
+    for (int j = jlo + first; j < jhi; j += stride) dw[j] = sw[j];
+  } else {
+    for (int j = jlo + first; j < jhi; j += stride) dw[j] = __builtin_amdgcn_alignbyte(sw[j + 1], sw[j], (uint32_t)a);
+  }
+  if (part == 0) {
+    int head = kd + 4 * jlo, tail = kd + 4 * jhi;
+    if (jhi == jlo) head = tail = 0;
+    for (int k = lane(); k < head && k < n; k += 64) d[k] = s[k];
+    for (int k = tail + lane(); k < n; k += 64) d[k] = s[k];
+  }
+}
+
+// 1 << shift wavefronts per minibatch row
+__global__ __launch_bounds__(64 * TRAJ_WAVES) void traj_gather_kernel(gvec_traj_gather_args A, int shift) {
+  const long long gw = uni_ll((long long)blockIdx.x * TRAJ_WAVES + (threadIdx.x >> 6));
+  const long long i = gw >> shift;
+  const int part = (int)(gw & ((1 << shift) - 1));
+  if (i >= A.M) return;
+  const long long p = uni_ll(A.pos[i]);
+  float* dobs = A.out_obs + (size_t)i * A.obs_floats;
+  uint8_t* dmask = A.out_mask + (size_t)i * A.mask_bytes;
+  const int first = part * 64 + lane(), stride = 64 << shift;
+  if (p < 0 || p >= A.T * A.N) {                   // a position the host never saw: a zeroed row that weighs nothing
+    for (int k = first; k < A.obs_floats; k += stride) dobs[k] = 0.0f;
+    for (int k = first; k < A.mask_bytes; k += stride) dmask[k] = 0;
+    if (first == 0) {
+      A.out_action[i] = 0;
+      A.out_logp[i] = A.out_value[i] = A.out_ret[i] = A.out_adv[i] = A.out_weight[i] = 0.0f;
+      atomicAdd(reinterpret_cast<unsigned long long*>(A.rejected), 1ull);
+    }
+    return;
+  }
+  move_row_f32(A.obs + (size_t)p * A.obs_floats, dobs, A.obs_floats, part, shift);
+  if (A.mask_bytes > 0) move_row_u8(A.mask + (size_t)p * A.mask_bytes, dmask, A.mask_bytes, part, shift);
+  if (first == 0) {
+    A.out_action[i] = A.action[p];
+    A.out_logp[i] = A.logp[p];
+    A.out_value[i] = A.value[p];
+    A.out_ret[i] = A.ret[p];
+    float a = A.adv[p];
+    if (A.stats) {
+      const double c = A.stats[0];
+      const double mean = c > 0.0 ? A.stats[1] / c : 0.0;
+      double var = c > 0.0 ? A.stats[2] / c - mean * mean : 0.0;
+      var = var > 0.0 ? var : 0.0;
+      a = (float)(((double)a - mean) / sqrt(var + 1e-8));
+    }
+    A.out_adv[i] = a;
+    A.out_weight[i] = (A.flags[p] & GVEC_TRAJ_VALID) ? 1.0f : 0.0f;
+  }
+}
+
+}  // namespace
+
+size_t traj_scratch_bytes(long long T, long long N) {
+  const size_t gae = (size_t)((N + 63) / 64) * 3 * 8;
+  const size_t compact = (size_t)compact_groups(T * N) * 2 * 8;
+  return ((gae > compact ? gae : compact) + 255) / 256 * 256;
+}
+hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s) {
+  const long long N = (long long)a.num_envs * a.num_learners;
+  hipLaunchKernelGGL(traj_record_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s) {
+  const long long groups = (a.N + 63) / 64;
+  hipLaunchKernelGGL(traj_gae_kernel, dim3((unsigned)groups), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(traj_stats_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(a.scratch), groups, a.stats);
+  return hipGetLastError();
+}
+hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s) {
+  const dim3 grid((unsigned)compact_groups(a.T * a.N));
+  hipLaunchKernelGGL(traj_compact_count_kernel, grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL(traj_compact_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(traj_compact_write_kernel, grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s) {
+  int shift = 0;                                   // enough wavefronts to fill 256 CUs when the batch is small
+  while (shift < 3 && (a.M << shift) < 16384) ++shift;
+  const long long waves = a.M << shift;
+  hipLaunchKernelGGL(traj_gather_kernel, dim3((unsigned)((waves + TRAJ_WAVES - 1) / TRAJ_WAVES)), dim3(64 * TRAJ_WAVES), 0, s, a, shift);
+  return hipGetLastError();
+}
+
+}  // namespace gvec

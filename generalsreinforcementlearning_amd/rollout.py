@@ -1,0 +1,228 @@
+"""SelfPlayRolloutBuffer — on-policy (PPO) collection from GeneralsSelfPlayVecEnv without leaving the device.
+
+A rollout is `horizon` = T steps of N = num_envs * num_learners streams ([B][L], learner-minor, as the env emits them).  The
+buffer owns every store in HBM: observations and masks of T + 1 slots (the env's step launch writes slot t + 1 directly: no
+second copy of the 8 to 14 KB rows), action / log-prob / value / reward / flags per row, and after `finish` advantages and
+returns.  Four HIP entry points do the work (include/generals_vec.h): gvec_traj_record (one launch
+per step), gvec_traj_gae, gvec_traj_compact, gvec_traj_gather.
+
+The episode protocol, which the flags of a row encode (TRAJ_VALID / TRAJ_TERMINAL / TRAJ_CUT):
+  - a step that re-dealt its env (info["reset"]) is no transition: the action was ignored - its rows are invalid;
+  - a learner that was eliminated before the step has no transition - invalid; the step that eliminates it is terminal for it;
+  - a truncated episode bootstraps from the value of its final observation: that observation is slot t + 1, the row after
+    it is the env's re-deal row, so value[t + 1] is exactly the bootstrap and no special case exists.
+Precondition: every board holds max_players players (GeneralsSelfPlayVecEnv always deals such boards).
+
+    buf = SelfPlayRolloutBuffer(env, horizon=128)
+    buf.begin(*env.reset())
+    while training:
+        while not buf.full:
+            actions, logp, value = policy(buf.obs, buf.valid_actions_mask)
+            buf.step(actions, logp, value)
+        buf.finish(policy.value(buf.obs))
+        for batch in buf.minibatches(4096, epochs=4):
+            ...                      # batch["weight"] is 0 for the invalid rows
+        buf.next_rollout()
+
+Nothing here synchronises with the host, except minibatches(compact=True): one 8-byte read per rollout.
+"""
+import ctypes as C
+
+from ._lib import TRAJ_VALID, TrajCompactArgs, TrajGaeArgs, TrajGatherArgs, TrajRecordArgs, check, load
+
+
+class SelfPlayRolloutBuffer:
+    def __init__(self, env, horizon, gamma=0.99, gae_lambda=0.95):
+        import torch
+        if not getattr(env, "device_outputs", False):
+            raise ValueError("SelfPlayRolloutBuffer needs an env built with device_outputs=True")
+        if horizon < 1:
+            raise ValueError(f"horizon must be >= 1: {horizon}")
+        if not (0.0 <= gamma <= 1.0 and 0.0 <= gae_lambda <= 1.0):
+            raise ValueError(f"gamma and gae_lambda must lie in [0, 1]: {gamma}, {gae_lambda}")
+        self._t = t = torch
+        self.env = env
+        self.horizon = T = int(horizon)
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        self.num_envs, self.num_learners = B, L = env.num_envs, env.num_learners
+        self.num_streams = N = B * L
+        self._dev = dev = env._dev
+        self._L = load()
+        H, W, nb = env.board_height, env.board_width, env.board_size
+        self.obs_floats, self.mask_bytes = 9 * nb, 5 * nb
+        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=dev)
+        self.obs_store = z((T + 1, B, L, 9, H, W), t.float32)
+        self.mask_store = z((T + 1, B, L, 5 * nb), t.uint8)
+        self.action, self.logp, self.value = z((T, N), t.int64), z((T, N), t.float32), z((T + 1, N), t.float32)
+        self.reward, self.flags = z((T, N), t.float64), z((T, N), t.uint8)
+        self._adv, self._ret = z((T, N), t.float32), z((T, N), t.float32)
+        self.stats = z(4, t.float64)
+        self.alive_state = t.ones(N, dtype=t.uint8, device=dev)
+        self._scratch = z(int(self._L.gvec_traj_scratch_bytes(T, N)), t.uint8)
+        self._idx, self._count, self.rejected = None, z(1, t.int64), z(1, t.int64)
+        self._valid_count = None
+        self._out = {}
+        self._step = 0
+        self._finished = False
+        self._rec = TrajRecordArgs(T=T, t=0, num_envs=B, num_learners=L, alive_state=self.alive_state.data_ptr(),
+                                   action=self.action.data_ptr(), logp=self.logp.data_ptr(), value=self.value.data_ptr(),
+                                   reward=self.reward.data_ptr(), flags=self.flags.data_ptr())
+        self._rec_ref = C.byref(self._rec)
+
+    # ---- collection ---------------------------------------------------------------------------------------------------
+    def _stream(self):
+        return self._t.cuda.current_stream(self._dev).cuda_stream
+
+    @property
+    def full(self):
+        return self._step >= self.horizon
+
+    @property
+    def obs(self):
+        """The current observation [B, L, 9, H, W]: a view of slot t."""
+        return self.obs_store[self._step]
+
+    @property
+    def valid_actions_mask(self):
+        return self.mask_store[self._step].view(self._t.bool)
+
+    def begin(self, obs, info):
+        """After env.reset(): slot 0 takes the observation and the mask, every learner is alive."""
+        self.obs_store[0].copy_(obs)
+        self.mask_store[0].copy_(info["valid_actions_mask"].view(self._t.uint8))
+        self.alive_state.fill_(1)
+        self._restart()
+
+    def _restart(self):
+        self._step, self._finished, self._valid_count = 0, False, None
+
+    def _as(self, x, dtype):
+        t = self._t
+        if not (isinstance(x, t.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() == self.num_streams):
+            x = t.as_tensor(x, dtype=dtype).to(self._dev).reshape(self.num_streams).contiguous()
+        return x
+
+    def step(self, actions, logp, value):
+        """env.step(actions) with the observation and mask written into slot t + 1, then row t of the small stores in one
+        launch.  actions int64, logp / value float32, [B, L] each (CUDA, contiguous: anything else is converted first).
+        Returns the env's tuple."""
+        k = self._step
+        if k >= self.horizon:
+            raise RuntimeError(f"the rollout is full ({self.horizon} steps): finish() and next_rollout() come first")
+        t = self._t
+        actions, logp, value = self._as(actions, t.int64), self._as(logp, t.float32), self._as(value, t.float32)
+        out = self.env.step(actions, obs_out=self.obs_store[k + 1], mask_out=self.mask_store[k + 1])
+        _, reward, terminated, truncated, info = out
+        r = self._rec
+        r.t = k
+        r.step_action, r.step_logp, r.step_value, r.step_reward = actions.data_ptr(), logp.data_ptr(), value.data_ptr(), reward.data_ptr()
+        r.reset, r.terminated, r.truncated, r.alive = (info["reset"].data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                                       info["alive"].data_ptr())
+        check(self._L.gvec_traj_record(self._dev.index, self._stream(), self._rec_ref), "gvec_traj_record")
+        self._step = k + 1
+        return out
+
+    def finish(self, last_value):
+        """last_value [B, L]: the value of the current observation (slot T), the bootstrap of every stream still running.
+        Runs gvec_traj_gae; afterwards advantages / returns / valid / stats are set."""
+        if not self.full:
+            raise RuntimeError(f"finish() after {self._step} of {self.horizon} steps")
+        T, N = self.horizon, self.num_streams
+        self.value[T].copy_(self._as(last_value, self._t.float32).view(-1))
+        a = TrajGaeArgs(T=T, N=N, gamma=self.gamma, lam=self.gae_lambda, reward=self.reward.data_ptr(), value=self.value.data_ptr(),
+                        flags=self.flags.data_ptr(), adv=self._adv.data_ptr(), ret=self._ret.data_ptr(), stats=self.stats.data_ptr(),
+                        scratch=self._scratch.data_ptr())
+        check(self._L.gvec_traj_gae(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_gae")
+        self._finished = True
+
+    def _done(self):
+        if not self._finished:
+            raise RuntimeError("advantages exist after finish()")
+        return (self.horizon, self.num_envs, self.num_learners)
+
+    @property
+    def advantages(self):
+        return self._adv.view(self._done())
+
+    @property
+    def returns(self):
+        return self._ret.view(self._done())
+
+    @property
+    def valid(self):
+        return (self.flags & TRAJ_VALID).bool().view(self._done())
+
+    # ---- minibatches ----------------------------------------------------------------------------------------------------
+    def _outputs(self, m):
+        o = self._out.get(m)
+        if o is None:
+            t, env = self._t, self.env
+            e = lambda shape, dt: t.empty(shape, dtype=dt, device=self._dev)
+            o = self._out[m] = {"obs": e((m, 9, env.board_height, env.board_width), t.float32), "mask": e((m, self.mask_bytes), t.uint8),
+                                "action": e(m, t.int64), "logp": e(m, t.float32), "value": e(m, t.float32), "ret": e(m, t.float32),
+                                "adv": e(m, t.float32), "weight": e(m, t.float32)}
+        return o
+
+    def gather(self, pos, normalize=True):
+        """The rows at positions pos (int64 CUDA tensor [M], p = t * N + b * L + l) as one batch: a dict of obs [M, 9, H, W],
+        valid_actions_mask bool [M, 5 * H * W], action, logp, value, returns, advantages (normalised over the rollout's valid
+        rows when `normalize`) and weight (1 for a valid row, 0 otherwise) [M].  The tensors are reused by the next gather of
+        the same M."""
+        self._done()
+        m = int(pos.numel())
+        o = self._outputs(m)
+        a = TrajGatherArgs(T=self.horizon, N=self.num_streams, M=m, obs_floats=self.obs_floats, mask_bytes=self.mask_bytes,
+                           pos=pos.data_ptr(), obs=self.obs_store.data_ptr(), mask=self.mask_store.data_ptr(), action=self.action.data_ptr(),
+                           logp=self.logp.data_ptr(), value=self.value.data_ptr(), ret=self._ret.data_ptr(), adv=self._adv.data_ptr(),
+                           flags=self.flags.data_ptr(), stats=self.stats.data_ptr() if normalize else None, out_obs=o["obs"].data_ptr(),
+                           out_mask=o["mask"].data_ptr(), out_action=o["action"].data_ptr(), out_logp=o["logp"].data_ptr(),
+                           out_value=o["value"].data_ptr(), out_ret=o["ret"].data_ptr(), out_adv=o["adv"].data_ptr(),
+                           out_weight=o["weight"].data_ptr(), rejected=self.rejected.data_ptr())
+        check(self._L.gvec_traj_gather(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_gather")
+        return {"obs": o["obs"], "valid_actions_mask": o["mask"].view(self._t.bool), "action": o["action"], "logp": o["logp"],
+                "value": o["value"], "returns": o["ret"], "advantages": o["adv"], "weight": o["weight"], "index": pos}
+
+    def valid_positions(self):
+        """(idx, count): the ascending positions of the valid rows in idx[:count] (gvec_traj_compact), count a Python int -
+        the one host read of a rollout, made once and remembered until the next rollout."""
+        self._done()
+        t = self._t
+        if self._valid_count is None:
+            T, N = self.horizon, self.num_streams
+            if self._idx is None:
+                self._idx = t.empty(T * N, dtype=t.int64, device=self._dev)
+            a = TrajCompactArgs(T=T, N=N, flags=self.flags.data_ptr(), idx=self._idx.data_ptr(), count=self._count.data_ptr(),
+                                scratch=self._scratch.data_ptr())
+            check(self._L.gvec_traj_compact(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_compact")
+            self._valid_count = int(self._count.item())
+        return self._idx, self._valid_count
+
+    def minibatches(self, batch_size, epochs=1, normalize=True, compact=False, seed=None):
+        """Yields `epochs` shuffled passes over the rollout in batches of batch_size rows (the last of a pass may be shorter).
+        compact=False  permutes all T * N rows: no host sync at all; invalid rows come with weight 0 (multiply the loss by
+                       it) and cost their share of the batch - a few percent at long episodes, more when max_turns is short.
+        compact=True   permutes only the valid rows: every row of every batch counts, at the price of one 8-byte read of
+                       their number per rollout (the host needs it to size the batches)."""
+        t = self._t
+        self._done()
+        gen = None
+        if seed is not None:
+            gen = t.Generator(device=self._dev)
+            gen.manual_seed(int(seed))
+        if compact:
+            idx, total = self.valid_positions()
+        else:
+            idx, total = None, self.horizon * self.num_streams
+        for _ in range(epochs):
+            perm = t.randperm(total, device=self._dev, generator=gen)
+            if idx is not None:
+                perm = idx[perm]
+            for lo in range(0, total, batch_size):
+                yield self.gather(perm[lo:lo + batch_size], normalize)
+
+    def next_rollout(self):
+        """Slot T becomes slot 0 (one slot's copy); alive_state carries over; the stores are reused."""
+        T = self.horizon
+        self.obs_store[0].copy_(self.obs_store[T])
+        self.mask_store[0].copy_(self.mask_store[T])
+        self._restart()

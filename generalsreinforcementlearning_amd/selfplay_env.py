@@ -123,7 +123,23 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
             a = self._arg_cache[key] = (ptrs, obs, out, info)
         return a
 
-    def _step_device(self, actions):
+    def _slot_args(self, k, obs_out, mask_out):
+        """_step_args for a step that writes its observation and mask into the caller's tensors (zero-copy slots)."""
+        t, B, L = self._t, self.num_envs, self.num_learners
+        n = B * L * 9 * self.board_size
+        if not (isinstance(obs_out, t.Tensor) and obs_out.is_cuda and obs_out.device == self._dev and obs_out.dtype == t.float32
+                and obs_out.is_contiguous() and obs_out.numel() == n):
+            raise ValueError(f"obs_out must be a contiguous float32 CUDA tensor of {n} elements on {self._dev}")
+        if not (isinstance(mask_out, t.Tensor) and mask_out.is_cuda and mask_out.device == self._dev
+                and mask_out.dtype in (t.uint8, t.bool) and mask_out.is_contiguous() and mask_out.numel() == B * L * self.board_size * 5):
+            raise ValueError(f"mask_out must be a contiguous uint8 / bool CUDA tensor of {B * L * self.board_size * 5} elements on {self._dev}")
+        ptrs, _, out, info = self._step_args(k, self._obs_flip)
+        obs = obs_out.view(B, L, 9, self.board_height, self.board_width)
+        info = dict(info)
+        info["valid_actions_mask"] = mask_out.view(t.bool).view(B, L, self.board_size * 5)
+        return ptrs[:3] + (obs_out.data_ptr(), mask_out.data_ptr()) + ptrs[5:], obs, out, info
+
+    def _step_device(self, actions, obs_out=None, mask_out=None):
         t, e = self._t, self.engine
         B, L = self.num_envs, self.num_learners
         if not (isinstance(actions, t.Tensor) and actions.is_cuda and actions.dtype == t.int64 and actions.is_contiguous()
@@ -131,11 +147,16 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
             if isinstance(actions, np.ndarray):
                 actions = t.from_numpy(np.ascontiguousarray(actions, np.int64))
             actions = t.as_tensor(actions, dtype=t.int64).to(self._dev).reshape(B, L).contiguous()
-        self.last_actions = actions        # the tensor the launch reads (kept alive until the next step)
         k = self._step_no
+        if obs_out is None and mask_out is None:
+            self._obs_flip ^= 1
+            ptrs, obs, out, info = self._step_args(k, self._obs_flip)
+        elif obs_out is None or mask_out is None:
+            raise ValueError("obs_out and mask_out go together: give both or neither")
+        else:                              # the env's own observation buffers sit this step out (and keep their rotation)
+            ptrs, obs, out, info = self._slot_args(k, obs_out, mask_out)
+        self.last_actions = actions        # the tensor the launch reads (kept alive until the next step)
         self._step_no += 1
-        self._obs_flip ^= 1
-        ptrs, obs, out, info = self._step_args(k, self._obs_flip)
         # ONE launch: every learner's action decoded against its own view of the resident state, the other players' moves
         # from the on-device agent, the turn (or the re-deal of a `resetting` env), then every learner's observation / mask /
         # reward and the env's flags
@@ -167,8 +188,17 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
         obs, info = self._reset_device()
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 
-    def step(self, actions):
-        """actions: [num_envs, num_learners] indices into Discrete(board_size * 5), column j for player_ids[j]."""
+    def step(self, actions, obs_out=None, mask_out=None):
+        """actions: [num_envs, num_learners] indices into Discrete(board_size * 5), column j for player_ids[j].
+        obs_out / mask_out (device_outputs=True only, both or neither): contiguous CUDA tensors on the env's device - float32
+        with the observation's numel, uint8 or bool with the mask's - that the launch writes the observation and the mask
+        straight into (a slot of a rollout store: no second copy of the rows); the returned obs and
+        info["valid_actions_mask"] are views of them, and they stay intact for as long as the caller leaves them alone.  A
+        slot needs no alignment beyond its dtype's.  ValueError otherwise."""
+        if obs_out is not None or mask_out is not None:
+            if not self.device_outputs:
+                raise ValueError("obs_out / mask_out need device_outputs=True")
+            return self._step_device(actions, obs_out, mask_out)
         if self.device_outputs:
             return self._step_device(actions)
         obs, reward, terminated, truncated, info = self._step_device(np.asarray(actions, np.int64))

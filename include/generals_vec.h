@@ -564,6 +564,84 @@ int32_t gvec_per_update(int32_t device, void* hip_stream, void* tree, int64_t ca
 int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* ring_counters, int64_t k,
                         float beta, const double* u, uint64_t seed, int64_t* idx, float* weight);
 
+/* ---- on-policy self-play rollouts: trajectory store, GAE, minibatch gather (PPO) ---------------------
+ * A rollout of T steps over N = num_envs * num_learners streams, learner-minor - exactly the [B][L] order
+ * gvec_gym_step_players emits.  Handle-free like gvec_pool_collect: every pointer is DEVICE memory on `device`, work is
+ * enqueued on hip_stream, nothing synchronises.  Precondition: every board holds max_players players (the boards
+ * GeneralsSelfPlayVecEnv deals), so that `alive` of a learner means what it says in every env.
+ * Row t describes step t: reset[b] is that step's `resetting` INPUT (the env was re-dealt and the action ignored),
+ * terminated[b] / truncated[b] its outputs, alive[b][l] the learner's Player.Alive after it.  alive_state u8[N] persists
+ * between steps and rollouts: `alive` after the previous step, all ones after a reset of the envs.
+ * gvec_traj_record, one launch per step: row t of action int64[T][N], logp float32[T][N], value float32[T+1][N], reward
+ *   float64[T][N] and flags uint8[T][N] from the step's [N] / [B] arrays, then alive_state := alive.
+ *     GVEC_TRAJ_VALID    = !reset & alive_state                   the row is a transition of a learner still in the game
+ *     GVEC_TRAJ_TERMINAL = VALID & (terminated | !alive)          no bootstrap past this row (elimination ends that learner)
+ *     GVEC_TRAJ_CUT      = VALID & (terminated | truncated | !alive)   the advantage recursion stops here
+ * gvec_traj_gae: generalized advantage estimation, backwards over t = T-1 .. 0 per stream, in float64; next_v = value[t+1]
+ *   and value[T] is the caller's bootstrap:
+ *     valid row    delta = reward + gamma * (TERMINAL ? 0 : next_v) - value[t]
+ *                  adv[t] = delta + gamma * lambda * (CUT ? 0 : adv[t+1]);   ret[t] = adv[t] + value[t]
+ *     invalid row  adv = 0, ret = value[t], and the carried advantage is cleared
+ *   A truncated episode needs no special case: row t+1 of a truncated env is its re-deal row, and value[t+1] was evaluated
+ *   on the final observation the truncating step returned - the bootstrap wanted.  adv / ret float32[T][N], rounded once.
+ *   stats double[4] = {valid rows, sum of adv, sum of adv^2, 0} over the valid rows, of adv AS STORED (float32), by a
+ *   fixed-order two-stage reduction without atomics: the same input gives the same bits.  Two launches.
+ * gvec_traj_compact: idx int64[T*N] takes the ascending positions p = t*N + n of the VALID rows, *count their number
+ *   (entries of idx beyond it are left alone).  Three launches.
+ * gvec_traj_gather: the minibatch of M positions pos[i] in [0, T*N): out_obs[i] = the obs_floats floats of row pos[i] of
+ *   the [T+1][N][obs_floats] observation store, out_mask[i] its mask_bytes bytes of the mask store (mask_bytes == 0: no
+ *   masks, the two pointers unused), action / logp / value / ret copied, out_adv = adv, or with stats != NULL
+ *   (adv - mean) / sqrt(var + 1e-8) in float64 with mean = stats[1] / stats[0], var = max(stats[2] / stats[0] - mean^2, 0)
+ *   (both 0 when stats[0] == 0); out_weight float32 = VALID ? 1 : 0.  A position outside the range gives a zeroed row with
+ *   weight 0 and adds one to *rejected (checked on the device).  Rows need only 4-byte (masks: 1-byte) alignment.  One launch,
+ *   one to eight wavefronts per row.
+ * scratch (gae, compact): gvec_traj_scratch_bytes(T, N) bytes, 16-byte aligned, contents of no interest to the caller.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL,
+ *   T < 1, N < 1 (num_envs < 1, num_learners < 1), t outside [0, T), M < 0, gamma or lambda outside [0, 1] (NaN included),
+ *   obs_floats < 1, mask_bytes < 0.  M == 0 is a no-op that needs no device. */
+#define GVEC_TRAJ_VALID    1
+#define GVEC_TRAJ_TERMINAL 2
+#define GVEC_TRAJ_CUT      4
+typedef struct gvec_traj_record_args {
+  int64_t T, t;
+  int32_t num_envs, num_learners;
+  const int64_t* step_action; const float* step_logp; const float* step_value; const double* step_reward;   /* [N] */
+  const uint8_t* reset; const uint8_t* terminated; const uint8_t* truncated;                                /* [B] */
+  const uint8_t* alive;                                                                                     /* [N] */
+  uint8_t* alive_state;                                                                                     /* [N] in / out */
+  int64_t* action; float* logp; float* value; double* reward; uint8_t* flags;                               /* the stores */
+} gvec_traj_record_args;
+typedef struct gvec_traj_gae_args {
+  int64_t T, N;
+  double gamma, lambda;
+  const double* reward; const float* value; const uint8_t* flags;
+  float* adv; float* ret;
+  double* stats;
+  void* scratch;
+} gvec_traj_gae_args;
+typedef struct gvec_traj_compact_args {
+  int64_t T, N;
+  const uint8_t* flags;
+  int64_t* idx; int64_t* count;
+  void* scratch;
+} gvec_traj_compact_args;
+typedef struct gvec_traj_gather_args {
+  int64_t T, N, M;
+  int32_t obs_floats, mask_bytes;
+  const int64_t* pos;
+  const float* obs; const uint8_t* mask;
+  const int64_t* action; const float* logp; const float* value; const float* ret; const float* adv; const uint8_t* flags;
+  const double* stats;                                                                     /* NULL: adv as stored */
+  float* out_obs; uint8_t* out_mask;
+  int64_t* out_action; float* out_logp; float* out_value; float* out_ret; float* out_adv; float* out_weight;
+  int64_t* rejected;
+} gvec_traj_gather_args;
+uint64_t gvec_traj_scratch_bytes(int64_t T, int64_t N);
+int32_t gvec_traj_record(int32_t device, void* hip_stream, const gvec_traj_record_args* args);
+int32_t gvec_traj_gae(int32_t device, void* hip_stream, const gvec_traj_gae_args* args);
+int32_t gvec_traj_compact(int32_t device, void* hip_stream, const gvec_traj_compact_args* args);
+int32_t gvec_traj_gather(int32_t device, void* hip_stream, const gvec_traj_gather_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
