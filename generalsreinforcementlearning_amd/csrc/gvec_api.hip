@@ -1602,6 +1602,54 @@ int32_t gvec_record_agent_actions(gvec_handle* h, int32_t on) {
   return GVEC_OK;
 }
 
+// the player stats the gym rewards are measured against, [B][3*MAXP]: allocated, zeroed, on first use (the handle's device is current)
+static int32_t ensure_gym_prev(gvec_handle* h) {
+  if (!h->d_gym_prev) {
+    const size_t bytes = (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4;
+    HIPCHK(hipMalloc(&h->d_gym_prev, bytes));
+    HIPCHK(hipMemsetAsync(h->d_gym_prev, 0, bytes, h->stream));
+  }
+  return GVEC_OK;
+}
+
+// what every gym observation call takes from the handle (after ensure_gym_prev)
+static GymArgs gym_args(gvec_handle* h, int32_t player, const int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask, double* reward,
+                        uint8_t* done, int8_t* winner) {
+  GymArgs a;
+  memset(&a, 0, sizeof a);
+  a.hdr = h->d_hdr;
+  a.rows = h->d_rows;
+  a.army16 = h->d_army16;
+  a.army32 = h->d_army32;
+  a.turn_count = turn_count;
+  a.obs = obs;
+  a.mask = mask;
+  a.reward = reward;
+  a.done = done;
+  a.winner = winner;
+  a.prev_stats = h->d_gym_prev;
+  a.num_envs = h->cfg.num_envs;
+  a.fd = h->fd;
+  a.row_dw = h->row_dw;
+  a.stride = h->stride;
+  a.player = player;
+  a.max_turns = max_turns;
+  return a;
+}
+
+// the fused steps end episodes by re-dealing, and their opponents are the on-device agent seeded per call
+static int32_t gym_fused_step_args(gvec_handle* h, uint64_t agent_seed, const char* what, StepArgs* a) {
+  if (!(h->cfg.auto_reset && h->pool_size > 0)) {
+    set_err("%s needs auto_reset and a board pool (gvec_build_board_pool): episodes end by re-dealing", what);
+    return GVEC_E_INVALID;
+  }
+  *a = base_args(h);
+  a->seed_lo = (uint32_t)agent_seed;
+  a->seed_hi = (uint32_t)(agent_seed >> 32);
+  a->invalid_permille = 0;
+  return GVEC_OK;
+}
+
 static int32_t gym_observe_impl(gvec_handle* h, int32_t player, const int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask,
                                 double* reward, uint8_t* done, int8_t* winner, const uint8_t* resetting, const uint8_t* played, int64_t* turn_io,
                                 int64_t* turn_out, uint8_t* terminated, uint8_t* truncated, uint8_t* needs_reset);
@@ -1626,23 +1674,8 @@ static int32_t gym_observe_impl(gvec_handle* h, int32_t player, const int64_t* t
   if (!h || !turn_count || !obs || !mask || player < 0 || player >= h->maxp || max_turns < 1) return GVEC_E_INVALID;
   if (h->sharded()) return sharded::unsupported("gvec_gym_observe / gvec_gym_finish_step");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->d_gym_prev) {
-    HIPCHK(hipMalloc(&h->d_gym_prev, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4));
-    HIPCHK(hipMemsetAsync(h->d_gym_prev, 0, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4, h->stream));
-  }
-  GymArgs a;
-  memset(&a, 0, sizeof a);
-  a.hdr = h->d_hdr;
-  a.rows = h->d_rows;
-  a.army16 = h->d_army16;
-  a.army32 = h->d_army32;
-  a.turn_count = turn_count;
-  a.obs = obs;
-  a.mask = mask;
-  a.reward = reward;
-  a.done = done;
-  a.winner = winner;
-  a.prev_stats = h->d_gym_prev;
+  RET_IF(ensure_gym_prev(h));
+  GymArgs a = gym_args(h, player, turn_count, max_turns, obs, mask, reward, done, winner);
   a.resetting = resetting;
   a.played = played;
   a.turn_io = turn_io;
@@ -1650,12 +1683,6 @@ static int32_t gym_observe_impl(gvec_handle* h, int32_t player, const int64_t* t
   a.terminated = terminated;
   a.truncated = truncated;
   a.needs_reset = needs_reset;
-  a.num_envs = h->cfg.num_envs;
-  a.fd = h->fd;
-  a.row_dw = h->row_dw;
-  a.stride = h->stride;
-  a.player = player;
-  a.max_turns = max_turns;
   HIPCHK(launch_gym_observe(h->var, a, h->stream));
   return GVEC_OK;
 }
@@ -1689,19 +1716,10 @@ int32_t gvec_gym_step(gvec_handle* h, int32_t player, uint64_t agent_seed, const
                       uint8_t* error) {
   if (!h || !gym_actions || !resetting || !turn_count || !obs || !mask || player < 0 || player >= h->maxp || max_turns < 1) return GVEC_E_INVALID;
   if (h->sharded()) return sharded::unsupported("gvec_gym_step");
-  if (!(h->cfg.auto_reset && h->pool_size > 0)) {
-    set_err("gvec_gym_step needs auto_reset and a board pool (gvec_build_board_pool): episodes end by re-dealing");
-    return GVEC_E_INVALID;
-  }
+  StepArgs a;
+  RET_IF(gym_fused_step_args(h, agent_seed, "gvec_gym_step", &a));
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->d_gym_prev) {
-    HIPCHK(hipMalloc(&h->d_gym_prev, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4));
-    HIPCHK(hipMemsetAsync(h->d_gym_prev, 0, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4, h->stream));
-  }
-  StepArgs a = base_args(h);
-  a.seed_lo = (uint32_t)agent_seed;
-  a.seed_hi = (uint32_t)(agent_seed >> 32);
-  a.invalid_permille = 0;
+  RET_IF(ensure_gym_prev(h));
   GymStepArgs g;
   memset(&g, 0, sizeof g);
   g.gym_actions = gym_actions;
@@ -1740,35 +1758,14 @@ static int32_t gym_players_prepare(gvec_handle* h, uint32_t learners, bool ptrs_
   }
   if (h->sharded()) return sharded::unsupported(what);
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->d_gym_prev) {
-    HIPCHK(hipMalloc(&h->d_gym_prev, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4));
-    HIPCHK(hipMemsetAsync(h->d_gym_prev, 0, (size_t)h->cfg.num_envs * 3 * h->var.maxp * 4, h->stream));
-  }
+  RET_IF(ensure_gym_prev(h));
   return GVEC_OK;
 }
 
 int32_t gvec_gym_observe_players(gvec_handle* h, uint32_t learners, const int64_t* turn_count, int32_t max_turns, float* obs, uint8_t* mask,
                                  double* reward, uint8_t* done, int8_t* winner) {
   RET_IF(gym_players_prepare(h, learners, turn_count && obs && mask, max_turns, "gvec_gym_observe_players"));
-  GymArgs a;
-  memset(&a, 0, sizeof a);
-  a.hdr = h->d_hdr;
-  a.rows = h->d_rows;
-  a.army16 = h->d_army16;
-  a.army32 = h->d_army32;
-  a.turn_count = turn_count;
-  a.obs = obs;
-  a.mask = mask;
-  a.reward = reward;
-  a.done = done;
-  a.winner = winner;
-  a.prev_stats = h->d_gym_prev;
-  a.num_envs = h->cfg.num_envs;
-  a.fd = h->fd;
-  a.row_dw = h->row_dw;
-  a.stride = h->stride;
-  a.player = -1;
-  a.max_turns = max_turns;
+  const GymArgs a = gym_args(h, -1, turn_count, max_turns, obs, mask, reward, done, winner);
   HIPCHK(launch_gym_observe_players(h->var, a, learners, h->stream));
   return GVEC_OK;
 }
@@ -1778,14 +1775,8 @@ int32_t gvec_gym_step_players(gvec_handle* h, uint32_t learners, uint64_t agent_
                               uint8_t* truncated, int8_t* winner, uint8_t* needs_reset, int64_t* turn_out, uint8_t* invalid, uint8_t* error,
                               uint8_t* alive) {
   RET_IF(gym_players_prepare(h, learners, gym_actions && resetting && turn_count && obs && mask, max_turns, "gvec_gym_step_players"));
-  if (!(h->cfg.auto_reset && h->pool_size > 0)) {
-    set_err("gvec_gym_step_players needs auto_reset and a board pool (gvec_build_board_pool): episodes end by re-dealing");
-    return GVEC_E_INVALID;
-  }
-  StepArgs a = base_args(h);
-  a.seed_lo = (uint32_t)agent_seed;
-  a.seed_hi = (uint32_t)(agent_seed >> 32);
-  a.invalid_permille = 0;
+  StepArgs a;
+  RET_IF(gym_fused_step_args(h, agent_seed, "gvec_gym_step_players", &a));
   GymPlayersArgs g;
   memset(&g, 0, sizeof g);
   g.gym_actions = gym_actions;
@@ -2005,11 +1996,7 @@ int32_t gvec_copy_envs(gvec_handle* dst, const int32_t* dst_ids, gvec_handle* sr
     return GVEC_E_INVALID;
   }
   HIPCHK(hipSetDevice(dc.device));
-  const size_t prev_bytes = (size_t)dc.num_envs * 3 * dst->var.maxp * 4;
-  if (src->d_gym_prev && !dst->d_gym_prev) {
-    HIPCHK(hipMalloc(&dst->d_gym_prev, prev_bytes));
-    HIPCHK(hipMemsetAsync(dst->d_gym_prev, 0, prev_bytes, dst->stream));
-  }
+  if (src->d_gym_prev) RET_IF(ensure_gym_prev(dst));
   if (src->d_snap && !dst->d_snap) RET_IF(ensure_snapshots(dst));
   int snap_dw = 0, record_dw = 0;
   experience_layout(dst->var, dst->fd, &snap_dw, &record_dw);
