@@ -357,8 +357,23 @@ class GeneralsEnv:
             others[0, 1] = (src.x, src.y, act.to.x, act.to.y, 1 | (2 if getattr(act, "half", False) else 0), (0, 0, 0))   # GVEC_ACT_VALID | _HALF
         return others
 
+    def _will_be_played(self, action):
+        """Whether the learner's own submit goes through (:226-243): the mask accepts the index (:399) and, for a half move,
+        the server accepts the first in-board direction the reference sends (:419-425; a mountain there is refused)."""
+        a, w, h = int(action), self.board_width, self.board_height
+        if not 0 <= a < self.board_size * 5 or not self.valid_actions_mask[a]:
+            return False
+        if a % 5 < 4:
+            return True
+        x, y = (a // 5) % w, (a // 5) // w
+        d = next(d for d, (dx, dy) in enumerate(((0, -1), (1, 0), (0, 1), (-1, 0))) if 0 <= x + dx < w and 0 <= y + dy < h)
+        return bool(self.valid_actions_mask[(a // 5) * 5 + d])
+
     def step(self, action):
-        others = self._opponent_moves() if self.opponent_agent is not None else None
+        others = None
+        if self.opponent_agent is not None:      # the reference asks its opponent only once the learner's submit went through (:244-253)
+            from .vec_engine import ACTION_DTYPE
+            others = self._opponent_moves() if self._will_be_played(action) else np.zeros((1, self.max_players), ACTION_DTYPE)
         obs, reward, terminated, truncated, info = self._vec.step(np.array([int(action)], np.int64), other_actions=others)
         self._obs = obs[0].copy()
         if info["invalid_action"][0]:                                           # :226-231

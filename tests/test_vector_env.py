@@ -4,7 +4,8 @@
   2. its batched numpy form + GeneralsEnv.step's bookkeeping (tests/_gym_reference.py: NumpyReferenceVecEnv), pinned to (1)
      here on CPU with states from the oracle.
 The product (GeneralsVecEnv: the HIP gym kernels, one launch per step) is compared with (2) output for output under -m gpu.
-The reference env itself cannot run here (needs gymnasium and a live Go server): parity unpinned beyond its source text."""
+Both layers and the product are pinned by the reference's own GeneralsEnv class in tests/test_gym_env_fixtures.py (returns
+recorded in the build container); the Go server behind that class stays unpinned."""
 import math
 
 import numpy as np
@@ -168,6 +169,9 @@ class OracleBackedEngine:
     def reset_generated(self, seed):
         army, owner, typ, ws, hs, ps = H.gen_boards(seed, [(self.w, self.h, self.p)] * self.B, self.w, self.h)
         self.ora.reset(army, owner, typ, ws, hs, ps)
+
+    def reset(self, army, owner, type, width, height, players):
+        self.ora.reset(army, owner, type, width, height, players)
 
     def build_board_pool(self, n, seed):
         self.ora.set_pool(n, seed)
