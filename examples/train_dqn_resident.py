@@ -9,7 +9,7 @@ The network, loss and exploration scheme follow the reference's choices in outli
 observation, Huber loss, gradient clipping at 1.0, a hard target update, fixed per-worker exploration rates spread
 geometrically over the workers); the code is this repo's own.  An example, not part of the measured hot path.
 
-    python examples/train_dqn_resident.py --num-envs 4096 --updates 200 [--prioritized]
+    python examples/train_dqn_resident.py --num-envs 4096 --updates 200 [--prioritized] [--n-step 3]
 """
 import argparse
 import json
@@ -57,6 +57,7 @@ def main(argv=None):
     ap.add_argument("--prioritized", action="store_true", help="prioritized replay: weighted loss, priorities from the batch's TD errors")
     ap.add_argument("--per-alpha", type=float, default=0.6)
     ap.add_argument("--per-beta", type=float, default=0.4)
+    ap.add_argument("--n-step", type=int, default=1, help="multi-step targets: returns + discounts * (1 - dones) * max Q(next), from the ring's links")
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
@@ -75,7 +76,10 @@ def main(argv=None):
             explore = (masks * torch.rand(masks.shape, device=dev, generator=gen)).argmax(1)      # a uniform valid action
             return torch.where(torch.rand(B, device=dev, generator=gen) < eps, explore, greedy)
 
-    buf = PrioritizedDeviceReplayBuffer(a.buffer_size, alpha=a.per_alpha, beta=a.per_beta) if a.prioritized else DeviceReplayBuffer(a.buffer_size)
+    if a.prioritized:
+        buf = PrioritizedDeviceReplayBuffer(a.buffer_size, alpha=a.per_alpha, beta=a.per_beta, n_step=a.n_step, gamma=a.gamma)
+    else:
+        buf = DeviceReplayBuffer(a.buffer_size, n_step=a.n_step, gamma=a.gamma)
     pool = ParallelVecEnvPool(B, lambda n: GeneralsVecEnv(n, board_width=a.board, board_height=a.board, max_players=2, max_turns=a.max_steps_per_episode,
                                                          seed=a.seed, device_outputs=True),
                               policy, buf, max_steps_per_episode=a.max_steps_per_episode, seed=a.seed, batched_actions=True)
@@ -83,12 +87,20 @@ def main(argv=None):
     losses, t0 = [], time.perf_counter()
     for u in range(a.updates):
         pool.collect(a.collect_per_update)
-        if a.prioritized:
-            s, act, r, ns, d, slots, weights = buf.sample_prioritized(a.batch_size)
+        if a.n_step > 1:                            # r: the discounted sum of up to n rewards; ns, d: the chain's last row
+            if a.prioritized:
+                s, act, r, ns, d, disc, _steps, slots, weights = buf.sample_nstep_prioritized(a.batch_size)
+            else:
+                s, act, r, ns, d, disc, _steps = buf.sample_nstep(a.batch_size)
+            disc = disc.float()                     # gamma ** steps: a chain cut short by its episode's end bootstraps sooner
         else:
-            s, act, r, ns, d = buf.sample_arrays(a.batch_size)
+            if a.prioritized:
+                s, act, r, ns, d, slots, weights = buf.sample_prioritized(a.batch_size)
+            else:
+                s, act, r, ns, d = buf.sample_arrays(a.batch_size)
+            disc = a.gamma
         with torch.no_grad():
-            tq = r.float() + a.gamma * target(ns).max(1).values * (~d).float()
+            tq = r.float() + disc * target(ns).max(1).values * (~d).float()
         qsa = q(s).gather(1, act[:, None]).squeeze(1)
         if a.prioritized:
             loss = (weights * F.smooth_l1_loss(qsa, tq, reduction="none")).mean()
@@ -108,7 +120,7 @@ def main(argv=None):
     results = pool.pop_episode_results()
     out = {"updates": a.updates, "env_steps": pool.total_env_steps, "episodes": pool.total_episodes, "seconds": dt,
            "env_steps_per_s": a.updates * a.collect_per_update * B / dt, "updates_per_s": a.updates / dt, "loss": losses,
-           "mean_episode_reward": sum(x[0] for x in results) / max(len(results), 1), "ring_fill": len(buf)}
+           "mean_episode_reward": sum(x[0] for x in results) / max(len(results), 1), "ring_fill": len(buf), "n_step": a.n_step}
     pool._env.close()
     print(json.dumps(out))
     return out

@@ -41,6 +41,14 @@ class CollectArgs(C.Structure):
                                              "pool_counters", "scratch")])
 
 
+class NstepGatherArgs(C.Structure):
+    """gvec_nstep_gather_args (include/generals_vec.h): every pointer is device memory."""
+    _fields_ = ([("k", C.c_int64), ("capacity", C.c_int64), ("n_step", C.c_int32), ("obs_floats", C.c_int32), ("gamma", C.c_double)]
+                + [(n, C.c_void_p) for n in ("idx", "ring_state", "ring_next_state", "ring_action", "ring_reward", "ring_done",
+                                             "ring_counters", "ring_succ", "state", "next_state", "action", "ret", "discount", "done",
+                                             "steps", "last_idx")])
+
+
 class TrajRecordArgs(C.Structure):
     """gvec_traj_record_args (include/generals_vec.h): every pointer is device memory."""
     _fields_ = ([("T", C.c_int64), ("t", C.c_int64), ("num_envs", C.c_int32), ("num_learners", C.c_int32)]
@@ -122,6 +130,8 @@ SYMBOLS = {
     "gvec_per_push": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64]),
     "gvec_per_update": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_float, C.c_float]),
     "gvec_per_sample": (_i32, [_i32, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_float, _vp, _u64, _vp, _vp]),
+    "gvec_nstep_link": (_i32, [_i32, _vp, C.POINTER(CollectArgs), _vp, _vp, _vp]),
+    "gvec_nstep_gather": (_i32, [_i32, _vp, C.POINTER(NstepGatherArgs)]),
     "gvec_traj_scratch_bytes": (_u64, [C.c_int64, C.c_int64]),
     "gvec_traj_record": (_i32, [_i32, _vp, C.POINTER(TrajRecordArgs)]),
     "gvec_traj_gae": (_i32, [_i32, _vp, C.POINTER(TrajGaeArgs)]),

@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libgvec_hip.so")
-SRCS = ["gvec_kernels.hip", "gvec_per.hip", "gvec_traj.hip", "gvec_api.hip"]
-DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", os.path.join(ROOT, "include", "generals_vec.h")]
+SRCS = ["gvec_kernels.hip", "gvec_per.hip", "gvec_traj.hip", "gvec_nstep.hip", "gvec_api.hip"]
+DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_collect.hpp", os.path.join(ROOT, "include", "generals_vec.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-save-temps=obj"]  # keeps build/*-gfx950.s: tests/test_kernel_asm.py scans the generated ISA
 

@@ -1505,6 +1505,62 @@ int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t ca
   return GVEC_OK;
 }
 
+// ---- n-step returns over the replay ring (gvec_nstep.hip) ----
+int32_t gvec_nstep_link(int32_t device, void* hip_stream, const gvec_collect_args* a, const int64_t* counters_before, int64_t* ring_succ,
+                        int64_t* nstep_last) {
+  if (!a || !counters_before || !ring_succ || !nstep_last) {
+    set_err("gvec_nstep_link: args, counters_before, ring_succ or nstep_last is NULL");
+    return GVEC_E_INVALID;
+  }
+  if (a->capacity < 1 || a->num_envs < 1 || a->num_envs > a->capacity) {
+    set_err("gvec_nstep_link: capacity %lld < 1, or num_envs %d outside [1, capacity]", (long long)a->capacity, a->num_envs);
+    return GVEC_E_INVALID;
+  }
+  if (!a->ring_counters || !a->scratch) {
+    set_err("gvec_nstep_link: a required pointer of args is NULL (ring_counters, scratch)");
+    return GVEC_E_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(a->scratch) & 15) {
+    set_err("gvec_nstep_link: scratch must be 16-byte aligned");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_nstep_link(*a, reinterpret_cast<const long long*>(counters_before), reinterpret_cast<long long*>(ring_succ),
+                           reinterpret_cast<long long*>(nstep_last), reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_nstep_gather(int32_t device, void* hip_stream, const gvec_nstep_gather_args* a) {
+  if (!a) {
+    set_err("gvec_nstep_gather: args is NULL");
+    return GVEC_E_INVALID;
+  }
+  if (a->capacity < 1 || a->k < 0 || a->k > ((int64_t)1 << 28) || a->n_step < 1 || a->obs_floats < 1) {
+    set_err("gvec_nstep_gather: capacity %lld < 1, k %lld outside [0, 2^28], n_step %d < 1 or obs_floats %d < 1", (long long)a->capacity,
+            (long long)a->k, a->n_step, a->obs_floats);
+    return GVEC_E_INVALID;
+  }
+  if (!(a->gamma >= 0.0) || !(a->gamma <= 1.7976931348623157e308)) {
+    set_err("gvec_nstep_gather: gamma %g must be finite and >= 0", a->gamma);
+    return GVEC_E_INVALID;
+  }
+  if (a->n_step > 1 && !a->ring_succ) {
+    set_err("gvec_nstep_gather: ring_succ is NULL with n_step %d > 1", a->n_step);
+    return GVEC_E_INVALID;
+  }
+  if (a->k == 0) return GVEC_OK;
+  if (!a->idx || !a->ring_state || !a->ring_next_state || !a->ring_action || !a->ring_reward || !a->ring_done || !a->ring_counters ||
+      !a->state || !a->next_state || !a->action || !a->ret || !a->discount || !a->done || !a->steps || !a->last_idx) {
+    set_err("gvec_nstep_gather: a required pointer is NULL (only ring_succ may be, with n_step == 1)");
+    return GVEC_E_INVALID;
+  }
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_nstep_gather(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
 // ---- on-policy rollouts (gvec_traj.hip) ----
 static int32_t traj_shape(const char* fn, int64_t T, int64_t N) {
   if (T < 1 || N < 1 || T > ((int64_t)1 << 40) / N) {

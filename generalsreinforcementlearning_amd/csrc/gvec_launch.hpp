@@ -291,6 +291,10 @@ hipError_t launch_per_update(float* tree, const PerLayout& y, const long long* i
 hipError_t launch_per_sample(float* tree, const PerLayout& y, const long long* ring_counters, long long k, float beta, const double* u,
                              unsigned long long seed, long long* idx, float* weight, hipStream_t s);
 
+// n-step returns over the replay ring (gvec_nstep.hip; generals_vec.h "n-step returns over the replay ring")
+hipError_t launch_nstep_link(const gvec_collect_args& a, const long long* before, long long* ring_succ, long long* nstep_last, hipStream_t s);
+hipError_t launch_nstep_gather(const gvec_nstep_gather_args& a, hipStream_t s);
+
 // on-policy rollouts (gvec_traj.hip; generals_vec.h "on-policy self-play rollouts")
 size_t traj_scratch_bytes(long long T, long long N);
 hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s);

@@ -125,11 +125,22 @@ class DeviceReplayBuffer:
     tensors a learner consumes in place.  288 GB of HBM hold 17 million 15x15 transitions (2 x 8,100 B of observation each).
     Same semantics as replay_buffer.py:13-55 - the oldest transition is overwritten once `capacity` is reached, `sample`
     draws uniformly without replacement and raises ValueError when fewer than batch_size are held, `total_pushed` counts
-    every push - with one difference: the draw comes from a torch generator on the device, not from `random`."""
+    every push - with one difference: the draw comes from a torch generator on the device, not from `random`.
 
-    def __init__(self, capacity, device=0):
+    `n_step` > 1 adds multi-step returns: the ring then keeps `ring_succ`, one int64 link per slot to the
+    same worker's next transition of the same episode (written on the device by gvec_nstep_link right after the pool's
+    gvec_pool_collect; -1 where the episode ended, was cut, or the row came from `push_batch`), and `sample_nstep` /
+    `gather_nstep` return `(states, actions, returns, next_states, dones, discounts, steps)` from ONE fused gather
+    (gvec_nstep_gather): `returns` the discounted sum of up to n_step rewards, `next_states` / `dones` those of the last row
+    of the chain, `discounts = gamma ** steps` - a learner's target is `returns + discounts * (1 - dones) * max Q(next)`.
+    They work on an n_step == 1 buffer too (returns == rewards, discounts == gamma), which allocates nothing more.
+    `sample_arrays` / `sample` stay one-step whatever n_step is: a learner written for them bootstraps with gamma."""
+
+    def __init__(self, capacity, device=0, n_step=1, gamma=0.99):
         if capacity <= 0:
             raise ValueError(f"capacity must be positive, got {capacity}")
+        if int(n_step) != n_step or n_step < 1 or not 0.0 <= float(gamma) < float("inf"):
+            raise ValueError(f"n_step {n_step} must be an integer >= 1 and gamma {gamma} finite and >= 0")
         import torch
         self._t = torch
         self.capacity = int(capacity)
@@ -139,9 +150,16 @@ class DeviceReplayBuffer:
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(0)
         self._guard = threading.Lock()
+        self.n_step, self.gamma = int(n_step), float(gamma)
+        self.ring_succ = None                     # int64 [capacity] once allocated, and only when n_step > 1
+        # the counters ahead of a collector's step (gvec_nstep_link, gvec_per_push): one 32-byte copy serves both
+        self._before = torch.zeros(4, dtype=torch.int64, device=self.device) if self.n_step > 1 else None
 
     def allocate(self, obs_shape):
-        """The five slabs of the ring (at the first push; a collector calls it with the env's observation shape)."""
+        """The five slabs of the ring (at the first push; a collector calls it with the env's observation shape), and the
+        successor links of an n_step > 1 buffer."""
+        if self.n_step > 1 and self.ring_succ is None:
+            self.ring_succ = self._t.full((self.capacity,), -1, dtype=self._t.int64, device=self.device)
         if self.state is None:
             t, dev, cap = self._t, self.device, self.capacity
             self.obs_shape = tuple(obs_shape)
@@ -174,6 +192,8 @@ class DeviceReplayBuffer:
             self.action[idx] = actions[lo:]
             self.reward[idx] = t.as_tensor(rewards, dtype=t.float64, device=dev).reshape(-1)[lo:]
             self.done[idx] = t.as_tensor(dones, dtype=t.bool, device=dev).reshape(-1)[lo:]
+            if self.ring_succ is not None:
+                self.ring_succ[idx] = -1                                      # no worker, no episode: such a row is a chain of one
             self.counters[:3] = t.tensor([(cursor + k) % self.capacity, min(size + k, self.capacity), pushed + k], dtype=t.int64)
 
     def push(self, state, action, reward, next_state, done):
@@ -198,6 +218,50 @@ class DeviceReplayBuffer:
         s, a, r, n, d = (x.cpu().numpy() for x in self.sample_arrays(batch_size))
         return [(s[i], int(a[i]), float(r[i]), n[i], bool(d[i])) for i in range(len(a))]
 
+    def mark_before_push(self):
+        """The counters' "before" copy of gvec_nstep_link and gvec_per_push (32 bytes, device to device); the caller holds
+        `_guard`."""
+        self._before.copy_(self.counters)
+
+    def _gather_nstep(self, idx):
+        """One launch of gvec_nstep_gather over `idx`; the caller holds `_guard`."""
+        import ctypes
+        from ._lib import NstepGatherArgs, check, load
+        t, dev = self._t, self.device
+        if self.state is None:
+            raise ValueError("the replay buffer is empty")
+        idx = t.as_tensor(idx, device=dev).to(t.int64).reshape(-1).contiguous()
+        k = int(idx.numel())
+        a = NstepGatherArgs()
+        a.k, a.capacity, a.n_step, a.obs_floats, a.gamma = k, self.capacity, self.n_step, int(np.prod(self.obs_shape)), self.gamma
+        out = dict(state=t.empty((k,) + self.obs_shape, dtype=t.float32, device=dev), next_state=t.empty((k,) + self.obs_shape, dtype=t.float32, device=dev),
+                   action=t.empty(k, dtype=t.int64, device=dev), ret=t.empty(k, dtype=t.float64, device=dev),
+                   discount=t.empty(k, dtype=t.float64, device=dev), done=t.empty(k, dtype=t.bool, device=dev),
+                   steps=t.empty(k, dtype=t.int32, device=dev), last_idx=t.empty(k, dtype=t.int64, device=dev))
+        for name, tensor in (("idx", idx), ("ring_state", self.state), ("ring_next_state", self.next_state), ("ring_action", self.action),
+                             ("ring_reward", self.reward), ("ring_done", self.done), ("ring_counters", self.counters)) + tuple(out.items()):
+            setattr(a, name, tensor.data_ptr())
+        a.ring_succ = None if self.ring_succ is None else self.ring_succ.data_ptr()
+        check(load().gvec_nstep_gather(dev.index, t.cuda.current_stream(dev).cuda_stream, ctypes.byref(a)), "gvec_nstep_gather")
+        return out
+
+    @staticmethod
+    def _seven(o):
+        return o["state"], o["action"], o["ret"], o["next_state"], o["done"], o["discount"], o["steps"]
+
+    def gather_nstep(self, idx):
+        """(states, actions, returns, next_states, dones, discounts, steps) for the slots `idx`: per slot the chain of up to
+        n_step transitions of one worker's episode that starts there.  A slot outside [0, len) gives steps 0, returns 0,
+        discounts 0, action -1 and zero rows."""
+        with self._guard:
+            return self._seven(self._gather_nstep(idx))
+
+    def sample_nstep(self, batch_size):
+        """The buffer's own draw (`sample_indices`) and its n-step gather, enqueued under the lock a collector's launches take
+        too, like `sample_arrays`: no vector step lands between the draw and the walk."""
+        with self._guard:
+            return self._seven(self._gather_nstep(self.sample_indices(batch_size)))
+
     @property
     def total_pushed(self):
         return int(self.counters[2])
@@ -217,8 +281,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     indices of an earlier draw: a slot the collector has overwritten in between simply takes the stale priority, as in
     standard prioritized replay (there is no generation check).  Nothing here synchronises except `len()`."""
 
-    def __init__(self, capacity, device=0, alpha=0.6, beta=0.4, eps=1e-6):
-        super().__init__(capacity, device)
+    def __init__(self, capacity, device=0, alpha=0.6, beta=0.4, eps=1e-6, n_step=1, gamma=0.99):
+        super().__init__(capacity, device, n_step=n_step, gamma=gamma)
         if alpha < 0 or beta < 0 or not eps > 0:
             raise ValueError(f"alpha {alpha} and beta {beta} must be >= 0 and eps {eps} > 0")
         import ctypes
@@ -230,7 +294,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         self.tree_levels, self._tree_words = int(layout[0]), int(layout[1])
         self.tree_offsets = [int(layout[2 + l]) for l in range(self.tree_levels + 1)]     # in floats; level 0 = the leaves
         self.tree = None
-        self._before = self._t.zeros(4, dtype=self._t.int64, device=self.device)           # the counters ahead of a push
+        if self._before is None:
+            self._before = self._t.zeros(4, dtype=self._t.int64, device=self.device)       # the counters ahead of a push
         self._guard = threading.RLock()          # push_batch holds it round the parent's push (which takes it too) and the tree's
         self._seed = 0
 
@@ -257,10 +322,6 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
             if self.tree is not None:
                 self._header()[PER_HDR_DRAWS:PER_HDR_DRAWS + 2].zero_()
-
-    def mark_before_push(self):
-        """The counters' "before" copy of gvec_per_push (32 bytes, device to device); the caller holds `_guard`."""
-        self._before.copy_(self.counters)
 
     def push_priorities(self, max_count):
         """The rows appended since `mark_before_push` get the maximum priority; the caller holds `_guard`."""
@@ -320,6 +381,14 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             idx, w = self._draw(batch_size, beta, u)
             return self.state[idx], self.action[idx], self.reward[idx], self.next_state[idx], self.done[idx], idx, w
 
+    def sample_nstep_prioritized(self, batch_size, beta=None, u=None):
+        """`sample_prioritized`'s draw with the n-step gather: (states, actions, returns, next_states, dones, discounts, steps,
+        indices, weights).  `indices` are the chains' first slots - the ones `update_priorities` takes."""
+        batch_size = self._checked(batch_size)
+        with self._guard:
+            idx, w = self._draw(batch_size, beta, u)
+            return self._seven(self._gather_nstep(idx)) + (idx, w)
+
     def _checked(self, batch_size):
         batch_size = int(batch_size)
         held = len(self)
@@ -378,10 +447,14 @@ class _DeviceCollector:
             setattr(a, name, tensor.data_ptr())
         self._device_index = dev.index
         self._prioritized = isinstance(buffer, PrioritizedDeviceReplayBuffer)
+        # n-step buffers: {sequence number, slot} of every worker's latest row while its episode is open (gvec_nstep_link)
+        self.nstep_last = torch.full((n, 2), -1, dtype=torch.int64, device=dev) if buffer.n_step > 1 else None
 
     def restart(self):
         self.episode_reward.zero_()
         self.episode_length.zero_()
+        if self.nstep_last is not None:
+            self.nstep_last.fill_(-1)             # a reopened env starts new episodes: nothing links across the gap
 
     def collect(self, state, actions, next_state, reward, terminated, truncated, was_reset, needs_reset):
         a = self.args
@@ -389,9 +462,12 @@ class _DeviceCollector:
         a.terminated, a.truncated, a.was_reset, a.needs_reset = terminated.data_ptr(), truncated.data_ptr(), was_reset.data_ptr(), needs_reset.data_ptr()
         stream = self._t.cuda.current_stream(self.env._dev).cuda_stream
         with self.buffer._guard:                  # ordered against a learner's sample_arrays / push_batch on the same stream
-            if self._prioritized:                 # the counters ahead of the step: the tree learns on the device how many rows came
-                self.buffer.mark_before_push()
+            if self._prioritized or self.nstep_last is not None:   # the counters ahead of the step: the tree and the links learn
+                self.buffer.mark_before_push()                     # on the device how many rows came, and where
             self._check(self.L.gvec_pool_collect(self._device_index, stream, self._C.byref(a)), "gvec_pool_collect")
+            if self.nstep_last is not None:
+                self._check(self.L.gvec_nstep_link(self._device_index, stream, self._C.byref(a), self.buffer._before.data_ptr(),
+                                                   self.buffer.ring_succ.data_ptr(), self.nstep_last.data_ptr()), "gvec_nstep_link")
             if self._prioritized:
                 self.buffer.push_priorities(a.num_envs)
 

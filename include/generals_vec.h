@@ -564,6 +564,61 @@ int32_t gvec_per_update(int32_t device, void* hip_stream, void* tree, int64_t ca
 int32_t gvec_per_sample(int32_t device, void* hip_stream, void* tree, int64_t capacity, const int64_t* ring_counters, int64_t k,
                         float beta, const double* u, uint64_t seed, int64_t* idx, float* weight);
 
+/* ---- n-step returns over the replay ring ("Multi-step Learning", n_step = 3, of the reference's
+ * documentation/claude/training-next-steps.md section 3.1, which it never built) -----------------------
+ * gvec_pool_collect appends only the live workers' rows, compacted from the cursor, so the distance in the ring between a
+ * worker's step t and its step t + 1 changes every step, and a cut at max_steps_per_episode leaves done = 0 in the ring.  Two
+ * arrays record what the ring does not.  ring_succ: int64 [capacity]; ring_succ[s] is the slot that holds the same worker's
+ * next transition of the same episode, or -1: that transition does not exist yet, the episode ended with row s (terminated |
+ * truncated, or cut at the limit - the collector's `over`), or the row was not written by the collector.  nstep_last: int64
+ * [num_envs][2], {global sequence number, slot} of each worker's latest row while its episode is open, {-1, -1} otherwise;
+ * a row's global sequence number is the ring's "total pushed" counter at the moment it was appended.  Fill both with -1 to
+ * start; a caller that writes rows by itself sets ring_succ = -1 for them.  Handle-free like gvec_pool_collect: every pointer
+ * is DEVICE memory on `device`, work is enqueued on hip_stream, nothing synchronises, the host never learns the row count.
+ * gvec_nstep_link: call it right after gvec_pool_collect, on the same stream, with the SAME args.  Ordering contract: it
+ *   reads only num_envs, capacity, ring_counters and scratch of args, and what that call left in args->scratch (every worker's live / over flags and the per-group prefix counts of the live
+ *   ones), so it must run after that gvec_pool_collect and before the next call that uses the same scratch, and nothing else
+ *   may append to the ring between the two.  counters_before: a copy of ring_counters taken ahead of gvec_pool_collect - the
+ *   32-byte device-to-device copy gvec_per_push wants, so one copy serves both; args->ring_counters holds the counters after.
+ *   For every live worker w (its step was not its reset: the live flag of the scratch), whose new row has sequence q = before.pushed + (live workers below w)
+ *   and slot s = (before.cursor + that count) mod capacity: if nstep_last[w] is open and its row is still held -
+ *   prev_seq >= after.pushed - capacity, decided by this arithmetic alone, never by reading the slot, which this very step's
+ *   push may have rewritten - then ring_succ[prev_slot] = s; ring_succ[s] = -1; nstep_last[w] = over ? {-1, -1} : {q, s}.
+ *   A worker whose step was its reset writes nothing.  A predecessor that is still held is never one of this step's slots,
+ *   so no two workers write one word.  One launch, one thread per worker.
+ * gvec_nstep_gather: the whole batch for k sampled slots idx[k] (from any draw; gvec_per_sample's included) in one launch.
+ *   Per sample, every float64 operation in exactly this order (no fused multiply-add: a float64 loop on the host
+ *   reproduces ret and discount bit for bit):
+ *     cur = idx; ret = reward[cur]; disc = 1.0; steps = 1
+ *     while steps < n_step and !done[cur] and succ[cur] >= 0:
+ *       cur = succ[cur]; disc = disc * gamma; ret = ret + disc * reward[cur]; steps += 1
+ *     discount = disc * gamma
+ *   Outputs: state[k] = ring_state[idx], next_state[k] = ring_next_state[cur], action[k] = ring_action[idx], ret[k],
+ *   discount[k] (= gamma ** steps by the repeated product), done[k] = ring_done[cur], steps[k], last_idx[k] = cur.  A
+ *   learner's target is ret + discount * (1 - done) * max Q(next_state).  An index outside [0, size) - the -1 of an empty
+ *   prioritized tree included - gives steps 0, ret 0, discount 0, done 0, action -1, last_idx -1 and zero-filled rows.  A link
+ *   that points outside [0, capacity) ends the walk like -1.  ring_succ may be NULL only when n_step == 1 (then ret = reward,
+ *   discount = gamma).  1 << s wavefronts per sample, s the smallest of 0..3 with k << s >= 16384 (else 3) - the rule of
+ *   gvec_pool_collect's copy, from the row count alone; the walk costs at most n_step - 1 dependent loads per wavefront,
+ *   the two rows - which come from two different slots - move with 16-byte loads and stores aligned on both sides.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL,
+ *   capacity < 1, k < 0 or > 2^28, n_step < 1, obs_floats < 1, gamma not finite or negative, ring_succ NULL with n_step > 1; for the
+ *   link call also num_envs < 1 or num_envs > capacity, and a scratch that is not 16-byte aligned.  k == 0 is a no-op that
+ *   needs no device. */
+typedef struct gvec_nstep_gather_args {
+  int64_t k, capacity;
+  int32_t n_step, obs_floats;
+  double gamma;
+  const int64_t* idx;
+  const float* ring_state; const float* ring_next_state; const int64_t* ring_action; const double* ring_reward;
+  const uint8_t* ring_done; const int64_t* ring_counters; const int64_t* ring_succ;
+  float* state; float* next_state; int64_t* action; double* ret; double* discount; uint8_t* done; int32_t* steps;
+  int64_t* last_idx;
+} gvec_nstep_gather_args;
+int32_t gvec_nstep_link(int32_t device, void* hip_stream, const gvec_collect_args* args, const int64_t* counters_before,
+                        int64_t* ring_succ, int64_t* nstep_last);
+int32_t gvec_nstep_gather(int32_t device, void* hip_stream, const gvec_nstep_gather_args* args);
+
 /* ---- on-policy self-play rollouts: trajectory store, GAE, minibatch gather (PPO) ---------------------
  * A rollout of T steps over N = num_envs * num_learners streams, learner-minor - exactly the [B][L] order
  * gvec_gym_step_players emits.  Handle-free like gvec_pool_collect: every pointer is DEVICE memory on `device`, work is
