@@ -15,8 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libgvec_hip.so")
-SRCS = ["gvec_kernels.hip", "gvec_per.hip", "gvec_traj.hip", "gvec_nstep.hip", "gvec_api.hip"]
-DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_collect.hpp", os.path.join(ROOT, "include", "generals_vec.h")]
+# one subsystem, one unit (DESIGN.md "Translation units"); tests/test_kernel_asm.py checks that every csrc/*.hip and *.hpp is listed here
+SRCS = ["gvec_kernels.hip", "gvec_gym.hip", "gvec_experience.hip", "gvec_state.hip", "gvec_stream.hip", "gvec_mapgen.hip",
+        "gvec_per.hip", "gvec_traj.hip", "gvec_nstep.hip", "gvec_api.hip"]
+DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_dispatch.hpp", "gvec_turn.hpp", "gvec_gym_emit.hpp", "gvec_collect.hpp",
+        "go_rand_cooked.inc", os.path.join(ROOT, "include", "generals_vec.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-save-temps=obj"]  # keeps build/*-gfx950.s: tests/test_kernel_asm.py scans the generated ISA
 
@@ -42,7 +45,7 @@ def build(force=False, verbose=True):
     if jobs:
         if verbose:
             print(f"[gvec build] compiling {len(jobs)} HIP translation unit(s) for gfx950 ...", flush=True)
-        with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), 16)) as ex:
             for r in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), jobs):
                 if r.returncode != 0:
                     sys.stderr.write(r.stdout + r.stderr)

@@ -1,4 +1,4 @@
-// gvec_collect.hpp — what the kernels that fill the replay ring (gvec_pool_collect, gvec_kernels.hip) and the kernels that
+// gvec_collect.hpp — what the kernels that fill the replay ring (gvec_pool_collect, gvec_stream.hip) and the kernels that
 // read it back (gvec_nstep_*, gvec_nstep.hip) share: the layout of the collect scratch and the row copy.
 #pragma once
 #include "gvec_device.hpp"

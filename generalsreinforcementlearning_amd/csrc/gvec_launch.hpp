@@ -1,4 +1,4 @@
-// gvec_launch.hpp — host-visible launchers of the HIP kernels in gvec_kernels.hip.
+// gvec_launch.hpp — host-visible launchers of the HIP kernels, one unit per subsystem (DESIGN.md "Translation units").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -148,7 +148,7 @@ struct ExperienceArgs {
   const uint32_t* rows;
   const uint32_t* army16;
   const int32_t* army32;
-  uint32_t* snap;     // [B][snap_dw]: see SnapLayout (gvec_kernels.hip); indexed by env
+  uint32_t* snap;     // [B][snap_dw]: see SnapLayout (gvec_experience.hip); indexed by env
   float* rewards;     // [n][pstride]
   uint8_t* done;      // [n] or null
   float* obs;         // observe: [B][9*stride] (one player) or [B][pstride][9*stride] (player = -1)

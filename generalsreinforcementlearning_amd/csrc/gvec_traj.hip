@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void traj_compact_write_kernel(gvec_traj_compa
 
 // ---- gather: the row mover ----
 // A row of n floats from s to d, both only dword-aligned (a row is 9 * W * H floats: 8,100 bytes at 15x15) and not alike: the
-// scheme of gvec_pool_collect's copy_row (gvec_kernels.hip), restated here so that no existing kernel's code changes.
+// scheme of gvec_pool_collect's copy_row (gvec_collect.hpp), restated here so that no existing kernel's code changes.
 // Sixteen bytes per lane with BOTH sides on 16-byte boundaries: destination quad j (floats [kd + 4j, kd + 4j + 4) of the row)
 // is cut out of the aligned source quads j and j + 1 counted from s + kd - a, a = the floats by which the two sides differ.
 // Only quads that lie inside the row are read; the floats before / after that body go one by one (part 0).

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Compares two builds' gfx950 ISA listings kernel symbol by kernel symbol: did a source change alter the generated code?
 
-usage: scripts/isa_diff.py OLD.s NEW.s [--quiet]      (csrc/build/gvec_kernels-hip-amdgcn-amd-amdhsa-gfx950.s of each build)
+usage: scripts/isa_diff.py OLD NEW [--quiet]
+OLD and NEW each name one build: a listing, several joined by commas, or a directory of them (csrc/build: every *-gfx950.s).
+The kernels of a build are those of all its listings; a symbol that two listings of one build define is an error.
 
 A kernel's instructions are normalised the way bench.py's step_kernel_isa_hash does it (directives, comments and labels
 dropped, the function's index stripped from .LBB labels), so a kernel that merely moved inside the file reports `same`.
 Every kernel prints `same` or `differs` (with --quiet: only the differing ones); a differing one also prints the old and new
 resource fields.  Last lines: the counts per kernel template.  Exit status 1 when a symbol exists in one listing only."""
 import collections
+import glob
 import hashlib
+import os
 import re
 import sys
 
@@ -42,6 +46,19 @@ def kernels(path):
     return out
 
 
+def build_kernels(spec):
+    """kernels() of every listing of one build"""
+    out = {}
+    for item in spec.split(","):
+        for path in sorted(glob.glob(os.path.join(item, "*-gfx950.s"))) if os.path.isdir(item) else [item]:
+            found = kernels(path)
+            twice = sorted(set(found) & set(out))
+            if twice:
+                sys.exit(f"{path}: {len(twice)} kernel symbol(s) already defined by another listing of {spec}, e.g. {twice[0]}")
+            out.update(found)
+    return out
+
+
 def template_of(sym):
     m = re.match(r"_ZN(\d+)", sym)   # _ZN4gvec15gym_step_kernelILi2E... -> gym_step_kernel
     n = m and re.match(r"\d+", sym[m.end() + int(m.group(1)):])
@@ -55,7 +72,7 @@ def main():
     args = [a for a in sys.argv[1:] if a != "--quiet"]
     if len(args) != 2:
         sys.exit(__doc__)
-    old, new = kernels(args[0]), kernels(args[1])
+    old, new = build_kernels(args[0]), build_kernels(args[1])
     quiet, tally = "--quiet" in sys.argv, collections.defaultdict(lambda: [0, 0])
     for sym in sorted(set(old) | set(new)):
         if sym not in old or sym not in new:

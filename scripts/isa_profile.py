@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Static instruction mix of one kernel, bucketed by the source function each instruction was inlined from."""
-import re, subprocess, sys, collections, os
+"""Static instruction mix of one kernel, bucketed by the source function each instruction was inlined from.
+usage: scripts/isa_profile.py [kernel symbol] [unit that defines it, default gvec_kernels]   (compiles that unit with line tables)"""
+import re, subprocess, sys, collections, os, tempfile
 kern = sys.argv[1] if len(sys.argv) > 1 else "_ZN4gvec11step_kernelILi4ELi7ELb1ELb1EEEvNS_8StepArgsE"
-src = "/root/repo/generalsreinforcementlearning_amd/csrc/gvec_kernels.hip"
-os.makedirs("/tmp/st2", exist_ok=True)
-subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-gline-tables-only", "-c", src, "-o", "/tmp/st2/k.o", "-save-temps"], cwd="/tmp/st2", check=True, capture_output=True)
-asm = open("/tmp/st2/gvec_kernels-hip-amdgcn-amd-amdhsa-gfx950.s").read().split("\n")
+unit = sys.argv[2] if len(sys.argv) > 2 else "gvec_kernels"
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "generalsreinforcementlearning_amd", "csrc")
+tmp = tempfile.mkdtemp(prefix="gvec_isa_profile_")
+subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-gline-tables-only", "-c", os.path.join(CSRC, unit + ".hip"),
+                "-o", os.path.join(tmp, "k.o"), "-save-temps"], cwd=tmp, check=True, capture_output=True)
+asm = open(os.path.join(tmp, unit + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
 # file table
 files = {}
 for l in asm:
@@ -20,7 +23,7 @@ def func_ranges(path):
     return out
 ranges = {}
 for fid, f in files.items():
-    p = f if os.path.isabs(f) else os.path.join("/root/repo/generalsreinforcementlearning_amd/csrc", f)
+    p = f if os.path.isabs(f) else os.path.join(CSRC, f)
     if os.path.exists(p) and ("gvec" in p): ranges[fid] = func_ranges(p)
 def which(fid, line):
     r = ranges.get(fid)

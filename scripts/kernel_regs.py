@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""Register / scratch / LDS use of every kernel variant matching a pattern (compiles gvec_kernels.hip with -save-temps).
+"""Register / scratch / LDS use of every kernel variant matching a pattern, read from the gfx950 listings csrc/build.py keeps
+for every unit (csrc/build/*-gfx950.s; run the build first).
 usage: scripts/kernel_regs.py [substring, default Li4ELi7]"""
-import os, re, subprocess, sys
+import glob, os, re, sys
 pat = sys.argv[1] if len(sys.argv) > 1 else "Li4ELi7"
-src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "generalsreinforcementlearning_amd", "csrc", "gvec_kernels.hip")
-os.makedirs("/tmp/gvec_regs", exist_ok=True)
-subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-c", src, "-o", "k.o", "-save-temps"],
-               cwd="/tmp/gvec_regs", check=True, capture_output=True)
-s = open("/tmp/gvec_regs/gvec_kernels-hip-amdgcn-amd-amdhsa-gfx950.s").read()
-for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S):
-    if pat not in m.group(1):
-        continue
-    g = lambda k: re.search(r"\.amdhsa_" + k + r"\s+(\S+)", m.group(2)).group(1)
-    print(f"{m.group(1)[:64]:64s} vgpr {g('next_free_vgpr'):>4s} sgpr {g('next_free_sgpr'):>4s} scratch {g('private_segment_fixed_size'):>5s} lds {g('group_segment_fixed_size'):>5s}")
+build = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "generalsreinforcementlearning_amd", "csrc", "build")
+listings = sorted(glob.glob(os.path.join(build, "*-gfx950.s")))
+if not listings:
+    sys.exit(f"no listings in {build}: run generalsreinforcementlearning_amd/csrc/build.py first")
+for path in listings:
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", open(path).read(), re.S):
+        if pat not in m.group(1):
+            continue
+        g = lambda k: re.search(r"\.amdhsa_" + k + r"\s+(\S+)", m.group(2)).group(1)
+        print(f"{m.group(1)[:64]:64s} vgpr {g('next_free_vgpr'):>4s} sgpr {g('next_free_sgpr'):>4s} scratch {g('private_segment_fixed_size'):>5s} lds {g('group_segment_fixed_size'):>5s}")

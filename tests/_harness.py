@@ -60,7 +60,7 @@ def run_lockstep(eng, ora, turns, seed, invalid_permille=0, check_every=1, want_
 
 
 # Every compiled instantiation of the kernels: <max players 2 / 4 / 8> x <1, 2, 4, 7, 10, 16 slots of 64 tiles> x <odd / even
-# number of plane dwords> (gvec_kernels.hip dispatch, launch_step).  The board limits below select each <slots, parity>.
+# number of plane dwords> (gvec_dispatch.hpp dispatch, gvec_kernels.hip launch_step).  The board limits below select each <slots, parity>.
 VARIANT_DIMS = {(1, "odd"): (5, 5), (1, "even"): (8, 8), (2, "odd"): (9, 10), (2, "even"): (11, 11), (4, "odd"): (14, 15),
                 (4, "even"): (16, 16), (7, "odd"): (20, 20), (7, "even"): (21, 21), (10, "odd"): (24, 25), (10, "even"): (25, 25),
                 (16, "odd"): (30, 32), (16, "even"): (32, 32)}

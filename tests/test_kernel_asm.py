@@ -10,8 +10,15 @@ import re
 
 import pytest
 
+from generalsreinforcementlearning_amd.csrc import build as B
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "generalsreinforcementlearning_amd", "csrc", "build")
+CSRC = os.path.join(ROOT, "generalsreinforcementlearning_amd", "csrc")
+BUILD = os.path.join(CSRC, "build")
+UNITS = [s[:-len(".hip")] for s in B.SRCS]
+# the staged 16-byte stores of the whole library, counted on the listing of the build that still had one kernel unit: a scan
+# that finds fewer has lost a file
+WIDE_STORE_SITES = 1962
 
 
 def _instructions(path):
@@ -24,17 +31,19 @@ def _instructions(path):
     return out
 
 
-@pytest.mark.parametrize("unit", ["gvec_kernels", "gvec_api"])
-def test_wide_asm_stores_keep_their_wait_states(unit):
+def _wide_store_sites(unit):
+    """(instructions, indices of the 16-byte streaming stores) of one unit's listing"""
     path = os.path.join(BUILD, f"{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
     if not os.path.exists(path):
-        import sys
-        sys.path.insert(0, ROOT)
-        from generalsreinforcementlearning_amd.csrc import build as B
         B.build(force=True, verbose=False)
     ins = _instructions(path)
-    sites = [i for i, s in enumerate(ins) if re.match(r"global_store_dwordx[34]\b.*\bsc1\b", s)]
-    if unit == "gvec_kernels":
+    return ins, [i for i, s in enumerate(ins) if re.match(r"global_store_dwordx[34]\b.*\bsc1\b", s)]
+
+
+@pytest.mark.parametrize("unit", UNITS)
+def test_wide_asm_stores_keep_their_wait_states(unit):
+    ins, sites = _wide_store_sites(unit)
+    if unit in ("gvec_kernels", "gvec_gym"):
         assert len(sites) > 100, "the step path's staged 16-byte stores were not found: has st_through changed its spelling?"
     for i in sites:
         nxt = ins[i + 1]
@@ -50,6 +59,17 @@ def test_wide_asm_stores_keep_their_wait_states(unit):
                 a = int(dst.group(1) or dst.group(3))
                 b = int(dst.group(2) or dst.group(3))
                 assert b < lo or a > hi, f"{unit}: `{ins[i]}` is followed within 2 wait states by `{ins[i + k]}`"
+
+
+def test_wide_store_scan_covers_every_unit():
+    assert sum(len(_wide_store_sites(unit)[1]) for unit in UNITS) >= WIDE_STORE_SITES
+
+
+def test_every_source_is_built_and_watched():
+    """A unit left out of SRCS is missing from the library, a header left out of DEPS from the rebuild check."""
+    names = sorted(os.listdir(CSRC))
+    assert sorted(n for n in names if n.endswith(".hip")) == sorted(B.SRCS)
+    assert {n for n in names if n.endswith(".hpp")} <= set(B.DEPS)
 
 
 def test_no_cross_lane_read_behind_a_short_circuit():
