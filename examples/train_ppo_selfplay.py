@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""A PPO learner over on-device self-play - every player of every board is a learner of one shared network, and env,
+rollout store, action head and learner all stay on one MI355X:
+
+    GeneralsSelfPlayVecEnv(device_outputs=True)  ->  network  ->  MaskedCategoricalHead.sample (gvec_policy_sample)
+        ->  SelfPlayRolloutBuffer.step (gvec_gym_step_players into slot t + 1, gvec_traj_record)  ->  finish (gvec_traj_gae)
+        ->  minibatches (gvec_traj_gather)  ->  MaskedCategoricalHead.evaluate (gvec_policy_evaluate / _backward)
+
+The loss is the clipped PPO surrogate with a value loss and an entropy bonus, every term weighted by batch["weight"] (0 for
+re-deal rows and eliminated learners).  The reference plans this phase (documentation/MASTER_PLAN.md:158-172) and has no
+learner for it; the code is this repo's own.  An example, not part of the measured hot path.
+
+    python examples/train_ppo_selfplay.py --num-envs 1024 --iterations 50
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn as nn
+
+from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead
+from generalsreinforcementlearning_amd.rollout import SelfPlayRolloutBuffer
+from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
+
+
+class ActorCritic(nn.Module):
+    def __init__(self, obs_shape, n_actions, width=64):
+        super().__init__()
+        c, h, w = obs_shape
+        self.torso = nn.Sequential(nn.Conv2d(c, width, 3, padding=1), nn.ReLU(), nn.Conv2d(width, width, 3, padding=1), nn.ReLU())
+        self.policy = nn.Conv2d(width, 5, 1)
+        self.value = nn.Sequential(nn.Conv2d(width, 4, 1), nn.ReLU(), nn.Flatten(), nn.Linear(4 * h * w, 1))
+        self.n_actions = n_actions
+
+    def forward(self, x):
+        # five action planes (up, right, down, left, half) per tile -> the env's index tile * 5 + d
+        z = self.torso(x)
+        return self.policy(z).permute(0, 2, 3, 1).reshape(x.shape[0], self.n_actions), self.value(z).squeeze(1)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num-envs", type=int, default=1024)
+    ap.add_argument("--board", type=int, default=15)
+    ap.add_argument("--players", type=int, default=2)
+    ap.add_argument("--horizon", type=int, default=64)
+    ap.add_argument("--iterations", type=int, default=50)
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--batch-size", type=int, default=4096)
+    ap.add_argument("--max-turns", type=int, default=500)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--gae-lambda", type=float, default=0.95)
+    ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--value-coef", type=float, default=0.5)
+    ap.add_argument("--entropy-coef", type=float, default=0.01)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--seed", type=int, default=42)
+    a = ap.parse_args(argv)
+
+    torch.manual_seed(a.seed)
+    dev = torch.device("cuda", 0)
+    obs_shape, n_actions = (9, a.board, a.board), a.board * a.board * 5
+    net = ActorCritic(obs_shape, n_actions).to(dev)
+    opt = torch.optim.Adam(net.parameters(), lr=a.lr)
+    start = [p.detach().clone() for p in net.parameters()]
+    env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
+                                 seed=a.seed, device_outputs=True)
+    buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda)
+    head = MaskedCategoricalHead(dev)
+    B, L = env.num_envs, env.num_learners
+    buf.begin(*env.reset())
+    out, draws, t0 = [], 0, time.perf_counter()
+    for it in range(a.iterations):
+        with torch.no_grad():
+            while not buf.full:
+                logits, value = net(buf.obs.view(B * L, *obs_shape))
+                draws += 1                          # one seed per step: a draw is keyed by (seed, row, action index)
+                actions, logp, _ = head.sample(logits.view(B, L, n_actions), buf.valid_actions_mask, seed=(a.seed << 32) + draws)
+                buf.step(actions, logp, value)
+            buf.finish(net(buf.obs.view(B * L, *obs_shape))[1])
+        sums = torch.zeros(5, device=dev)           # policy loss, value loss, entropy, clipped share, batches
+        for batch in buf.minibatches(a.batch_size, epochs=a.epochs, seed=a.seed + it):
+            w = batch["weight"]
+            n = w.sum().clamp_min(1.0)
+            logits, value = net(batch["obs"])
+            logp, entropy = head.evaluate(logits, batch["valid_actions_mask"], batch["action"])
+            ratio = (logp - batch["logp"]).exp()
+            adv = batch["advantages"]
+            pg = -(torch.min(ratio * adv, ratio.clamp(1 - a.clip, 1 + a.clip) * adv) * w).sum() / n
+            vl = (0.5 * (value - batch["returns"]) ** 2 * w).sum() / n
+            ent = (entropy * w).sum() / n
+            loss = pg + a.value_coef * vl - a.entropy_coef * ent
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            nn.utils.clip_grad_norm_(net.parameters(), 0.5)
+            opt.step()
+            with torch.no_grad():
+                sums += torch.stack([pg, vl, ent, (((ratio - 1).abs() > a.clip).float() * w).sum() / n, torch.ones((), device=dev)])
+        valid = float(buf.stats[0])                 # the iteration's one host read (with the sums below)
+        buf.next_rollout()
+        s = (sums[:4] / sums[4].clamp_min(1.0)).tolist()
+        row = {"iteration": it, "policy_loss": s[0], "value_loss": s[1], "entropy": s[2], "clip_fraction": s[3],
+               "valid_rows": valid / (a.horizon * B * L), "env_steps": (it + 1) * a.horizon * B,
+               "seconds": time.perf_counter() - t0}
+        print(json.dumps(row))
+        out.append(row)
+    moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), start))
+    result = {"iterations": out, "bad_actions": head.bad_actions, "rejected": int(buf.rejected.item()), "parameter_change": moved}
+    env.close()
+    return result
+
+
+if __name__ == "__main__":
+    main()

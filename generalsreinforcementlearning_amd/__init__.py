@@ -11,6 +11,7 @@ from .vec_engine import (ACTION_DTYPE, ACT_HALF, ACT_VALID, ERR_NAMES, TILE_CITY
 from .env_state import VecEnvState  # noqa: F401
 from .env_pool import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
 from .rollout import SelfPlayRolloutBuffer  # noqa: F401
+from .policy_head import MaskedCategoricalHead  # noqa: F401
 
 __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState",
-           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer"]
+           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead"]

@@ -72,6 +72,22 @@ class TrajGatherArgs(C.Structure):
                                              "rejected")])
 
 
+class PolicySampleArgs(C.Structure):
+    """gvec_policy_sample_args (include/generals_vec.h): every pointer is device memory."""
+    _fields_ = ([("rows", C.c_int64), ("num_actions", C.c_int32), ("greedy", C.c_int32), ("seed", C.c_uint64), ("row_base", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "action", "logp", "entropy")])
+
+
+class PolicyEvaluateArgs(C.Structure):
+    _fields_ = ([("rows", C.c_int64), ("num_actions", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "action", "logp", "entropy", "bad_actions")])
+
+
+class PolicyBackwardArgs(C.Structure):
+    _fields_ = ([("rows", C.c_int64), ("num_actions", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "action", "grad_logp", "grad_entropy", "grad_logits")])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -137,6 +153,9 @@ SYMBOLS = {
     "gvec_traj_gae": (_i32, [_i32, _vp, C.POINTER(TrajGaeArgs)]),
     "gvec_traj_compact": (_i32, [_i32, _vp, C.POINTER(TrajCompactArgs)]),
     "gvec_traj_gather": (_i32, [_i32, _vp, C.POINTER(TrajGatherArgs)]),
+    "gvec_policy_sample": (_i32, [_i32, _vp, C.POINTER(PolicySampleArgs)]),
+    "gvec_policy_evaluate": (_i32, [_i32, _vp, C.POINTER(PolicyEvaluateArgs)]),
+    "gvec_policy_backward": (_i32, [_i32, _vp, C.POINTER(PolicyBackwardArgs)]),
     "gvec_gym_observe": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

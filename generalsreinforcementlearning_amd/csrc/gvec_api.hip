@@ -1648,6 +1648,49 @@ int32_t gvec_traj_gather(int32_t device, void* hip_stream, const gvec_traj_gathe
   return GVEC_OK;
 }
 
+// ---- masked-categorical policy head (gvec_policy.hip) ----
+static int32_t policy_shape(const char* fn, int64_t rows, int32_t num_actions, bool null_ptr) {
+  if (rows < 0 || rows > 0x7FFFFFFFll || num_actions < 1) {
+    set_err("%s: rows %lld outside [0, 2^31) or num_actions %d < 1", fn, (long long)rows, num_actions);
+    return GVEC_E_INVALID;
+  }
+  if (null_ptr) {
+    set_err("%s: a required pointer is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  return GVEC_OK;
+}
+
+int32_t gvec_policy_sample(int32_t device, void* hip_stream, const gvec_policy_sample_args* a) {
+  if (!a) return traj_null("gvec_policy_sample");
+  RET_IF(policy_shape("gvec_policy_sample", a->rows, a->num_actions, !a->logits || !a->mask || !a->action || !a->logp || !a->entropy));
+  if (a->rows == 0) return GVEC_OK;
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_policy_sample(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_policy_evaluate(int32_t device, void* hip_stream, const gvec_policy_evaluate_args* a) {
+  if (!a) return traj_null("gvec_policy_evaluate");
+  RET_IF(policy_shape("gvec_policy_evaluate", a->rows, a->num_actions, !a->logits || !a->mask || !a->action || !a->logp || !a->entropy));
+  if (a->rows == 0) return GVEC_OK;
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_policy_evaluate(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
+int32_t gvec_policy_backward(int32_t device, void* hip_stream, const gvec_policy_backward_args* a) {
+  if (!a) return traj_null("gvec_policy_backward");
+  RET_IF(policy_shape("gvec_policy_backward", a->rows, a->num_actions, !a->logits || !a->mask || !a->action || !a->grad_logits));
+  if (a->rows == 0) return GVEC_OK;
+  RET_IF(ensure_device());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(launch_policy_backward(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+  return GVEC_OK;
+}
+
 int32_t gvec_record_agent_actions(gvec_handle* h, int32_t on) {
   if (!h) return GVEC_E_INVALID;
   if (h->sharded()) {

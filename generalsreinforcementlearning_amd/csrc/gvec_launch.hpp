@@ -302,4 +302,9 @@ hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s);
 hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s);
 hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s);
 
+// masked-categorical policy head (gvec_policy.hip; generals_vec.h "masked-categorical policy head")
+hipError_t launch_policy_sample(const gvec_policy_sample_args& a, hipStream_t s);
+hipError_t launch_policy_evaluate(const gvec_policy_evaluate_args& a, hipStream_t s);
+hipError_t launch_policy_backward(const gvec_policy_backward_args& a, hipStream_t s);
+
 }  // namespace gvec

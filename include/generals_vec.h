@@ -697,6 +697,54 @@ int32_t gvec_traj_gae(int32_t device, void* hip_stream, const gvec_traj_gae_args
 int32_t gvec_traj_compact(int32_t device, void* hip_stream, const gvec_traj_compact_args* args);
 int32_t gvec_traj_gather(int32_t device, void* hip_stream, const gvec_traj_gather_args* args);
 
+/* ---- masked-categorical policy head: sample, evaluate, backward (PPO) -----------------------------
+ * What stands between a network's logits and gvec_traj_record.  Handle-free like gvec_traj_*: every pointer is DEVICE memory
+ * on `device`, work is enqueued on hip_stream, nothing synchronises.  A row is num_actions = A float32 logits and A mask
+ * bytes (nonzero = legal; a bool tensor as it is); rows are dense ([rows][A]) and need only their dtype's alignment.
+ * Logits are finite or -inf; NaN and +inf are the caller's error and may propagate.  Per row, with S = {i : mask_i != 0 and
+ * l_i > -inf}:  m = max_S l_i,  Z = sum_S exp(l_i - m),  logp_i = l_i - m - log Z,  p_i = exp(logp_i),  H = -sum_S p_i logp_i.
+ * A row with S empty is DEAD (no legal action, or every legal logit -inf): action 0, logp 0, entropy 0, zero gradients, never
+ * a NaN.  |S| = 1 gives logp = 0 and H = 0 exactly.  float32 throughout, fixed reduction orders: the same input gives the same
+ * bits on every call.  One wavefront per row; a row of A <= 5120 is read from HBM once.
+ * gvec_policy_sample: action int64[rows], logp float32[rows] (of that action), entropy float32[rows].  greedy == 0: Gumbel-max,
+ *   action = argmax_S (l_i + g_i), lowest index among equals, g_i = -log(-log u_i) from the build's counter RNG keyed by
+ *   (seed, row_base + r, i) - DESIGN.md section 6 "Policy head" has the formula.  A draw depends on nothing else: rows
+ *   [R/2, R) sampled alone with row_base = R/2 repeat the second half of the full call.  greedy != 0: argmax_S l_i, lowest
+ *   index among equals.
+ * gvec_policy_evaluate: logp[r] = logp_{action[r]} and entropy[r].  An action outside [0, A) or outside S has logp 0 and adds
+ *   one to *bad_actions (int64, may be NULL; a device atomic, as gvec_traj_gather's `rejected`) - except on a dead row, where
+ *   no action is legal and none is counted.
+ * gvec_policy_backward: grad_logits float32[rows][A], EVERY element written (no clearing needed), p recomputed from the
+ *   logits:  i in S: grad_logp[r] * (1[i == action[r]] - p_i) - grad_entropy[r] * p_i * (logp_i + H);  otherwise 0.
+ *   grad_logp / grad_entropy float32[rows], either may be NULL (= zeros).  An action outside S carries no logp gradient.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL,
+ *   num_actions < 1, rows < 0 or rows >= 2^31.  rows == 0 is a no-op that needs no device. */
+typedef struct gvec_policy_sample_args {
+  int64_t rows;
+  int32_t num_actions, greedy;
+  uint64_t seed;
+  int64_t row_base;
+  const float* logits; const uint8_t* mask;
+  int64_t* action; float* logp; float* entropy;
+} gvec_policy_sample_args;
+typedef struct gvec_policy_evaluate_args {
+  int64_t rows;
+  int32_t num_actions, reserved;
+  const float* logits; const uint8_t* mask; const int64_t* action;
+  float* logp; float* entropy;
+  int64_t* bad_actions;                                                                    /* NULL: not counted */
+} gvec_policy_evaluate_args;
+typedef struct gvec_policy_backward_args {
+  int64_t rows;
+  int32_t num_actions, reserved;
+  const float* logits; const uint8_t* mask; const int64_t* action;
+  const float* grad_logp; const float* grad_entropy;                                       /* NULL: zeros */
+  float* grad_logits;
+} gvec_policy_backward_args;
+int32_t gvec_policy_sample(int32_t device, void* hip_stream, const gvec_policy_sample_args* args);
+int32_t gvec_policy_evaluate(int32_t device, void* hip_stream, const gvec_policy_evaluate_args* args);
+int32_t gvec_policy_backward(int32_t device, void* hip_stream, const gvec_policy_backward_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
