@@ -30,7 +30,7 @@ static hipError_t launch_waves(void (*k)(P...), int n, hipStream_t s, const A&..
   return hipGetLastError();
 }
 
-// the resident format keeps planes of 2*S-1 or 2*S dwords (gvec_api.hip: plane_dwords), and the kernels that take the plane
+// the resident format keeps planes of 2*S-1 or 2*S dwords (gvec_api.hip: set_geometry), and the kernels that take the plane
 // stride as a compile-time constant come in both: 1 for the odd form, 0 for the even one, -1 when a is neither of variant <P, S>
 template <int P, int S>
 static int plane_parity(const StepArgs& a) {

@@ -8,7 +8,7 @@ import _oracle as O
 
 def layout_for(max_w, max_h, max_p):
     """What gvec_experience_record_layout reports for a handle of these limits (gvec_kernels.hip pick_variant,
-    gvec_api.hip plane_dwords, RecordLayout)."""
+    gvec_api.hip set_geometry, RecordLayout)."""
     stride = max_w * max_h
     mp = next(m for m in (2, 4, 8) if m >= max_p)
     ns = next(n for n in (1, 2, 4, 7, 10, 16) if n * 64 >= stride)

@@ -70,6 +70,11 @@ def test_every_source_is_built_and_watched():
     names = sorted(os.listdir(CSRC))
     assert sorted(n for n in names if n.endswith(".hip")) == sorted(B.SRCS)
     assert {n for n in names if n.endswith(".hpp")} <= set(B.DEPS)
+    # build.py watches a HOST_DEPS header for the gvec_api* units alone: no other unit or header may include one
+    for n in names:
+        if n.endswith((".hip", ".hpp", ".inc")) and not n.startswith("gvec_api") and n not in B.HOST_DEPS:
+            text = open(os.path.join(CSRC, n)).read()
+            assert not [d for d in B.HOST_DEPS if f'"{d}"' in text], n
 
 
 def test_no_cross_lane_read_behind_a_short_circuit():
