@@ -377,13 +377,16 @@ int32_t gvec_step_traffic_bytes(const gvec_handle* h, int64_t* out4) {
   static_assert(Planes<4>::MUTABLE == 2 * 4 + 3 && Planes<4>::LST - Planes<4>::MUTABLE == 10 && Planes<4>::COUNT - Planes<4>::LST == 4,
                 "gvec_step_traffic_bytes restates the plane block's partition");
   const int64_t fd = h->fd, mp = h->var.maxp;
+  const int nslot = h->var.nslot;
+  const bool odd = fd == 2 * nslot - 1;
   const int64_t hdr = HDR_DW * 4;
   const int64_t mut = (2 * mp + 3) * fd * 4;    // Planes<MAXP>::MUTABLE: own, vis, chg, vch, gt1
-  const int64_t cst = 10 * fd * 4;              // gen, city, mtn, valid, ncol0, ncolL, ok[4]
+  // gen, city, mtn, valid, ncol0, ncolL, and ok[4] where the kernel does not rebuild them (gvec_device.hpp "GVEC_LEAN")
+  const int64_t cst = (lean_derive_ok(nslot) ? 6 : 10) * fd * 4;
   const int64_t lst = mp * fd * 4;              // OwnedTiles planes: only while HF_LDIFF
   const int64_t a16 = (int64_t)h->army_dw * 2, a32 = (int64_t)h->army_dw * 4;
-  out4[0] = hdr + mut + cst + a16;
-  out4[1] = hdr + mut + a16;
+  out4[0] = hdr + mut + cst + a16 - (lean_half_last(nslot, odd) ? 64 : 0);       // the dead half of an odd last army slot is not read
+  out4[1] = hdr + mut + lean_fold_dwords((int)(2 * mp + 3), (int)fd) * 4 + a16;  // the staged store ends on a whole chunk
   out4[2] = (int64_t)h->maxp * h->mask_bytes;
   out4[3] = 2 * lst + 2 * a32;
   return GVEC_OK;

@@ -62,7 +62,25 @@ extern "C" __device__ int gvec_llvm_writelane(int value, int lane, int vdst_in) 
 #define GVEC_SC1 1
 #endif
 
+// What the per-turn load path (load_turn<true>: step and gym kernels) and its staged plane store leave out because it
+// carries no information for the turn (bits; DESIGN.md 4.1 "Lean traffic"; one-process A/B per bit, scripts/ab_bench.py):
+// 1: ok[4] is rebuilt from mtn / valid / ncol0 / ncolL instead of loaded      2: the dead half of an odd last army slot is
+// not loaded      4: the staged plane store ends on a whole 16-byte chunk (no 1..3-dword tail instruction)
+#ifndef GVEC_LEAN
+#define GVEC_LEAN 7
+#endif
+
 namespace gvec {
+
+// The same knob as constants of a kernel variant (NSLOT 64-tile slots, FD = 2*NSLOT or - `odd` - 2*NSLOT-1 plane dwords):
+// shared by the kernels and by gvec_step_traffic_bytes, which reports what they move.
+// ok[4] is rebuilt except on full 32-lane rows (NSLOT = 16: two players per register, 32 dwords a plane), whose shifts each
+// cost a column select more and whose largest gym kernel has no register left for them (it would spill).
+constexpr bool lean_derive_ok(int nslot) { return (GVEC_LEAN & 1) != 0 && 2 * nslot < 64 / (nslot <= 7 ? 4 : 2); }
+// an `odd` board has at most 32*(2*NSLOT-1) tiles: lanes 32..63 of an odd last army slot hold none
+constexpr bool lean_half_last(int nslot, bool odd) { return (GVEC_LEAN & 2) != 0 && odd && (nslot & 1) != 0; }
+// dwords of the GEN plane the staged plane store rewrites to end on a 16-byte boundary (mutable_planes = Planes<MAXP>::MUTABLE)
+constexpr int lean_fold_dwords(int mutable_planes, int fd) { return (GVEC_LEAN & 4) != 0 ? ((mutable_planes * fd + 3) & ~3) - mutable_planes * fd : 0; }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -192,7 +210,10 @@ template <int NSLOT>
 __device__ __forceinline__ ArmyCRef army_cref(const uint32_t* a16, const int32_t* a32, int env) {
   return ArmyCRef(a16 + (size_t)env * (NSLOT * 32), a32 + (size_t)env * (NSLOT * 64));
 }
-template <int NSLOT>
+// HALF_LAST (odd NSLOT only): the caller knows that the board has at most 32*(2*NSLOT-1) tiles, so lanes 32..63 of the
+// last slot hold no tile - they are zero in memory from import or re-deal on, and every store writes zeros back - and read
+// as zero without a load
+template <int NSLOT, bool HALF_LAST = false>
 __device__ __forceinline__ void army_load_narrow(int32_t (&army)[NSLOT], const uint32_t* n) {
   const int lane = (int)(threadIdx.x & 63u);
 #pragma unroll
@@ -201,7 +222,14 @@ __device__ __forceinline__ void army_load_narrow(int32_t (&army)[NSLOT], const u
     army[2 * k] = (int32_t)(w & 0xFFFFu);
     army[2 * k + 1] = (int32_t)(w >> 16);
   }
-  if constexpr ((NSLOT & 1) != 0) army[NSLOT - 1] = (int32_t)ld_stream(reinterpret_cast<const uint16_t*>(n + 64 * (NSLOT / 2)) + lane);
+  if constexpr ((NSLOT & 1) != 0) {
+    if constexpr (HALF_LAST) {
+      army[NSLOT - 1] = 0;
+      if (lane < 32) army[NSLOT - 1] = (int32_t)ld_stream(reinterpret_cast<const uint16_t*>(n + 64 * (NSLOT / 2)) + lane);
+    } else {
+      army[NSLOT - 1] = (int32_t)ld_stream(reinterpret_cast<const uint16_t*>(n + 64 * (NSLOT / 2)) + lane);
+    }
+  }
 }
 template <int NSLOT>
 __device__ __forceinline__ void army_load_wide(int32_t (&army)[NSLOT], const int32_t* w) {

@@ -284,6 +284,7 @@ template <int MAXP_, int NSLOT_, bool ODD>
 struct GymStepGeom {
   static constexpr int MAXP = MAXP_, NSLOT = NSLOT_;
   static constexpr int FD = 2 * NSLOT - (ODD ? 1 : 0);
+  static constexpr bool ODD_FD = ODD;
   static constexpr int ROW_DW = (Planes<MAXP>::COUNT * FD + 3) / 4 * 4;
   static constexpr int STAGE_DW = (NSLOT * 64 * 5 + 15) / 16 * 4;  // the gym mask's stage (5 bytes a tile) is the larger user of the army shadow
   static_assert(STAGE_DW >= NSLOT * 64, "the stage also serves as the action phase's army shadow");
@@ -295,7 +296,7 @@ __device__ __forceinline__ ArmyRef gym_load_turn(typename K::B& b, const StepArg
   b.larmy = stage;
   b.lscr = scratch;
   const ArmyRef army_env = army_ref<K::NSLOT>(A.army16, A.army32, env);
-  load_turn<true>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * K::ROW_DW, army_env, K::FD, A.zeros);
+  load_turn<true, lean_half_last(K::NSLOT, K::ODD_FD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * K::ROW_DW, army_env, K::FD, A.zeros);
   b.small = !(b.hflags & HF_WIDE);
   return army_env;
 }

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, step_waves(MAXP, NSLOT)) void
   b.larmy = army_shadow[wave];
   b.lscr = act_scratch[wave];
   const ArmyRef army_env = army_ref<NSLOT>(A.army16, A.army32, env);
-  load_turn<true>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
+  load_turn<true, lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
   b.small = !(b.hflags & HF_WIDE);  // one turn from armies <= 65535: every sum of the turn stays below 2^23
   const bool emit = (A.flags & KF_EMIT) != 0u;
   uint32_t m[B::NR][4];

@@ -109,7 +109,10 @@ struct PBoard {
   uint32_t valid, ncol0, ncolL, ok[4];        // replicated constant planes (see Board)
   uint32_t rowbit[NR];                        // 1 << (the player this lane holds in register k)
   static constexpr int NSHARED = PL::SHARED;                    // the 13 shared planes, CHG .. OK[3], contiguous in the block
-  static constexpr int NSR = (NSHARED + PPR - 1) / PPR;         // ... loaded PPR at a time, like the packed ones
+  static constexpr bool DERIVE_OK = lean_derive_ok(NSLOT);      // the per-turn load rebuilds OK[4] from the planes before them
+  static_assert(!(DERIVE_OK && FULL_ROWS), "lean_derive_ok leaves the full-row variants alone");
+  static constexpr int NPACKED = DERIVE_OK ? PL::OK - PL::CHG : NSHARED;  // what load_planes<true> fetches: CHG .. NCOLL, or all 13
+  static constexpr int NSR = (NPACKED + PPR - 1) / PPR;         // ... loaded PPR at a time, like the packed ones
   uint32_t shp[NSR];                          // in flight between load_planes and spread_shared: row r of shp[k] = shared plane k*PPR + r
   int32_t army[NSLOT];                        // tile domain, as in Board
   uint32_t hv;
@@ -277,7 +280,7 @@ struct PBoard {
 #pragma unroll
       for (int k = 0; k < NSR; ++k) {
         shp[k] = 0u;
-        if (in && (k * PPR + row() < NSHARED)) shp[k] = ld_stream(lane_base + (PL::CHG + k * PPR) * fd);
+        if (in && (k * PPR + row() < NPACKED)) shp[k] = ld_stream(lane_base + (PL::CHG + k * PPR) * fd);
       }
     } else {
 #pragma unroll
@@ -336,8 +339,20 @@ struct PBoard {
     valid = shared_plane(PL::VALID - PL::CHG);
     ncol0 = shared_plane(PL::NCOL0 - PL::CHG);
     ncolL = shared_plane(PL::NCOLL - PL::CHG);
+    if constexpr (DERIVE_OK) {
+      // Board::targets() in the packed domain: bit for bit the stored planes on every lane with col() < fd.  The lanes
+      // beyond hold zero in valid / ncol0 / ncolL (never loaded), so notm, ok[1] and ok[3] are zero there; ok[0] and ok[2]
+      // may carry the neighbouring lane's bits into column fd, where every plane they are ever ANDed with (own, lst, gt1:
+      // legal_planes) is zero.  Needs W (the header has landed) and wave-uniform control flow.
+      const uint32_t notm = valid & ~mtn;
+      ok[0] = upW(notm);
+      ok[1] = dn1(notm) & ncolL;
+      ok[2] = dnW(notm);
+      ok[3] = up1(notm) & ncol0;
+    } else {
 #pragma unroll
-    for (int d = 0; d < 4; ++d) ok[d] = shared_plane(PL::OK + d - PL::CHG);
+      for (int d = 0; d < 4; ++d) ok[d] = shared_plane(PL::OK + d - PL::CHG);
+    }
   }
   // The planes from GEN on change only when the env is re-dealt (with_types).
   __device__ __forceinline__ void store_planes(uint32_t* rows_env, int fd, int row_dw, bool with_types) const {
@@ -378,7 +393,8 @@ struct PBoard {
     army_load_narrow<NSLOT>(army, a.n);
     if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
   }
-  __device__ __forceinline__ void load_army_narrow(const ArmyCRef& a) { army_load_narrow<NSLOT>(army, a.n); }  // needs no header
+  template <bool HALF_LAST = false>
+  __device__ __forceinline__ void load_army_narrow(const ArmyCRef& a) { army_load_narrow<NSLOT, HALF_LAST>(army, a.n); }  // needs no header
   __device__ __forceinline__ void load_army_wide_if_flagged(const ArmyCRef& a) {
     if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
   }
@@ -1014,8 +1030,17 @@ struct PBoard {
       const int j = k * PPR + row();
       if (in && j < 3) g[(PL::CHG + k * PPR) * fd] = j == 0 ? chg : (j == 1 ? vch : gt1);
     }
+    // The dwords between the mutable planes' end and the next 16-byte boundary are the first of the GEN plane (and of
+    // CITY / MTN where a plane is shorter than the gap): constants this wave holds.  Staged behind the mutable planes,
+    // they make the flush whole chunks - no 1..3-dword tail instruction - and rewrite what is there.
+    const int gap = lean_fold_dwords(PL::MUTABLE, fd);  // 0..3
+    if (in && row() == 0) {
+      if (col() < gap) g[PL::GEN * fd] = gen;
+      if (fd + col() < gap) g[PL::CITY * fd] = city;
+      if (2 * fd + col() < gap) g[PL::MTN * fd] = mtn;
+    }
     wave_lds_fence();
-    flush_stage<GVEC_NT_PLANE>(rows_env, PL::MUTABLE * fd);
+    flush_stage<GVEC_NT_PLANE>(rows_env, PL::MUTABLE * fd + gap);
     store_lists(rows_env, fd);
   }
   // narrow armies (the caller has checked army_fits_narrow): the block's layout is army_store_narrow's

@@ -112,12 +112,13 @@ __device__ __forceinline__ void load_board(BT& b, const uint32_t* hdr, const uin
 // EARLY (the per-turn step kernel): every load of the board goes out before the header is decoded - one memory round
 // trip per board instead of two, worth 10 % there (one-process A/B: 338.7 -> 305.6 us per 262,144 boards).  The fused
 // rollout amortises its loads over many turns and runs 4 % faster with the plain order (fewer live registers).
-template <bool EARLY = false, typename BT>
+// HALF_LAST (EARLY only): the board has at most 32*(2*NSLOT-1) tiles - see army_load_narrow.
+template <bool EARLY = false, bool HALF_LAST = false, typename BT>
 __device__ __forceinline__ void load_turn(BT& b, const uint32_t* hdr, const uint32_t* rows, const ArmyCRef& army, int fd, const uint32_t* zeros) {
   if constexpr (EARLY) {
     b.issue_hdr(hdr);
     b.load_planes(rows, fd, zeros);
-    b.load_army_narrow(army);
+    b.template load_army_narrow<HALF_LAST>(army);
     b.decode_hdr_scalar(hdr);   // SMEM: in flight with the vector loads above
     b.land();
     b.land_scalars();

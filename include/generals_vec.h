@@ -297,8 +297,9 @@ int32_t gvec_set_agent_mix(gvec_handle* h, int32_t noop_per_65536, int32_t half_
 int32_t gvec_counters(gvec_handle* h, gvec_rollout_stats* out);
 /* The HBM bytes ONE env-step of the hot path (gvec_step / per-turn gvec_rollout) must move BY CONSTRUCTION of the
  * resident layout, from the same constants the kernel is compiled with:
- * out4[0] read  = header + mutable and constant planes + narrow armies
- * out4[1] write = header + mutable planes + narrow armies
+ * out4[0] read  = header + the mutable and constant planes the step kernel fetches (not the move-target planes where it
+ *                 rebuilds them) + narrow armies (less an odd last slot's dead half)
+ * out4[1] write = header + mutable planes (rounded up to a whole 16-byte chunk) + narrow armies
  * out4[2] mask  = the legal masks written when legal_bits / the agent is on (max_players * mask_bytes)
  * out4[3] extra = what an env in the rare forms adds on top (list planes both ways + the int32 army escape both ways)
  * bench.py prices roofline.frac with read + write + mask. */
