@@ -11,6 +11,10 @@ re-deal rows and eliminated learners).  The reference plans this phase (document
 learner for it; the code is this repo's own.  An example, not part of the measured hot path.
 
     python examples/train_ppo_selfplay.py --num-envs 1024 --iterations 50
+
+--features adds the five strategic feature planes (features.strategic_features: distances to the own general, the nearest
+enemy, city and fogged tile, and the front line) to the nine of the observation.  The store keeps nine planes per row: the
+five are recomputed from them where they are consumed, while acting and on every minibatch.
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 
+from generalsreinforcementlearning_amd.features import NUM_STRATEGIC_FEATURES, strategic_features
 from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead
 from generalsreinforcementlearning_amd.rollout import SelfPlayRolloutBuffer
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
@@ -59,12 +64,16 @@ def main(argv=None):
     ap.add_argument("--entropy-coef", type=float, default=0.01)
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--features", action="store_true", help="feed the five strategic feature planes next to the observation's nine")
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
     dev = torch.device("cuda", 0)
     obs_shape, n_actions = (9, a.board, a.board), a.board * a.board * 5
-    net = ActorCritic(obs_shape, n_actions).to(dev)
+    channels = 9 + (NUM_STRATEGIC_FEATURES if a.features else 0)
+    net = ActorCritic((channels,) + obs_shape[1:], n_actions).to(dev)
+    # the network's input of observations [N, 9, H, W]: a pure function of them, so stored rows need no extra planes
+    inputs = (lambda o: torch.cat([o, strategic_features(o)], dim=1)) if a.features else (lambda o: o)
     opt = torch.optim.Adam(net.parameters(), lr=a.lr)
     start = [p.detach().clone() for p in net.parameters()]
     env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
@@ -77,16 +86,16 @@ def main(argv=None):
     for it in range(a.iterations):
         with torch.no_grad():
             while not buf.full:
-                logits, value = net(buf.obs.view(B * L, *obs_shape))
+                logits, value = net(inputs(buf.obs.view(B * L, *obs_shape)))
                 draws += 1                          # one seed per step: a draw is keyed by (seed, row, action index)
                 actions, logp, _ = head.sample(logits.view(B, L, n_actions), buf.valid_actions_mask, seed=(a.seed << 32) + draws)
                 buf.step(actions, logp, value)
-            buf.finish(net(buf.obs.view(B * L, *obs_shape))[1])
+            buf.finish(net(inputs(buf.obs.view(B * L, *obs_shape)))[1])
         sums = torch.zeros(5, device=dev)           # policy loss, value loss, entropy, clipped share, batches
         for batch in buf.minibatches(a.batch_size, epochs=a.epochs, seed=a.seed + it):
             w = batch["weight"]
             n = w.sum().clamp_min(1.0)
-            logits, value = net(batch["obs"])
+            logits, value = net(inputs(batch["obs"]))
             logp, entropy = head.evaluate(logits, batch["valid_actions_mask"], batch["action"])
             ratio = (logp - batch["logp"]).exp()
             adv = batch["advantages"]

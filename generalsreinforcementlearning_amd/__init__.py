@@ -12,6 +12,8 @@ from .env_state import VecEnvState  # noqa: F401
 from .env_pool import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
 from .rollout import SelfPlayRolloutBuffer  # noqa: F401
 from .policy_head import MaskedCategoricalHead  # noqa: F401
+from .features import NUM_STRATEGIC_FEATURES, STRATEGIC_FEATURE_NAMES, strategic_features  # noqa: F401
 
 __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState",
-           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead"]
+           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "strategic_features",
+           "NUM_STRATEGIC_FEATURES", "STRATEGIC_FEATURE_NAMES"]

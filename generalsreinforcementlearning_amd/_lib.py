@@ -88,6 +88,12 @@ class PolicyBackwardArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("logits", "mask", "action", "grad_logp", "grad_entropy", "grad_logits")])
 
 
+class ObsFeaturesArgs(C.Structure):
+    """gvec_obs_features_args (include/generals_vec.h): obs and out are device memory."""
+    _fields_ = ([("rows", C.c_int64)] + [(n, C.c_int32) for n in ("width", "height", "cap", "reserved")]
+                + [("obs_row_stride", C.c_int64), ("obs", C.c_void_p), ("out", C.c_void_p)])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -156,7 +162,8 @@ SYMBOLS = {
     "gvec_policy_sample": (_i32, [_i32, _vp, C.POINTER(PolicySampleArgs)]),
     "gvec_policy_evaluate": (_i32, [_i32, _vp, C.POINTER(PolicyEvaluateArgs)]),
     "gvec_policy_backward": (_i32, [_i32, _vp, C.POINTER(PolicyBackwardArgs)]),
-    "gvec_gym_observe": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gvec_obs_features": (_i32, [_i32, _vp, C.POINTER(ObsFeaturesArgs)]),
+    "gvec_gym_observe":(_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_step": (_i32, [_vp, _i32, _u64] + [_vp] * 3 + [_i32] + [_vp] * 11),

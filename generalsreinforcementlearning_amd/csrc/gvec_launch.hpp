@@ -307,4 +307,7 @@ hipError_t launch_policy_sample(const gvec_policy_sample_args& a, hipStream_t s)
 hipError_t launch_policy_evaluate(const gvec_policy_evaluate_args& a, hipStream_t s);
 hipError_t launch_policy_backward(const gvec_policy_backward_args& a, hipStream_t s);
 
+// strategic feature planes (gvec_features.hip; generals_vec.h "strategic feature planes")
+hipError_t launch_obs_features(const gvec_obs_features_args& a, hipStream_t s);
+
 }  // namespace gvec

@@ -91,7 +91,8 @@ class VecEnvState:
 class EnvStateMixin:
     """copy_envs / save_state / restore_state for the vector envs.  The env provides engine, num_envs, _t, _dev, _d_turn,
     _d_step, _step_no, _seed, _episode, _pool, device_outputs, _to_numpy, _observe_info() (one observe pass over the batch
-    -> (obs, info) as reset() returns them in device mode) and _learner_ids()."""
+    -> (obs, info) as reset() returns them in device mode), _learner_ids() and _feat_cap / _feat_bufs / _feat_flip
+    (_feature_option, _add_features)."""
 
     def state_config(self):
         e = self.engine
@@ -99,6 +100,42 @@ class EnvStateMixin:
                 "fog_of_war": bool(self.fog_of_war), "production": list(e.production),
                 "normal_growth_interval": int(e.normal_growth_interval), "max_turns": int(self.max_turns),
                 "learners": list(self._learner_ids()), "num_envs": self.num_envs}
+
+    # ---- info["strategic_features"] (features.py): the option of both envs ----
+    @staticmethod
+    def _feature_option(strategic_features, feature_cap, device_outputs):
+        """The cap when the option is on, else None.  Checked before anything touches a device."""
+        if not strategic_features:
+            return None
+        from .features import check_cap
+        if not device_outputs:
+            raise ValueError("strategic_features=True needs device_outputs=True: the planes are computed on the device from the "
+                             "observation tensor the step wrote")
+        return check_cap(feature_cap)
+
+    def _check_uniform_boards(self, engine=None):
+        """The feature kernel reads every observation as [9, board_height, board_width].  In a padded batch of unequal board
+        sizes an env's planes have its own row pitch inside the padded slot: refused with ValueError (reset, restore_state)."""
+        if self._feat_cap is None:
+            return
+        st = (engine or self.engine).game_state(fields=("width", "height"))
+        if bool((st["width"] != self.board_width).any() or (st["height"] != self.board_height).any()):
+            raise ValueError(f"strategic_features=True needs every board to be {self.board_width}x{self.board_height}: this is a padded "
+                             "batch of unequal board sizes")
+
+    def _add_features(self, obs, info):
+        """One extra launch on the observation just written fills info["strategic_features"] ([..., 5, H, W] for obs
+        [..., 9, H, W]).  Two buffers owned by the env alternate, like the observation's: what a step returns is reused by
+        the step after next.  With the option off nothing is allocated or launched and info is left as it is."""
+        if self._feat_cap is None:
+            return info
+        from .features import strategic_features
+        if self._feat_bufs is None:
+            shape = tuple(obs.shape[:-3]) + (5,) + tuple(obs.shape[-2:])
+            self._feat_bufs = [self._t.empty(shape, dtype=self._t.float32, device=self._dev) for _ in range(2)]
+        self._feat_flip ^= 1
+        info["strategic_features"] = strategic_features(obs, cap=self._feat_cap, out=self._feat_bufs[self._feat_flip])
+        return info
 
     def _env_ids(self, ids):
         t = self._t
@@ -192,6 +229,7 @@ class EnvStateMixin:
         if ids.numel() != state.num_envs:
             raise GvecError(GVEC_E_INVALID, f"restore_state: {ids.numel()} env ids for a state of {state.num_envs} envs")
         self._check_ids(ids, "restore_state")
+        self._check_uniform_boards(state.engine)
         self.engine.copy_envs(ids, None, n=state.num_envs, src=state.engine)
         self._set_rows(ids, state.turn_count, state.resetting)
         if full:

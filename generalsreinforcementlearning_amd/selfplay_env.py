@@ -27,14 +27,19 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
     copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, learners=None, fog_of_war=True, max_turns=500,
-                 seed=0, device=0, board_pool=1024, device_outputs=False):
+                 seed=0, device=0, board_pool=1024, device_outputs=False, strategic_features=False, feature_cap=64):
         """learners: the player ids that are learners (None: every player); the others are the on-device random agent.
         device_outputs=True  observation / mask / reward / flags are torch tensors on the GPU; `step` takes a CUDA int64
                              tensor [B, L] of actions.  Every tensor a step returns lives in a buffer that the step AFTER
                              NEXT reuses.
         default              numpy arrays in, numpy arrays out - the same kernel, its outputs copied to pinned host
                              buffers; the observation and mask arrays a step returns likewise stay intact until the step
-                             after next."""
+                             after next.
+        strategic_features=True  (needs device_outputs=True) reset / step / copy_envs / restore_state add
+                             info["strategic_features"], float32 [B, L, 5, H, W]: features.strategic_features of the observation
+                             they return (a step's obs_out slot included), distances capped at feature_cap.  One extra
+                             launch per call."""
+        self._feat_cap, self._feat_bufs, self._feat_flip = self._feature_option(strategic_features, feature_cap, device_outputs), None, 0
         import torch
         if not torch.cuda.is_available():
             from ._lib import GvecError
@@ -105,7 +110,8 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
                                            self._d_reward.data_ptr(), self._d_done.data_ptr(), self._d_winner.data_ptr()),
               "gvec_gym_observe_players")
         self.valid_actions_mask = mask.view(self._t.bool)
-        return obs, {"player_ids": list(self.player_ids), "valid_actions_mask": self.valid_actions_mask, "turn": self._d_turn.clone()}
+        return obs, self._add_features(obs, {"player_ids": list(self.player_ids), "valid_actions_mask": self.valid_actions_mask,
+                                             "turn": self._d_turn.clone()})
 
     def _step_args(self, k, flip):
         """The pointer arguments of gvec_gym_step_players for step number k (mod 3) writing observation buffer `flip`."""
@@ -164,7 +170,7 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
               "gvec_gym_step_players")
         self._episode += 1
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], dict(info)
+        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
     def _to_numpy(self, obs, info):
         """The device outputs as numpy arrays (default mode): observation and mask land in pinned buffers that alternate,
@@ -185,6 +191,7 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
         self.engine.reset_generated(self._seed * 1000003 + 17)
         self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
         self._pool_key = (self._pool, self._seed * 7919 + 5)
+        self._check_uniform_boards()
         obs, info = self._reset_device()
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 

@@ -38,7 +38,8 @@ class GeneralsVecEnv(EnvStateMixin):
     copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, fog_of_war=True, max_turns=500,
-                 seed=0, device=0, board_pool=1024, device_outputs=False, opponent="random", opponent_random_permille=0):
+                 seed=0, device=0, board_pool=1024, device_outputs=False, opponent="random", opponent_random_permille=0,
+                 strategic_features=False, feature_cap=64):
         """device_outputs=True  observation / mask / reward / flags are torch tensors on the GPU; `step` takes a CUDA int64
                              tensor of actions: no board state crosses PCIe, a step is one kernel launch.  Every tensor a
                              step returns lives in a buffer that the step AFTER NEXT reuses.
@@ -48,7 +49,11 @@ class GeneralsVecEnv(EnvStateMixin):
         opponent="bot"       the other seats are the scripted opponent (gvec_bot_actions), computed on
                              the device into the step's action buffer, then the composed step (_step_composed);
                              opponent_random_permille of its moves are the random agent's instead.
-        step(actions, other_actions=...) overrides either choice for that step."""
+        step(actions, other_actions=...) overrides either choice for that step.
+        strategic_features=True  (needs device_outputs=True) reset / step / copy_envs / restore_state add
+                             info["strategic_features"], float32 [B, 5, H, W]: features.strategic_features of the observation
+                             they return, distances capped at feature_cap.  One extra launch per call."""
+        self._feat_cap, self._feat_bufs, self._feat_flip = self._feature_option(strategic_features, feature_cap, device_outputs), None, 0
         if opponent not in ("random", "bot"):
             raise ValueError(f"opponent must be 'random' or 'bot', not {opponent!r}")
         if not 0 <= int(opponent_random_permille) <= 1000:
@@ -118,7 +123,8 @@ class GeneralsVecEnv(EnvStateMixin):
 
     def _observe_info(self):
         obs = self._gym_observe()
-        return obs, {"player_id": self.player_id, "valid_actions_mask": self.valid_actions_mask, "turn": self._d_turn.clone()}
+        return obs, self._add_features(obs, {"player_id": self.player_id, "valid_actions_mask": self.valid_actions_mask,
+                                             "turn": self._d_turn.clone()})
 
     def _learner_ids(self):
         return [self.player_id]
@@ -158,7 +164,7 @@ class GeneralsVecEnv(EnvStateMixin):
         check(e.L.gvec_gym_step(e.h, self.player_id, self._seed + 1000 * self._episode + 1, actions.data_ptr(), *ptrs), "gvec_gym_step")
         self._episode += 1
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], dict(info)
+        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
     def _step_bot(self, actions):
         """The other seats played by the scripted opponent: gvec_bot_actions writes their moves into the step's action buffer
@@ -206,7 +212,7 @@ class GeneralsVecEnv(EnvStateMixin):
                                      out["truncated"].data_ptr(), out["winner"].data_ptr(), out["needs_reset"].data_ptr(),
                                      out["turn"].data_ptr()), "gvec_gym_finish_step")
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], dict(info)
+        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
     def _to_numpy(self, obs, info):
         """The device path's outputs as numpy arrays (default mode): observation and mask land in pinned buffers that
@@ -227,6 +233,7 @@ class GeneralsVecEnv(EnvStateMixin):
         self.engine.reset_generated(self._seed * 1000003 + 17)
         self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
         self._pool_key = (self._pool, self._seed * 7919 + 5)
+        self._check_uniform_boards()
         obs, info = self._reset_device()
         return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
 

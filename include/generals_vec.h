@@ -746,6 +746,30 @@ int32_t gvec_policy_sample(int32_t device, void* hip_stream, const gvec_policy_s
 int32_t gvec_policy_evaluate(int32_t device, void* hip_stream, const gvec_policy_evaluate_args* args);
 int32_t gvec_policy_backward(int32_t device, void* hip_stream, const gvec_policy_backward_args* args);
 
+/* ---- strategic feature planes: a pure function of the observation ------------------------------------
+ * Five planes a small conv torso cannot compute for itself, from the nine planes of any observation: what a step returned, a
+ * replay or rollout minibatch.  Handle-free like the policy head: DEVICE pointers on `device`, enqueued on hip_stream, nothing
+ * synchronises.  Nothing is read that the observation does not hold, so no fog leaks.
+ * obs float32 [rows][9][H*W], consecutive observations obs_row_stride floats apart; tile t = y*W + x.  Per tile:
+ *   vis = obs[0] != 0, mine = obs[1] == 0.5, enemy = obs[1] == 1.0, mtn = obs[4] != 0, city = obs[5] != 0, gen = obs[6] != 0,
+ *   pass = !mtn.  Planes 2, 3, 7 and 8 are not read.
+ * out float32 [rows][5][H*W], contiguous, EVERY element written.  Planes 0-3 hold min(d, cap) / cap, d the length of the
+ *   shortest 4-connected path from the tile to a source tile of the plane over passable tiles (both ends included; no step
+ *   wraps from column W-1 to column 0 of the next row).  A source has d = 0; an impassable or unreachable tile, and every tile
+ *   of a plane without a source, gets 1.0.  Sources: 0 gen & mine (the own general), 1 enemy, 2 city & !mine (cities to take),
+ *   3 !vis & pass (the nearest fogged tile).  Plane 4, the front line: 1.0 where mine holds and a 4-neighbour is enemy, else 0.0.
+ *   cap is a power of two, so every value is an exact float32: the result is defined to the bit.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL,
+ *   rows < 0 or rows >= 2^31, width or height outside [1, GVEC_MAX_DIM], cap not a power of two in [2, 1024], reserved != 0,
+ *   obs_row_stride < 9*width*height.  rows == 0 is a no-op that needs no device. */
+typedef struct gvec_obs_features_args {
+  int64_t rows;
+  int32_t width, height, cap, reserved;
+  int64_t obs_row_stride;                                                                  /* floats, >= 9*width*height */
+  const float* obs; float* out;
+} gvec_obs_features_args;
+int32_t gvec_obs_features(int32_t device, void* hip_stream, const gvec_obs_features_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
