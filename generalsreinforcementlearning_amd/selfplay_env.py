@@ -13,18 +13,22 @@ Differences from GeneralsVecEnv: an action the mask refuses is
 plays its turn (one policy's mistake must not freeze the other learners) - and costs -0.1 on top of the step's reward;
 a learner eliminated at the start of a step is not flagged.  Finished / truncated envs are re-dealt on their next step,
 as in GeneralsVecEnv.
+
+Buffers, reset / force_reset, numpy mode and the state methods are GymVecEnvBase's (_gym_base.py), shared with
+GeneralsVecEnv; this file holds the learner set, the two launches and the zero-copy slots of step().
 """
 import numpy as np
 
-from .env_state import EnvStateMixin
-from .vec_engine import VecEngine
+from ._gym_base import GymVecEnvBase
 from ._lib import check
 
 
-class GeneralsSelfPlayVecEnv(EnvStateMixin):
+class GeneralsSelfPlayVecEnv(GymVecEnvBase):
     """B boards with L learners each behind the (gymnasium-style) vector API:
     reset() -> (obs [B, L, 9, H, W], info);  step(actions [B, L]) -> (obs, reward [B, L], terminated [B], truncated [B], info).
-    copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
+    copy_envs / save_state / restore_state (_gym_base.py): clone, save and restore env states on the device."""
+    _STEP_FLAGS = ("invalid", "error", "alive")         # gvec_gym_step_players' last three outputs
+    _INFO_FLAGS = (("invalid", "invalid"), ("error", "error"), ("alive", "alive"))
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, learners=None, fog_of_war=True, max_turns=500,
                  seed=0, device=0, board_pool=1024, device_outputs=False, strategic_features=False, feature_cap=64):
@@ -39,65 +43,18 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
                              info["strategic_features"], float32 [B, L, 5, H, W]: features.strategic_features of the observation
                              they return (a step's obs_out slot included), distances capped at feature_cap.  One extra
                              launch per call."""
-        self._feat_cap, self._feat_bufs, self._feat_flip = self._feature_option(strategic_features, feature_cap, device_outputs), None, 0
-        import torch
-        if not torch.cuda.is_available():
-            from ._lib import GvecError
-            raise GvecError(-2, "GeneralsSelfPlayVecEnv needs a GPU: its observations, masks and rewards come from the HIP gym "
-                                "kernels (there is no host path)")
+        feat_cap = self._feature_option(strategic_features, feature_cap, device_outputs)
+        self._require_gpu()
         ids = list(range(max_players)) if learners is None else sorted({int(p) for p in learners})
         if not ids or ids[0] < 0 or ids[-1] >= max_players:
             raise ValueError(f"learners must be a non-empty set of player ids below max_players={max_players}: {learners}")
-        self._t = torch
-        self.num_envs = num_envs
-        self.board_width, self.board_height = board_width, board_height
-        self.board_size = board_width * board_height
-        self.max_players = max_players
         self.player_ids = ids
-        self.num_learners = L = len(ids)
+        self.num_learners = len(ids)
         self._bits = sum(1 << p for p in ids)
-        self.fog_of_war = fog_of_war
-        self.max_turns = max_turns
-        self.single_observation_shape = (9, board_height, board_width)
-        self.single_action_n = self.board_size * 5
-        self._seed = seed
-        self._episode = 0
-        self.engine = VecEngine(num_envs, board_width, board_height, max_players, fog_of_war=fog_of_war, device=device,
-                                auto_reset=True)
-        self._pool = board_pool
-        self.valid_actions_mask = None
-        self._obs_flip = 0
-        self.device_outputs = bool(device_outputs)
-        dev = torch.device("cuda", device)
-        self._dev = dev
-        self.engine.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        n, B = self.board_size, num_envs
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self._d_obs = [z((B, L, 9, board_height, board_width), torch.float32) for _ in range(2)]
-        self._d_mask = [z((B, L, n * 5), torch.uint8) for _ in range(2)]
-        self._d_reward, self._d_done, self._d_winner = z((B, L), torch.float64), z(B, torch.uint8), z(B, torch.int8)
-        self._d_turn = z(B, torch.int64)
-        # per-step outputs rotate through three buffer sets: what step k returns is overwritten by step k + 2
-        # (needs_reset: written by step k, read by step k + 1 as `resetting` and handed out as info["reset"])
-        self._d_step = [{"reward": z((B, L), torch.float64), "invalid": z((B, L), torch.bool), "error": z((B, L), torch.bool),
-                         "alive": z((B, L), torch.bool), "winner": z(B, torch.int8), "turn": z(B, torch.int64),
-                         "terminated": z(B, torch.bool), "truncated": z(B, torch.bool), "needs_reset": z(B, torch.bool)}
-                        for _ in range(3)]
-        self._step_no = 0
-        self._arg_cache = {}
-        self.last_actions = None
-        if not self.device_outputs:   # pinned landing buffers for the default (numpy) mode
-            pin = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=True)
-            self._h_obs = [pin((B, L, 9, board_height, board_width), torch.float32) for _ in range(2)]
-            self._h_mask = [pin((B, L, n * 5), torch.bool) for _ in range(2)]
+        super().__init__((len(ids),), feat_cap, num_envs, board_width, board_height, max_players, fog_of_war, max_turns, seed, device,
+                         board_pool, device_outputs)
 
     # ---- the device path ---------------------------------------------------------------------------------
-    def _reset_device(self):
-        self._d_turn.zero_()
-        for b in self._d_step:
-            b["needs_reset"].zero_()
-        return self._observe_info()
-
     def _learner_ids(self):
         return list(self.player_ids)
 
@@ -112,22 +69,6 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
         self.valid_actions_mask = mask.view(self._t.bool)
         return obs, self._add_features(obs, {"player_ids": list(self.player_ids), "valid_actions_mask": self.valid_actions_mask,
                                              "turn": self._d_turn.clone()})
-
-    def _step_args(self, k, flip):
-        """The pointer arguments of gvec_gym_step_players for step number k (mod 3) writing observation buffer `flip`."""
-        key = (k % 3, flip)
-        a = self._arg_cache.get(key)
-        if a is None:
-            cur, out = self._d_step[k % 3], self._d_step[(k + 1) % 3]
-            obs, mask = self._d_obs[flip], self._d_mask[flip]
-            ptrs = (cur["needs_reset"].data_ptr(), self._d_turn.data_ptr(), self.max_turns, obs.data_ptr(), mask.data_ptr(),
-                    out["reward"].data_ptr(), out["terminated"].data_ptr(), out["truncated"].data_ptr(), out["winner"].data_ptr(),
-                    out["needs_reset"].data_ptr(), out["turn"].data_ptr(), out["invalid"].data_ptr(), out["error"].data_ptr(),
-                    out["alive"].data_ptr())
-            info = {"turn": out["turn"], "valid_actions_mask": mask.view(self._t.bool), "invalid": out["invalid"], "error": out["error"],
-                    "alive": out["alive"], "winner": out["winner"], "reset": cur["needs_reset"]}
-            a = self._arg_cache[key] = (ptrs, obs, out, info)
-        return a
 
     def _slot_args(self, k, obs_out, mask_out):
         """_step_args for a step that writes its observation and mask into the caller's tensors (zero-copy slots)."""
@@ -146,13 +87,8 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
         return ptrs[:3] + (obs_out.data_ptr(), mask_out.data_ptr()) + ptrs[5:], obs, out, info
 
     def _step_device(self, actions, obs_out=None, mask_out=None):
-        t, e = self._t, self.engine
-        B, L = self.num_envs, self.num_learners
-        if not (isinstance(actions, t.Tensor) and actions.is_cuda and actions.dtype == t.int64 and actions.is_contiguous()
-                and actions.numel() == B * L):
-            if isinstance(actions, np.ndarray):
-                actions = t.from_numpy(np.ascontiguousarray(actions, np.int64))
-            actions = t.as_tensor(actions, dtype=t.int64).to(self._dev).reshape(B, L).contiguous()
+        e = self.engine
+        actions = self._as_actions(actions)
         k = self._step_no
         if obs_out is None and mask_out is None:
             self._obs_flip ^= 1
@@ -172,29 +108,7 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
         self.valid_actions_mask = info["valid_actions_mask"]
         return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
-    def _to_numpy(self, obs, info):
-        """The device outputs as numpy arrays (default mode): observation and mask land in pinned buffers that alternate,
-        so the arrays returned by step k stay intact until step k + 2."""
-        i = self._obs_flip
-        self._h_obs[i].copy_(obs, non_blocking=True)
-        self._h_mask[i].copy_(info["valid_actions_mask"], non_blocking=True)
-        out = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in info.items() if k != "valid_actions_mask"}
-        self._t.cuda.current_stream(self._dev).synchronize()
-        out["valid_actions_mask"] = self._h_mask[i].numpy()
-        self.valid_actions_mask = out["valid_actions_mask"]
-        return self._h_obs[i].numpy(), out
-
     # ---- gym API ------------------------------------------------------------------------------------
-    def reset(self, seed=None):
-        if seed is not None:
-            self._seed = seed
-        self.engine.reset_generated(self._seed * 1000003 + 17)
-        self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
-        self._pool_key = (self._pool, self._seed * 7919 + 5)
-        self._check_uniform_boards()
-        obs, info = self._reset_device()
-        return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
-
     def step(self, actions, obs_out=None, mask_out=None):
         """actions: [num_envs, num_learners] indices into Discrete(board_size * 5), column j for player_ids[j].
         obs_out / mask_out (device_outputs=True only, both or neither): contiguous CUDA tensors on the env's device - float32
@@ -208,24 +122,4 @@ class GeneralsSelfPlayVecEnv(EnvStateMixin):
             return self._step_device(actions, obs_out, mask_out)
         if self.device_outputs:
             return self._step_device(actions)
-        obs, reward, terminated, truncated, info = self._step_device(np.asarray(actions, np.int64))
-        obs, info = self._to_numpy(obs, info)
-        return obs, reward.cpu().numpy(), terminated.cpu().numpy(), truncated.cpu().numpy(), info
-
-    def force_reset(self, env_mask):
-        """Ends the running episode of the marked envs: they are re-dealt in the NEXT step, as if that step had been preceded
-        by terminated / truncated."""
-        t = self._t
-        if isinstance(env_mask, t.Tensor):
-            m = env_mask.to(device=self._dev, dtype=t.bool)
-        else:
-            m = t.as_tensor(np.asarray(env_mask, bool)).to(self._dev)
-        self.needs_reset_buffer().logical_or_(m)
-
-    def needs_reset_buffer(self):
-        """The bool[num_envs] CUDA tensor the NEXT step reads as `resetting` (written by the last step: terminated |
-        truncated)."""
-        return self._d_step[self._step_no % 3]["needs_reset"]
-
-    def close(self):
-        self.engine.close()
+        return self._step_to_numpy(*self._step_device(np.asarray(actions, np.int64)))

@@ -24,18 +24,22 @@ Deliberate differences (documented in DESIGN.md): opponents are by default the o
 full moves - or whatever the caller supplies per step (`step(actions, other_actions=...)`: an opponent
 policy, self-play; GeneralsEnv's `opponent_agent`); finished / truncated envs are re-dealt on their next step ("next-step" autoreset)
 because a vector env cannot wait for a per-env reset() call.
+
+Buffers, reset / force_reset, numpy mode and the state methods are GymVecEnvBase's (_gym_base.py), shared with
+GeneralsSelfPlayVecEnv; this file holds the opponent options and the three ways a step is launched.
 """
 import numpy as np
 
-from .env_state import EnvStateMixin
-from .vec_engine import VecEngine
+from ._gym_base import GymVecEnvBase
 from ._lib import check
 
 
-class GeneralsVecEnv(EnvStateMixin):
+class GeneralsVecEnv(GymVecEnvBase):
     """B GeneralsEnv instances behind the (gymnasium-style) vector API:
     reset() -> (obs, info);  step(actions[B]) -> (obs, reward, terminated, truncated, info).
-    copy_envs / save_state / restore_state (env_state.py): clone, save and restore env states on the device."""
+    copy_envs / save_state / restore_state (_gym_base.py): clone, save and restore env states on the device."""
+    _STEP_FLAGS = ("played", "invalid", "error")        # gvec_gym_step's last three outputs
+    _INFO_FLAGS = (("invalid_action", "invalid"), ("error", "error"))
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, fog_of_war=True, max_turns=500,
                  seed=0, device=0, board_pool=1024, device_outputs=False, opponent="random", opponent_random_permille=0,
@@ -53,107 +57,35 @@ class GeneralsVecEnv(EnvStateMixin):
         strategic_features=True  (needs device_outputs=True) reset / step / copy_envs / restore_state add
                              info["strategic_features"], float32 [B, 5, H, W]: features.strategic_features of the observation
                              they return, distances capped at feature_cap.  One extra launch per call."""
-        self._feat_cap, self._feat_bufs, self._feat_flip = self._feature_option(strategic_features, feature_cap, device_outputs), None, 0
+        feat_cap = self._feature_option(strategic_features, feature_cap, device_outputs)
         if opponent not in ("random", "bot"):
             raise ValueError(f"opponent must be 'random' or 'bot', not {opponent!r}")
         if not 0 <= int(opponent_random_permille) <= 1000:
             raise ValueError("opponent_random_permille must be in [0, 1000]")
-        import torch
-        if not torch.cuda.is_available():
-            from ._lib import GvecError
-            raise GvecError(-2, "GeneralsVecEnv needs a GPU: its observations, masks and rewards come from the HIP gym kernels "
-                                "(there is no host path)")
-        self._t = torch
-        self.num_envs = num_envs
-        self.board_width, self.board_height = board_width, board_height
-        self.board_size = board_width * board_height
-        self.max_players = max_players
-        self.fog_of_war = fog_of_war
-        self.max_turns = max_turns
+        self._require_gpu()
+        super().__init__((), feat_cap, num_envs, board_width, board_height, max_players, fog_of_war, max_turns, seed, device,
+                         board_pool, device_outputs)
         self.player_id = 0  # "RL_Agent" joins first (generals_env.py:163-169)
-        self.single_observation_shape = (9, board_height, board_width)   # spaces.Box(0, 1, (9,H,W), float32) :111-116
-        self.single_action_n = self.board_size * 5                        # spaces.Discrete(board_size*5)      :118-120
-        self._seed = seed
-        self._episode = 0
-        self.engine = VecEngine(num_envs, board_width, board_height, max_players, fog_of_war=fog_of_war, device=device,
-                                auto_reset=True)
-        self._pool = board_pool
         self.opponent, self.opponent_random_permille = opponent, int(opponent_random_permille)
-        self.valid_actions_mask = None
-        self._obs_flip = 0
-        self.device_outputs = bool(device_outputs)
-        dev = torch.device("cuda", device)
-        self._dev = dev
-        self.engine.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        n = self.board_size
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self._d_obs = [z((num_envs, 9, board_height, board_width), torch.float32) for _ in range(2)]
-        self._d_mask = [z((num_envs, n * 5), torch.uint8) for _ in range(2)]
-        self._d_reward, self._d_done, self._d_winner = z(num_envs, torch.float64), z(num_envs, torch.uint8), z(num_envs, torch.int8)
-        self._d_turn = z(num_envs, torch.int64)
-        # per-step outputs rotate through three buffer sets: what step k returns is overwritten by step k + 2
-        # (needs_reset: written by step k, read by step k + 1 as `resetting` and handed out as info["reset"])
-        self._d_step = [{"reward": z(num_envs, torch.float64), "winner": z(num_envs, torch.int8), "turn": z(num_envs, torch.int64),
-                         "terminated": z(num_envs, torch.bool), "truncated": z(num_envs, torch.bool), "needs_reset": z(num_envs, torch.bool),
-                         "played": z(num_envs, torch.bool), "invalid": z(num_envs, torch.bool), "error": z(num_envs, torch.bool)}
-                        for _ in range(3)]
-        self._step_no = 0
-        self._arg_cache = {}
-        self._acts, self.last_actions = None, None
-        if not self.device_outputs:   # pinned landing buffers for the default (numpy) mode
-            pin = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=True)
-            self._h_obs = [pin((num_envs, 9, board_height, board_width), torch.float32) for _ in range(2)]
-            self._h_mask = [pin((num_envs, n * 5), torch.bool) for _ in range(2)]
+        self._acts = None
 
     # ---- the device path ---------------------------------------------------------------------------------
-    def _gym_observe(self):
+    def _observe_info(self):
         self._obs_flip ^= 1
         obs, mask = self._d_obs[self._obs_flip], self._d_mask[self._obs_flip]
         e = self.engine
         check(e.L.gvec_gym_observe(e.h, self.player_id, self._d_turn.data_ptr(), self.max_turns, obs.data_ptr(), mask.data_ptr(),
                                    self._d_reward.data_ptr(), self._d_done.data_ptr(), self._d_winner.data_ptr()), "gvec_gym_observe")
         self.valid_actions_mask = mask.view(self._t.bool)
-        return obs
-
-    def _reset_device(self):
-        self._d_turn.zero_()
-        for b in self._d_step:
-            b["needs_reset"].zero_()
-        return self._observe_info()        # also stores the stats the first step's reward is measured against
-
-    def _observe_info(self):
-        obs = self._gym_observe()
         return obs, self._add_features(obs, {"player_id": self.player_id, "valid_actions_mask": self.valid_actions_mask,
                                              "turn": self._d_turn.clone()})
 
     def _learner_ids(self):
         return [self.player_id]
 
-    def _step_args(self, k, flip):
-        """The pointer arguments of gvec_gym_step for step number k (mod 3) writing observation buffer `flip`: computed once
-        per combination - at 4,096 envs the launch itself takes ~20 us and seventeen data_ptr() calls would add half of that."""
-        key = (k % 3, flip)
-        a = self._arg_cache.get(key)
-        if a is None:
-            cur, out = self._d_step[k % 3], self._d_step[(k + 1) % 3]
-            obs, mask = self._d_obs[flip], self._d_mask[flip]
-            ptrs = (cur["needs_reset"].data_ptr(), self._d_turn.data_ptr(), self.max_turns, obs.data_ptr(), mask.data_ptr(),
-                    out["reward"].data_ptr(), out["terminated"].data_ptr(), out["truncated"].data_ptr(), out["winner"].data_ptr(),
-                    out["needs_reset"].data_ptr(), out["turn"].data_ptr(), out["played"].data_ptr(), out["invalid"].data_ptr(),
-                    out["error"].data_ptr())
-            info = {"turn": out["turn"], "valid_actions_mask": mask.view(self._t.bool), "invalid_action": out["invalid"], "error": out["error"],
-                    "winner": out["winner"], "reset": cur["needs_reset"]}
-            a = self._arg_cache[key] = (ptrs, obs, out, info)
-        return a
-
     def _step_device(self, actions):
-        t, e = self._t, self.engine
-        if not (isinstance(actions, t.Tensor) and actions.is_cuda and actions.dtype == t.int64 and actions.is_contiguous()
-                and actions.numel() == self.num_envs):
-            if isinstance(actions, np.ndarray):
-                actions = t.from_numpy(np.ascontiguousarray(actions, np.int64))
-            actions = t.as_tensor(actions, dtype=t.int64).to(self._dev).reshape(self.num_envs).contiguous()
-        self.last_actions = actions        # the tensor the launch reads (kept alive; a collector records it)
+        e = self.engine
+        self.last_actions = actions = self._as_actions(actions)        # the tensor the launch reads (kept alive; a collector records it)
         k = self._step_no
         self._step_no += 1
         self._obs_flip ^= 1
@@ -166,14 +98,18 @@ class GeneralsVecEnv(EnvStateMixin):
         self.valid_actions_mask = info["valid_actions_mask"]
         return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
+    def _other_moves(self):
+        """The [num_envs, max_players, 8] uint8 buffer of the composed step's gvec_action moves, made on first use."""
+        if self._acts is None:
+            self._acts = self._t.zeros((self.num_envs, self.max_players, 8), dtype=self._t.uint8, device=self._dev)
+        return self._acts
+
     def _step_bot(self, actions):
         """The other seats played by the scripted opponent: gvec_bot_actions writes their moves into the step's action buffer
         on the device (seeded like the random agent's draw of a one-launch step), then the composed step runs on it."""
-        B, P = self.num_envs, self.max_players
-        if self._acts is None:
-            self._acts = self._t.zeros((B, P, 8), dtype=self._t.uint8, device=self._dev)
-        others = ((1 << P) - 1) & ~(1 << self.player_id)
-        self.engine.bot_actions_device(others, self._seed + 1000 * self._episode + 1, self.opponent_random_permille, self._acts.data_ptr())
+        others = ((1 << self.max_players) - 1) & ~(1 << self.player_id)
+        self.engine.bot_actions_device(others, self._seed + 1000 * self._episode + 1, self.opponent_random_permille,
+                                       self._other_moves().data_ptr())
         self._episode += 1
         return self._step_composed(actions, None)
 
@@ -185,17 +121,12 @@ class GeneralsVecEnv(EnvStateMixin):
         which together equal gvec_gym_step output for output when `others` are the agent's moves
         (tests/test_vector_env.py::test_gym_step_equals_the_four_call_composition)."""
         t, e, B, P = self._t, self.engine, self.num_envs, self.max_players
-        if not (isinstance(actions, t.Tensor) and actions.is_cuda and actions.dtype == t.int64 and actions.is_contiguous() and actions.numel() == B):
-            if isinstance(actions, np.ndarray):
-                actions = t.from_numpy(np.ascontiguousarray(actions, np.int64))
-            actions = t.as_tensor(actions, dtype=t.int64).to(self._dev).reshape(B).contiguous()
-        if self._acts is None:
-            self._acts = t.zeros((B, P, 8), dtype=t.uint8, device=self._dev)
+        actions, acts = self._as_actions(actions), self._other_moves()
         if isinstance(others, np.ndarray):
             from .vec_engine import ACTION_DTYPE
             others = t.from_numpy(np.ascontiguousarray(others, ACTION_DTYPE).reshape(B, P).view(np.uint8).reshape(B, P, 8))
-        if others is not None:                                          # None: _acts already holds them (_step_bot)
-            self._acts.copy_(others.reshape(B, P, 8))
+        if others is not None:                                          # None: acts already holds them (_step_bot)
+            acts.copy_(others.reshape(B, P, 8))
         self.last_actions = actions
         k = self._step_no
         self._step_no += 1
@@ -204,9 +135,9 @@ class GeneralsVecEnv(EnvStateMixin):
         _, obs, out, info = self._step_args(k, self._obs_flip)
         cur, mask = self._d_step[k % 3], self._d_mask[self._obs_flip]
         L, pl = e.L, self.player_id
-        check(L.gvec_gym_actions(e.h, pl, actions.data_ptr(), prev_mask.data_ptr(), cur["needs_reset"].data_ptr(), self._acts.data_ptr(),
+        check(L.gvec_gym_actions(e.h, pl, actions.data_ptr(), prev_mask.data_ptr(), cur["needs_reset"].data_ptr(), acts.data_ptr(),
                                  out["played"].data_ptr(), out["invalid"].data_ptr(), out["error"].data_ptr()), "gvec_gym_actions")
-        e.step_device(self._acts.data_ptr())
+        e.step_device(acts.data_ptr())
         check(L.gvec_gym_finish_step(e.h, pl, self._d_turn.data_ptr(), self.max_turns, cur["needs_reset"].data_ptr(), out["played"].data_ptr(),
                                      obs.data_ptr(), mask.data_ptr(), out["reward"].data_ptr(), out["terminated"].data_ptr(),
                                      out["truncated"].data_ptr(), out["winner"].data_ptr(), out["needs_reset"].data_ptr(),
@@ -214,29 +145,7 @@ class GeneralsVecEnv(EnvStateMixin):
         self.valid_actions_mask = info["valid_actions_mask"]
         return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
 
-    def _to_numpy(self, obs, info):
-        """The device path's outputs as numpy arrays (default mode): observation and mask land in pinned buffers that
-        alternate, so the arrays returned by step k stay intact until step k + 2."""
-        i = self._obs_flip
-        self._h_obs[i].copy_(obs, non_blocking=True)
-        self._h_mask[i].copy_(info["valid_actions_mask"], non_blocking=True)
-        out = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in info.items() if k != "valid_actions_mask"}
-        self._t.cuda.current_stream(self._dev).synchronize()
-        out["valid_actions_mask"] = self._h_mask[i].numpy()
-        self.valid_actions_mask = out["valid_actions_mask"]
-        return self._h_obs[i].numpy(), out
-
     # ---- gym API ------------------------------------------------------------------------------------
-    def reset(self, seed=None):
-        if seed is not None:
-            self._seed = seed
-        self.engine.reset_generated(self._seed * 1000003 + 17)
-        self.engine.build_board_pool(self._pool, self._seed * 7919 + 5)
-        self._pool_key = (self._pool, self._seed * 7919 + 5)
-        self._check_uniform_boards()
-        obs, info = self._reset_device()
-        return (obs, info) if self.device_outputs else self._to_numpy(obs, info)
-
     def step(self, actions, other_actions=None):
         """other_actions: None = the other players are the env's opponent (the on-device random agent in ONE launch, or the
         scripted opponent with opponent="bot"); else their moves for this step ([num_envs][max_players] gvec_action, see
@@ -247,28 +156,7 @@ class GeneralsVecEnv(EnvStateMixin):
             run = self._step_bot if self.opponent == "bot" else self._step_device
         if self.device_outputs:
             return run(actions)
-        obs, reward, terminated, truncated, info = run(np.asarray(actions, np.int64))
-        obs, info = self._to_numpy(obs, info)
-        return obs, reward.cpu().numpy(), terminated.cpu().numpy(), truncated.cpu().numpy(), info
-
-    def force_reset(self, env_mask):
-        """Ends the running episode of the marked envs: they are re-dealt in the NEXT step (GVEC_ACT_RESET_ENV semantics),
-        exactly as if that step had been preceded by terminated / truncated.  How a collector cuts an episode at its own
-        length limit (ParallelEnvPool.max_steps_per_episode, vector_env.py:177) without a per-env reset() call."""
-        t = self._t
-        if isinstance(env_mask, t.Tensor):
-            m = env_mask.to(device=self._dev, dtype=t.bool)        # a CUDA mask stays on the device: no synchronisation
-        else:
-            m = t.as_tensor(np.asarray(env_mask, bool)).to(self._dev)
-        self.needs_reset_buffer().logical_or_(m)
-
-    def needs_reset_buffer(self):
-        """The bool[num_envs] CUDA tensor the NEXT step reads as `resetting` (written by the last step: terminated |
-        truncated).  A device-side collector raises entries of it to cut episodes (gvec_pool_collect)."""
-        return self._d_step[self._step_no % 3]["needs_reset"]
-
-    def close(self):
-        self.engine.close()
+        return self._step_to_numpy(*run(np.asarray(actions, np.int64)))
 
 
 # --------------------------------------------------------------------------------------------------------------------

@@ -628,3 +628,112 @@ def test_single_env_facade_plays_an_opponent_agent(capsys):
     text = capsys.readouterr().out.splitlines()
     assert text[1].startswith("Turn ") and text[2] == "=" * (W * 4 + 1) and len(text) == Hh + 4 and all(len(r) == W * 4 + 1 for r in text[3:3 + Hh])
     env.close()
+
+
+# ---- the env's surface on every step path: shapes, dtypes, info keys, both modes, the buffer reuse rule ---------------
+STEP_INFO_KEYS = ["turn", "valid_actions_mask", "invalid_action", "error", "winner", "reset"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["random", "bot", "other_actions"])
+def test_vector_env_shapes_modes_buffers_and_force_reset(path):
+    """GeneralsVecEnv on its three step paths (the one-launch step, opponent="bot", step(..., other_actions=...)), numpy
+    mode against device mode: info keys, shapes and dtypes of everything returned, equal values at every step, force_reset
+    with a host and a device mask, and the reuse rule - what a call returns (observation AND mask) is intact after the next
+    call, a copy_envs between two steps counting as one."""
+    import torch
+    from generalsreinforcementlearning_amd.vec_engine import ACTION_DTYPE
+    from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
+    B, P, W, Hh = 32, 3, 9, 8
+    kw = dict(board_width=W, board_height=Hh, max_players=P, max_turns=15, seed=6, board_pool=16,
+              opponent="bot" if path == "bot" else "random")
+    a = GeneralsVecEnv(B, device_outputs=False, **kw)
+    d = GeneralsVecEnv(B, device_outputs=True, **kw)
+    others = (None, None)
+    if path == "other_actions":                                # all-zero moves (no GVEC_ACT_VALID): the other seats pass
+        others = (np.zeros((B, P), ACTION_DTYPE), torch.zeros((B, P, 8), dtype=torch.uint8, device="cuda"))
+    (oa, ia), (od, idd) = a.reset(), d.reset()
+    assert set(ia) == set(idd) == {"player_id", "valid_actions_mask", "turn"} and list(idd) == ["player_id", "valid_actions_mask", "turn"]
+    assert ia["player_id"] == idd["player_id"] == 0
+    assert isinstance(oa, np.ndarray) and oa.shape == (B, 9, Hh, W) and oa.dtype == np.float32
+    assert ia["valid_actions_mask"].shape == (B, W * Hh * 5) and ia["valid_actions_mask"].dtype == bool
+    assert ia["turn"].shape == (B,) and ia["turn"].dtype == np.int64 and not ia["turn"].any()
+    assert isinstance(od, torch.Tensor) and od.is_cuda and od.dtype == torch.float32 and idd["valid_actions_mask"].dtype == torch.bool
+    assert np.array_equal(oa, od.cpu().numpy()) and np.array_equal(ia["valid_actions_mask"], idd["valid_actions_mask"].cpu().numpy())
+
+    held = []                                                   # (what the last call returned, its copy then) - checked after the next call
+
+    def returned(*pairs):
+        for now, then in held:
+            assert (torch.equal(now, then) if isinstance(now, torch.Tensor) else np.array_equal(now, then)), "overwritten one call later"
+        held[:] = [(x, x.clone() if isinstance(x, torch.Tensor) else x.copy()) for x in pairs]
+
+    returned(oa, ia["valid_actions_mask"], od, idd["valid_actions_mask"])
+    rng = np.random.default_rng(0)
+    for k in range(30):
+        m = ia["valid_actions_mask"]
+        acts = np.array([rng.choice(np.flatnonzero(r)) if r.any() else 0 for r in m], np.int64)
+        if k % 7 == 3:
+            acts[:3] = [int(np.flatnonzero(~r)[0]) for r in m[:3]]                       # refused
+        if k == 10:
+            a.force_reset(np.arange(B) < 8)
+            d.force_reset(torch.arange(B, device="cuda") < 8)
+        if k == 20:                                             # an empty copy: one observe pass, one step of the rotation
+            (oa, ia), (od, idd) = a.copy_envs([], []), d.copy_envs([], [])
+            assert np.array_equal(oa, od.cpu().numpy()) and np.array_equal(ia["valid_actions_mask"], idd["valid_actions_mask"].cpu().numpy())
+            returned(oa, ia["valid_actions_mask"], od, idd["valid_actions_mask"])
+        ra = a.step(acts, other_actions=others[0])
+        rd = d.step(torch.from_numpy(acts).cuda(), other_actions=others[1])
+        obs, reward, term, trunc, info = ra
+        assert obs.shape == (B, 9, Hh, W) and obs.dtype == np.float32 and reward.shape == (B,) and reward.dtype == np.float64
+        assert term.shape == (B,) and trunc.shape == (B,) and term.dtype == bool and trunc.dtype == bool
+        assert info["valid_actions_mask"].shape == (B, W * Hh * 5) and info["valid_actions_mask"].dtype == bool
+        assert set(info) == set(STEP_INFO_KEYS) and list(rd[4]) == STEP_INFO_KEYS
+        for f, dt in (("turn", np.int64), ("invalid_action", bool), ("error", bool), ("winner", np.int8), ("reset", bool)):
+            assert info[f].shape == (B,) and info[f].dtype == dt, f
+        assert rd[0].dtype == torch.float32 and rd[1].dtype == torch.float64 and rd[2].dtype == torch.bool and rd[3].dtype == torch.bool
+        for x, y in zip(ra[:4], rd[:4]):
+            assert y.is_cuda and np.array_equal(x, y.cpu().numpy()), k
+        for f in info:
+            assert rd[4][f].is_cuda and np.array_equal(info[f], rd[4][f].cpu().numpy()), (k, f)
+        assert a.valid_actions_mask is info["valid_actions_mask"] and d.valid_actions_mask is rd[4]["valid_actions_mask"]
+        if k == 10:
+            assert info["reset"][:8].all() and (info["turn"][:8] == 0).all()
+        returned(obs, info["valid_actions_mask"], rd[0], rd[4]["valid_actions_mask"])
+        ia = info
+    a.close(); d.close()
+
+
+def test_vector_env_constructors_check_in_their_order_without_a_gpu():
+    """Option checks come before the GPU check (feature option first, then GeneralsVecEnv's opponent options); the self-play
+    env's `learners` check comes after it.  The GPU check is GvecError(-2) naming the class that was constructed."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    from generalsreinforcementlearning_amd import GvecError
+    from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
+    from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
+    with pytest.raises(ValueError, match="opponent must be 'random' or 'bot'"):
+        GeneralsVecEnv(4, opponent="minimax")
+    with pytest.raises(ValueError, match="opponent_random_permille must be in"):
+        GeneralsVecEnv(4, opponent_random_permille=1001)
+    for cls, bad in ((GeneralsVecEnv, {"opponent": "minimax"}), (GeneralsSelfPlayVecEnv, {"learners": [9]})):
+        with pytest.raises(ValueError, match="strategic_features=True needs device_outputs=True"):
+            cls(4, strategic_features=True, **bad)
+    for cls, extra in ((GeneralsVecEnv, {}), (GeneralsSelfPlayVecEnv, {}), (GeneralsSelfPlayVecEnv, {"learners": [9]})):
+        with pytest.raises(GvecError) as ei:
+            cls(4, board_width=8, board_height=8, **extra)
+        assert ei.value.code == -2 and f"{cls.__name__} needs a GPU" in str(ei.value)
+
+
+def test_the_two_vector_envs_share_one_base_class():
+    """What the two envs have in common is written once: each of these is defined by exactly one of the base class and the
+    two envs."""
+    from generalsreinforcementlearning_amd._gym_base import GymVecEnvBase
+    from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
+    from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
+    assert issubclass(GeneralsVecEnv, GymVecEnvBase) and issubclass(GeneralsSelfPlayVecEnv, GymVecEnvBase)
+    for name in ("reset", "force_reset", "needs_reset_buffer", "close", "_to_numpy", "_reset_device", "_step_args", "copy_envs",
+                 "save_state", "restore_state", "_add_features"):
+        owners = [c.__name__ for c in (GymVecEnvBase, GeneralsVecEnv, GeneralsSelfPlayVecEnv) if name in c.__dict__]
+        assert len(owners) == 1, (name, owners)
