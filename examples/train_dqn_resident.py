@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from generalsreinforcementlearning_amd.env_pool import DeviceReplayBuffer, ParallelVecEnvPool, PrioritizedDeviceReplayBuffer
+from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
+from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 

@@ -9,7 +9,7 @@ from ._lib import GvecError, lib, lib_path, load  # noqa: F401
 from .vec_engine import (ACTION_DTYPE, ACT_HALF, ACT_VALID, ERR_NAMES, TILE_CITY, TILE_GENERAL, TILE_MOUNTAIN,  # noqa: F401
                          TILE_NORMAL, VecEngine, make_actions, unpack_legal_bits)
 from .env_state import VecEnvState  # noqa: F401
-from .env_pool import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
+from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
 from .rollout import SelfPlayRolloutBuffer  # noqa: F401
 from .policy_head import MaskedCategoricalHead  # noqa: F401
 from .features import NUM_STRATEGIC_FEATURES, STRATEGIC_FEATURE_NAMES, strategic_features  # noqa: F401

@@ -1,4 +1,4 @@
-"""Uniform draws without replacement on the device, shared by the replay memories (env_pool.DeviceReplayBuffer,
+"""Uniform draws without replacement on the device, shared by the replay memories (replay.DeviceReplayBuffer,
 experience.RecordReplayRing): `random.sample(range(size), k)`'s contract - k distinct values, ValueError when k > size."""
 
 

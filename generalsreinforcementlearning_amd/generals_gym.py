@@ -10,7 +10,8 @@ all workers as one vector env: it asks the factory for worker 0's env, reads the
 a GeneralsVecEnv of `num_envs` boards with that configuration (one HIP launch per vector step instead of one gRPC
 session per worker).  Code that wants one policy call per vector step uses env_pool.ParallelVecEnvPool directly.
 """
-from .env_pool import ParallelVecEnvPool, ReplayBuffer
+from .env_pool import ParallelVecEnvPool
+from .replay import ReplayBuffer
 from .vector_env import GeneralsEnv, GeneralsVecEnv
 
 __all__ = ["GeneralsEnv", "ParallelEnvPool", "ReplayBuffer"]

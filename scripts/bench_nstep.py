@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from generalsreinforcementlearning_amd._lib import CollectArgs, load
-from generalsreinforcementlearning_amd.env_pool import DeviceReplayBuffer, ParallelVecEnvPool
+from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
+from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 ap = argparse.ArgumentParser()

@@ -10,7 +10,8 @@ import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from generalsreinforcementlearning_amd.env_pool import DeviceReplayBuffer, ParallelVecEnvPool, PrioritizedDeviceReplayBuffer
+from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
+from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 ap = argparse.ArgumentParser()

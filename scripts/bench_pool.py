@@ -6,7 +6,8 @@ import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool, ReplayBuffer, DeviceReplayBuffer
+from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
+from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, ReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
@@ -44,7 +45,7 @@ t0 = time.perf_counter(); pool.collect(n); torch.cuda.synchronize(); dt = time.p
 out["resident"] = {"ms_per_vector_step": dt / n * 1e3, "transitions_per_s": B * n / dt, "ring_capacity": cap,
                    "ring_bytes_per_transition": 2 * obs_bytes + 17}
 # the same with a policy that costs nothing: the env step + the collection alone
-fixed = device_policy(pool._state, pool._mask, None, pool._generator)
+fixed = device_policy(pool._state, pool._mask, None, pool._dc.generator)
 pool.action_fn = fixed_policy
 pool.collect(20); torch.cuda.synchronize()
 t0 = time.perf_counter(); pool.collect(n); torch.cuda.synchronize(); dt = time.perf_counter() - t0

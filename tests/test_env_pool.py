@@ -1,9 +1,11 @@
 """ParallelVecEnvPool / ReplayBuffer against what the REFERENCE's own ParallelEnvPool / ReplayBuffer did
 with the same scripted environment (tests/golden/pool_fixtures.json, recorded by tests/golden/make_pool_fixtures.py from
 python/generals_gym/vector_env.py + replay_buffer.py), then - under -m gpu - over the real GeneralsVecEnv."""
+import inspect
 import json
 import os
 import random
+import re
 import threading
 import time
 
@@ -463,3 +465,124 @@ def test_device_replay_buffer_draws_distinct_slots_from_a_big_ring():
     assert torch.equal(st[:, 0, 0, 0].long(), ac) and torch.equal(ns, st + 0.5)      # a row's fields belong together
     with pytest.raises(ValueError):
         buf.sample_indices(n + 1)
+
+
+# ---- replay.py holds the buffers, env_pool.py the pool and its two collectors ---------------------------------------------
+def test_the_buffer_classes_are_one_object_under_every_name():
+    import generalsreinforcementlearning_amd as pkg
+    from generalsreinforcementlearning_amd import env_pool, generals_gym, replay
+    for name in ("ReplayBuffer", "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer"):
+        assert getattr(env_pool, name) is getattr(replay, name)
+    assert pkg.DeviceReplayBuffer is replay.DeviceReplayBuffer and pkg.PrioritizedDeviceReplayBuffer is replay.PrioritizedDeviceReplayBuffer
+    assert generals_gym.ReplayBuffer is replay.ReplayBuffer is ReplayBuffer
+
+
+def test_device_ring_keyword_errors_come_before_any_device_work():
+    """ValueError, not whatever a machine without a GPU says when a tensor is put on one."""
+    from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+    for cls in (DeviceReplayBuffer, PrioritizedDeviceReplayBuffer):
+        for kw in (dict(capacity=0), dict(capacity=-3), dict(capacity=8, n_step=0), dict(capacity=8, n_step=2.5), dict(capacity=8, gamma=-0.1),
+                   dict(capacity=8, gamma=float("inf")), dict(capacity=8, gamma=float("nan"))):
+            with pytest.raises(ValueError):
+                cls(**kw)
+    for kw in (dict(alpha=-0.1), dict(beta=-1.0), dict(eps=0.0), dict(eps=float("nan"))):
+        with pytest.raises(ValueError):
+            PrioritizedDeviceReplayBuffer(8, **kw)
+
+
+def test_the_pool_module_leaves_the_ring_s_append_to_the_ring():
+    """What env_pool.py no longer spells out: the ring's lock, its counters' copy, its links, the launches that follow
+    gvec_pool_collect, and which kind of buffer it is talking to - one isinstance picks the collector, and past the
+    constructor no method of the pool asks which of the two it has."""
+    from generalsreinforcementlearning_amd import env_pool
+    src = inspect.getsource(env_pool)
+    for word in ("_guard", "_before", "ring_succ", "gvec_per_push", "gvec_nstep_link", "_prioritized"):
+        assert word not in src, word
+    assert len(re.findall(r"isinstance\([^)]*ReplayBuffer", src)) == 1
+    pool = env_pool.ParallelVecEnvPool
+    methods = [m for n, m in vars(pool).items() if n != "__init__" and (inspect.isfunction(m) or isinstance(m, property))]
+    assert len(methods) > 8
+    for m in methods:
+        body = inspect.getsource(m.fget if isinstance(m, property) else m)
+        assert "on_device" not in body and "_dc" not in body, body.splitlines()[0]
+    for c in (env_pool._HostCollector, env_pool._DeviceCollector):
+        assert all(callable(getattr(c, n)) for n in ("restart", "step", "pop_results")) and isinstance(c.episodes, property)
+
+
+class _RecordingLib:
+    """The loaded library with the names of a collector step's launches written down as they are called."""
+    def __init__(self, real, calls):
+        self._real, self._calls = real, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        if not name.startswith(("gvec_pool_collect", "gvec_nstep_", "gvec_per_push")):
+            return fn
+
+        def recorded(*args):
+            self._calls.append(name)
+            return fn(*args)
+        return recorded
+
+
+def _tiny_device_pool(buf, policy=_first_valid_device):
+    from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
+    return ParallelVecEnvPool(8, lambda n: GeneralsVecEnv(n, board_width=6, board_height=6, max_players=2, seed=2, board_pool=8, device_outputs=True),
+                              policy, buf, max_steps_per_episode=3, batched_actions=True)
+
+
+@pytest.mark.gpu
+def test_launches_of_a_collector_step_per_kind_of_ring(monkeypatch):
+    """Per vector step, in this order: gvec_pool_collect, gvec_nstep_link where n_step > 1, gvec_per_push where there is a
+    tree - and nothing else of theirs; the four rings then hold the same number of rows."""
+    import torch
+    from generalsreinforcementlearning_amd import _lib
+    from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+    calls = []
+    monkeypatch.setattr(_lib, "_LIB", _RecordingLib(_lib.load(), calls))
+    pushed = []
+    for cls, n_step, want in ((DeviceReplayBuffer, 1, ["gvec_pool_collect"]), (DeviceReplayBuffer, 3, ["gvec_pool_collect", "gvec_nstep_link"]),
+                              (PrioritizedDeviceReplayBuffer, 1, ["gvec_pool_collect", "gvec_per_push"]),
+                              (PrioritizedDeviceReplayBuffer, 3, ["gvec_pool_collect", "gvec_nstep_link", "gvec_per_push"])):
+        del calls[:]
+        buf = cls(64, n_step=n_step)
+        pool = _tiny_device_pool(buf)
+        pool.collect(10)
+        torch.cuda.synchronize()
+        assert calls == ["gvec_pool_collect_scratch_bytes"] + want * 10, (cls.__name__, n_step, calls)
+        assert len(buf) == 64
+        pushed.append(buf.total_pushed)
+        pool._env.close()
+    assert len(set(pushed)) == 1 and pushed[0] >= 64
+
+
+@pytest.mark.gpu
+def test_device_pool_reads_action_fn_every_step_and_keeps_its_count_over_a_new_env():
+    import torch
+    from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer
+    answered = []
+
+    def last_valid(states, masks, workers, generator):
+        m = masks.to(torch.uint8)
+        answered.append((m.shape[1] - 1 - torch.argmax(m.flip(1), dim=1), torch.argmax(m, dim=1)))
+        return answered[-1][0]
+
+    buf = DeviceReplayBuffer(64)
+    pool = _tiny_device_pool(buf)
+    pool.collect(3)                                           # every worker's first episode is cut at 3 steps
+    pool.action_fn = last_valid                               # swapped after construction: the next step asks the new one
+    pool.collect(2)
+    assert len(answered) == 2 and torch.equal(pool._env.last_actions, answered[-1][0])
+    assert not torch.equal(answered[-1][0], answered[-1][1])  # ... and the first policy would have answered otherwise
+    before = pool.total_episodes
+    assert before == 8 == int(pool._dc.counters[1])           # counted, logged, not yet read
+    old = pool._env
+    pool._env = pool._create_env(old_env=old)                 # what _worker_loop does after a step that raised
+    pool._begin()
+    assert pool._env is not old and pool._dc.env is pool._env and pool.total_episodes == before
+    assert pool._dc.episode_length.tolist() == [0] * 8        # the episodes that were running are lost, like a failed worker's
+    pool.collect(3)
+    res = pool.pop_episode_results()
+    assert pool.total_episodes == len(res) == before + 8 and [w for _, _, w in res] == list(range(8)) * 2 and all(l == 3 for _, l, _ in res)
+    assert buf.total_pushed == 8 * (3 + 1 + 3) and pool.pop_episode_results() == []
+    pool._env.close()
