@@ -29,7 +29,8 @@
 // anywhere (HBM-roofline kernel).
 //
 // This file holds the PLAIN layout (`Board`: one register per plane, used by the conversion and experience
-// kernels) and everything both layouts share; the turn logic lives in gvec_packed.hpp (`PBoard`).
+// kernels) and everything both layouts share - the header record's unpack and pack, the army storage, the flat <-> tile domain crossings, the move-target planes, the list settlement and the
+// variant geometry; the turn logic lives in gvec_packed.hpp (`PBoard`).
 //
 // Every routine cites the Go function it reproduces (paths relative to
 // /root/reference/internal/game/).  Semantics are the plane re-statement derived in
@@ -151,6 +152,18 @@ struct Planes {
                        COUNT = 3 * MAXP + 13, MUTABLE = 2 * MAXP + 3, SHARED = 13 /* CHG .. OK[3] */;
 };
 
+// Geometry of a kernel variant whose plane stride is a compile-time constant.  ODD: the planes are 2*NSLOT-1 dwords long
+// (else 2*NSLOT).  GYM_STAGE_DW: the gym mask's LDS stage (5 bytes a tile, whole 16-byte chunks).
+template <int MAXP_, int NSLOT_, bool ODD_>
+struct VariantGeom {
+  static constexpr int MAXP = MAXP_, NSLOT = NSLOT_;
+  static constexpr bool ODD = ODD_;
+  static constexpr int FD = 2 * NSLOT - (ODD ? 1 : 0);
+  static constexpr int ROW_DW = (Planes<MAXP>::COUNT * FD + 3) / 4 * 4;
+  static constexpr int GYM_STAGE_DW = (NSLOT * 64 * 5 + 15) / 16 * 4;
+  static_assert(GYM_STAGE_DW >= NSLOT * 64, "the larger user of the gym step kernels' army shadow: the stage serves as both");
+};
+
 constexpr uint32_t KF_AGENT = 1u;      // sample actions on device instead of reading them
 constexpr uint32_t KF_EMIT = 2u;       // write legal-action masks
 constexpr uint32_t KF_AUTORESET = 4u;  // re-deal finished envs from the pool
@@ -259,6 +272,28 @@ __device__ __forceinline__ void army_store_wide(const int32_t (&army)[NSLOT], in
   for (int s = 0; s < NSLOT; ++s) w[64 * s + lane] = army[s];
 }
 
+// The two forms for any board type with army[] and hflags.  Whole 64-tile slots travel both ways (the padding beyond N
+// holds zeros).  The narrow block is read unconditionally (its loads need not wait for the header); a WIDE env - rare -
+// reads its escape block on top.  Needs hflags: call after load_hdr.
+template <typename BT>
+__device__ __forceinline__ void load_army(BT& b, const ArmyCRef& a) {
+  army_load_narrow(b.army, a.n);
+  if (b.hflags & HF_WIDE) army_load_wide(b.army, a.w);
+}
+// Chooses the form (and sets / clears HF_WIDE in hflags accordingly): call BEFORE store_hdr.  STAGED: the narrow block
+// leaves through the board's LDS stage (PBoard::store_army_narrow_staged).
+template <bool STAGED = false, typename BT>
+__device__ __forceinline__ void store_army(BT& b, const ArmyRef& a) {
+  if (army_fits_narrow(b.army)) {
+    b.hflags &= ~HF_WIDE;
+    if constexpr (STAGED) b.store_army_narrow_staged(a.n);
+    else army_store_narrow(b.army, a.n);
+  } else {
+    b.hflags |= HF_WIDE;
+    army_store_wide(b.army, a.w);
+  }
+}
+
 // ---- wave primitives --------------------------------------------------------------------
 // NOTE: ds_bpermute / DPP read 0 from lanes that are masked off in EXEC.  Every cross-lane
 // helper below must therefore be called under wave-uniform control flow only.
@@ -302,6 +337,23 @@ __device__ __forceinline__ bool wave_any(bool c) { return __builtin_amdgcn_ballo
 __device__ __forceinline__ uint32_t bperm(int byte_addr, uint32_t v) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
 }
+// ---- flat <-> tile domain ------------------------------------------------------------------
+// tile-domain all-ones / zero mask (gather_mask) or 0/1 (gather) of a flat plane: tile 64s+l is bit l&31 of dword
+// 2s + (l>>5) - of the wave (row 0 of a replicated PBoard plane), or of the row that starts at lane row_base (a packed one)
+__device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s, int row_base = 0) {
+  const int lane = lane_id();
+  return __builtin_amdgcn_sbfe((int32_t)bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
+}
+__device__ __forceinline__ uint32_t gather(uint32_t plane, int s, int row_base = 0) {
+  const int lane = lane_id();
+  return __builtin_amdgcn_ubfe(bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
+}
+// tile-domain predicates -> flat plane: the ballot of slot s is dwords 2s, 2s+1 of the bit string (lanes 2s, 2s+1: row 0)
+__device__ __forceinline__ void ballot_to_row0(uint32_t& plane, unsigned long long ballot, int s) {
+  plane = (uint32_t)gvec_llvm_writelane((int)(uint32_t)ballot, 2 * s, (int)plane);
+  plane = (uint32_t)gvec_llvm_writelane((int)(uint32_t)(ballot >> 32), 2 * s + 1, (int)plane);
+}
+
 // LDS traffic inside one wave needs no s_barrier (DS ops of a wave execute in order); this
 // only stops the compiler from reordering the accesses of different lanes.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -338,6 +390,70 @@ struct ColumnPatternTable {
   __device__ __forceinline__ uint32_t operator[](int w) const { return v[w]; }
 };
 __device__ const ColumnPatternTable kColumnPattern{};
+
+// ---- the header record in registers: for any board type with hv (lane k holds header dword k) and the wave-uniform
+// fields W, H, P, N, turn, recipW, alive, hflags --------------------------------------------------
+__device__ __forceinline__ void unpack_dims(uint32_t dims, int& W, int& H, int& P, uint32_t& hflags) {
+  W = (int)(dims & 0xFFu);
+  H = (int)((dims >> 8) & 0xFFu);
+  P = (int)((dims >> 16) & 0xFFu);
+  hflags = dims >> 24;
+}
+// the wave-uniform fields from the header words: word(k) is header dword k
+template <typename BT, typename F>
+__device__ __forceinline__ void unpack_hdr(BT& b, F&& word) {
+  b.turn = (int)word(H_TURN);
+  unpack_dims(word(H_DIMS), b.W, b.H, b.P, b.hflags);
+  b.N = b.W * b.H;
+  b.alive = word(H_STATUS) & 0xFFu;
+  b.recipW = (int)word(H_RECIPW);
+}
+template <typename BT>
+__device__ __forceinline__ void decode_hdr(BT& b) {
+  unpack_hdr(b, [&](int k) { return rdlane(b.hv, k); });
+}
+// v must be wave-uniform (every caller passes scalar values): one v_writelane, no compare / select
+template <typename BT>
+__device__ __forceinline__ void hdr_set(BT& b, int k, uint32_t v) { b.hv = (uint32_t)gvec_llvm_writelane((int)v, k, (int)b.hv); }
+template <typename BT>
+__device__ __forceinline__ uint32_t hdr_get(const BT& b, int k) { return rdlane(b.hv, k); }
+// RECIPW: H_RECIPW is written too (else it rides along in hv unchanged: a function of W); CLASS: the store's streaming
+// class (st_stream; 0 = a plain store)
+template <bool RECIPW, int CLASS, typename BT>
+__device__ __forceinline__ void pack_hdr(BT& b, uint32_t* hdr_env, uint32_t last_err) {
+  hdr_set(b, H_TURN, (uint32_t)b.turn);
+  hdr_set(b, H_DIMS, (uint32_t)b.W | ((uint32_t)b.H << 8) | ((uint32_t)b.P << 16) | (b.hflags << 24));
+  hdr_set(b, H_STATUS, b.alive | (last_err << 16));
+  if constexpr (RECIPW) hdr_set(b, H_RECIPW, (uint32_t)b.recipW);
+  if (lane_id() < HDR_DW) st_stream<CLASS>(hdr_env + lane_id(), b.hv);
+}
+
+// the player-independent half of MoveAction.Validate (core/action.go:58-64, :96-98) per direction,
+// rules/legal_moves.go:13-18 order: needs the geometry masks, the type planes and W.  On PBoard: bit for bit the stored
+// planes on every lane with col() < fd.  The lanes beyond hold zero in valid / ncol0 / ncolL (never loaded), so notm, ok[1]
+// and ok[3] are zero there; ok[0] and ok[2] may carry the neighbouring lane's bits into column fd, where every plane they
+// are ever ANDed with (own, lst, gt1: legal_planes) is zero.  Wave-uniform control flow only.
+template <typename BT>
+__device__ __forceinline__ void derive_targets(BT& b) {
+  const uint32_t notm = ~b.mtn & b.valid;
+  b.ok[0] = b.upW(notm);            // target (x, y-1)
+  b.ok[1] = b.dn1(notm) & b.ncolL;  // target (x+1, y)
+  b.ok[2] = b.dnW(notm);            // target (x, y+1)
+  b.ok[3] = b.up1(notm) & b.ncol0;  // target (x-1, y)
+}
+// OwnedTiles == board ownership for every player (no owned-but-unlisted tile, H6)
+template <typename BT>
+__device__ __forceinline__ bool lists_match(const BT& b) {
+  uint32_t d = 0u;
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(b.own) / sizeof(b.own[0])); ++k) d |= b.lst[k] ^ b.own[k];
+  return !wave_any(d != 0u);
+}
+// Sets HF_LDIFF to what the lists are now: call BEFORE store_hdr; the plane stores write the list planes accordingly.
+template <typename BT>
+__device__ __forceinline__ void settle_lists(BT& b) {
+  b.hflags = lists_match(b) ? (b.hflags & ~HF_LDIFF) : (b.hflags | HF_LDIFF);
+}
 
 // =========================================================================================
 // Board: the PLAIN register layout - one register per (plane kind, player); lane i holds dword i of the bit
@@ -377,15 +493,6 @@ struct Board {
     ncol0 = (lane_id() < 32) ? ncol0 : 0xFFFFFFFFu;                // lanes beyond the bit string hold no tiles: any value
     ncolL = (lane_id() < 32) ? ncolL : 0xFFFFFFFFu;                // would do, a fixed one keeps the stored planes canonical
   }
-  // the player-independent half of MoveAction.Validate (core/action.go:58-64, :96-98) per direction,
-  // rules/legal_moves.go:13-18 order: needs geometry() and the type planes
-  __device__ __forceinline__ void targets() {
-    const uint32_t notm = ~mtn & valid;
-    ok[0] = upW(notm);          // target (x, y-1)
-    ok[1] = dn1(notm) & ncolL;  // target (x+1, y)
-    ok[2] = dnW(notm);          // target (x, y+1)
-    ok[3] = up1(notm) & ncol0;  // target (x-1, y)
-  }
   // the header flags that are functions of the board, and "nothing is known" for the turn engine's bookkeeping
   // flags: wherever a board is imported or modified from outside
   __device__ __forceinline__ void static_flags() {
@@ -396,7 +503,7 @@ struct Board {
   __device__ __forceinline__ void refresh_gt1() {
     gt1 = 0u;
 #pragma unroll
-    for (int s = 0; s < NSLOT; ++s) scatter(gt1, __builtin_amdgcn_ballot_w64(army[s] > 1), s);
+    for (int s = 0; s < NSLOT; ++s) ballot_to_row0(gt1, __builtin_amdgcn_ballot_w64(army[s] > 1), s);
   }
 
   // ---- flat-string shifts: bit t of the result = bit (t -+ k) of m ---------------------------
@@ -413,28 +520,9 @@ struct Board {
   __device__ __forceinline__ void load_hdr(const uint32_t* hdr_env) {
     const int lane = lane_id();
     hv = (lane < HDR_DW) ? hdr_env[lane] : 0u;
-    turn = (int)rdlane(hv, H_TURN);
-    const uint32_t dims = rdlane(hv, H_DIMS);
-    W = (int)(dims & 0xFFu);
-    H = (int)((dims >> 8) & 0xFFu);
-    P = (int)((dims >> 16) & 0xFFu);
-    hflags = dims >> 24;
-    N = W * H;
-    alive = rdlane(hv, H_STATUS) & 0xFFu;
-    recipW = (int)rdlane(hv, H_RECIPW);
+    decode_hdr(*this);
   }
-  // v must be wave-uniform (every caller passes scalar values): one v_writelane, no compare / select
-  __device__ __forceinline__ void hdr_set(int k, uint32_t v) { hv = (uint32_t)gvec_llvm_writelane((int)v, k, (int)hv); }
-  __device__ __forceinline__ uint32_t hdr_get(int k) const { return rdlane(hv, k); }
-
-  __device__ __forceinline__ void store_hdr(uint32_t* hdr_env, uint32_t last_err) {
-    const int lane = lane_id();
-    hdr_set(H_TURN, (uint32_t)turn);
-    hdr_set(H_DIMS, (uint32_t)W | ((uint32_t)H << 8) | ((uint32_t)P << 16) | (hflags << 24));
-    hdr_set(H_STATUS, alive | (last_err << 16));
-    hdr_set(H_RECIPW, (uint32_t)recipW);
-    if (lane < HDR_DW) hdr_env[lane] = hv;
-  }
+  __device__ __forceinline__ void store_hdr(uint32_t* hdr_env, uint32_t last_err) { pack_hdr<true, 0>(*this, hdr_env, last_err); }
 
   __device__ __forceinline__ void load_planes(const uint32_t* rows_env, int fd) {
     const int lane = lane_id();
@@ -465,13 +553,6 @@ struct Board {
     for (int d = 0; d < 4; ++d) ok[d] = ld(PL::OK + d);
   }
 
-  // Sets HF_LDIFF to what the lists are: call BEFORE store_hdr (store_planes writes the list planes accordingly).
-  __device__ __forceinline__ void settle_lists() {
-    uint32_t d = 0u;
-#pragma unroll
-    for (int p = 0; p < MAXP; ++p) d |= lst[p] ^ own[p];
-    hflags = wave_any(d != 0u) ? (hflags | HF_LDIFF) : (hflags & ~HF_LDIFF);
-  }
   // The planes from GEN on change only when a board is imported or re-dealt (with_types).  all_lists: write the list
   // planes whatever the flag says (a record slab is complete on its own).
   __device__ __forceinline__ void store_planes(uint32_t* rows_env, int fd, int row_dw, bool with_types, bool all_lists = false) const {
@@ -499,41 +580,6 @@ struct Board {
       }
     }
     if (with_types && lane < row_dw - PL::COUNT * fd) rows_env[PL::COUNT * fd + lane] = 0u;  // the block's padding
-  }
-
-  // whole 64-tile slots travel both ways (the padding beyond N holds zeros).
-  // The narrow block is read unconditionally (its loads need not wait for the header); a WIDE env
-  // - rare - reads its escape block on top.  Needs hflags: call after load_hdr.
-  __device__ __forceinline__ void load_army(const ArmyCRef& a) {
-    army_load_narrow<NSLOT>(army, a.n);
-    if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
-  }
-  // Chooses the form (and sets / clears HF_WIDE in hflags accordingly): call BEFORE store_hdr.
-  __device__ __forceinline__ void store_army(const ArmyRef& a) {
-    if (army_fits_narrow<NSLOT>(army)) {
-      hflags &= ~HF_WIDE;
-      army_store_narrow<NSLOT>(army, a.n);
-    } else {
-      hflags |= HF_WIDE;
-      army_store_wide<NSLOT>(army, a.w);
-    }
-  }
-
-  // ---- flat <-> tile domain ------------------------------------------------------------------
-  // tile-domain all-ones / zero mask (gather_mask) or 0/1 (gather) of a flat plane: tile 64s+l is
-  // bit l&31 of dword 2s + (l>>5)
-  __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s) const {
-    const int lane = lane_id();
-    return __builtin_amdgcn_sbfe((int32_t)bperm(((lane >> 5) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
-  }
-  __device__ __forceinline__ uint32_t gather(uint32_t plane, int s) const {
-    const int lane = lane_id();
-    return __builtin_amdgcn_ubfe(bperm(((lane >> 5) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
-  }
-  // tile-domain predicates -> flat plane (the ballot of slot s is dwords 2s, 2s+1 of the bit string)
-  __device__ __forceinline__ void scatter(uint32_t& plane, unsigned long long ballot, int s) const {
-    plane = (uint32_t)gvec_llvm_writelane((int)(uint32_t)ballot, 2 * s, (int)plane);
-    plane = (uint32_t)gvec_llvm_writelane((int)(uint32_t)(ballot >> 32), 2 * s + 1, (int)plane);
   }
 
   // ---- internal/experience/rewards.go helpers ---------------------------------------------------

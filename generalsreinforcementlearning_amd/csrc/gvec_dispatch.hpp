@@ -1,5 +1,6 @@
 // gvec_dispatch.hpp — host side of the board-kernel units: the launch shape (one wavefront per board, WAVES_PER_BLOCK boards
-// per workgroup), the <MAXP, NSLOT> dispatch, and what their launchers share.  Nothing here is device code.
+// per workgroup), the <MAXP, NSLOT> dispatch, and what their launchers share.  The only device code is the launch shape's
+// other half: which wave of its block a kernel is, and which item it owns.
 #pragma once
 #include "gvec_launch.hpp"
 
@@ -21,6 +22,11 @@ static hipError_t dispatch(const Variant& v, F&& f) {
   return hipErrorInvalidValue;
 }
 
+// device side of launch_waves: this wave's index in its block, and the item it owns (wave-uniform) - none when it is not
+// below the launch's n (the spare waves of the last block), and the kernel leaves
+__device__ __forceinline__ int block_wave() { return (int)(threadIdx.x >> 6); }
+__device__ __forceinline__ int wave_item() { return uni((int)blockIdx.x * WAVES_PER_BLOCK + block_wave()); }
+
 static inline dim3 wave_grid(int n) { return dim3((unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)); }
 
 // kernel k with one wavefront per item, n items
@@ -34,9 +40,10 @@ static hipError_t launch_waves(void (*k)(P...), int n, hipStream_t s, const A&..
 // stride as a compile-time constant come in both: 1 for the odd form, 0 for the even one, -1 when a is neither of variant <P, S>
 template <int P, int S>
 static int plane_parity(const StepArgs& a) {
-  const bool odd = a.fd == 2 * S - 1;
-  if ((!odd && a.fd != 2 * S) || a.row_dw != (Planes<P>::COUNT * a.fd + 3) / 4 * 4) return -1;
-  return odd ? 1 : 0;
+  using Odd = VariantGeom<P, S, true>;
+  using Even = VariantGeom<P, S, false>;
+  if (a.fd == Odd::FD && a.row_dw == Odd::ROW_DW) return 1;
+  return (a.fd == Even::FD && a.row_dw == Even::ROW_DW) ? 0 : -1;
 }
 
 // env_key_of(base, env) = fmix32(base + env * C): a handle that is shard [env_base, env_base + B) of a larger batch

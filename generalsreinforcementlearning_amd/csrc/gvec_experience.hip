@@ -39,8 +39,8 @@ __device__ __forceinline__ void store_army_sat16(const int32_t (&army)[NSLOT], u
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void snapshot_kernel(ExperienceArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.num_envs) return;
   const int env = A.env_begin + i;
   B b;
@@ -126,8 +126,8 @@ __device__ __forceinline__ float compute_rewards(const Board<MAXP, NSLOT>& b, co
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rewards_kernel(ExperienceArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.num_envs) return;
   const int env = A.env_begin + i;
   B b;
@@ -162,8 +162,8 @@ struct RecordLayout {
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void experience_record_kernel(ExperienceArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.num_envs) return;
   const int env = A.env_begin + i;
   B b;
@@ -327,8 +327,8 @@ __device__ __forceinline__ void expand_tensor(float* out, const uint32_t* own_p,
 // dynamic LDS: per wave the record (record_dw dwords) + two fd-dword "anybody owns it" planes (prev, next)
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void expand_records_kernel(ExpandArgs A) {
   extern __shared__ uint32_t expand_lds[];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int i = wave_item();
   if (i >= A.n) return;
   const int mp = A.mp, fd = A.fd;
   uint32_t* rec = expand_lds + (size_t)wave * (A.record_dw + 2 * fd);
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void expand_records_kernel(Ex
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void observe_kernel(ExperienceArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
@@ -478,8 +478,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void observe_kernel(Experienc
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
-      const bool mine = b.gather(own_p, s) != 0u, owned = b.gather(own_any, s) != 0u, seen = b.gather(vis_p, s) != 0u;
-      const bool spec = b.gather(special, s) != 0u, mount = b.gather(b.mtn, s) != 0u;
+      const bool mine = gather(own_p, s) != 0u, owned = gather(own_any, s) != 0u, seen = gather(vis_p, s) != 0u;
+      const bool spec = gather(special, s) != 0u, mount = gather(b.mtn, s) != 0u;
       const bool visible = !fog_on || seen;  // :50
       const bool open = visible && !mount;   // mountains short-circuit (:68-71)
       float norm = (float)b.army[s] / 1000.0f;  // :82-85

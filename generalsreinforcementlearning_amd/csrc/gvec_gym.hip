@@ -23,8 +23,7 @@ namespace gvec {
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void setup_kernel(ImportArgs A) {
   using B = Turn<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6);
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int i = wave_item();
   if (i >= A.n) return;
   const int env = A.env_ids ? uni(A.env_ids[i]) : A.dst_begin + i;
   if (env < 0 || env >= A.dst_envs) return;  // reported by the import kernel
@@ -34,7 +33,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void setup_kernel(ImportArgs 
   if (!(b.hflags & HF_SETUP)) return;  // this env's input was rejected: left as it was
   b.hflags &= ~HF_SETUP;
   b.initial_setup();
-  b.settle_lists();
+  settle_lists(b);
   b.store_hdr(A.hdr + (size_t)env * HDR_DW, 0u);
   b.store_planes(A.rows + (size_t)env * A.row_dw, A.fd, A.row_dw, false);
 }
@@ -77,7 +76,7 @@ __device__ __forceinline__ uint32_t player_view(int pl, const uint32_t (&reg)[B:
   uint32_t out = 0u;
 #pragma unroll
   for (int k = 0; k < B::NR; ++k) {
-    const uint32_t g = bperm((((pl % B::PPR) * B::ROWL) + B::col()) << 2, reg[k]);
+    const uint32_t g = bperm(player_lane<B::ROWL>(pl, B::col()) << 2, reg[k]);
     out = (pl / B::PPR == k) ? g : out;
   }
   return out;
@@ -154,7 +153,7 @@ __device__ __forceinline__ uint32_t turn_tile_counts(const B& b) {
 #pragma unroll
   for (int k = 0; k < B::NR; ++k) {
     const uint32_t sc = row_scan_add<B::ROWL>((uint32_t)__builtin_popcount(b.lst[k]));
-    const uint32_t got = bperm((((lane % B::PPR) * B::ROWL) + B::ROWL - 1) << 2, sc);
+    const uint32_t got = row_result<B::ROWL>(sc, lane % B::PPR);
     tcl = (lane / B::PPR == k) ? got : tcl;
   }
   return tcl;
@@ -279,33 +278,23 @@ __device__ __forceinline__ GymMove gym_decode(const B& b, uint32_t src, long lon
   return mv;
 }
 
-// The two step kernels' geometry.  ODD: see step_kernel.
-template <int MAXP_, int NSLOT_, bool ODD>
-struct GymStepGeom {
-  static constexpr int MAXP = MAXP_, NSLOT = NSLOT_;
-  static constexpr int FD = 2 * NSLOT - (ODD ? 1 : 0);
-  static constexpr bool ODD_FD = ODD;
-  static constexpr int ROW_DW = (Planes<MAXP>::COUNT * FD + 3) / 4 * 4;
-  static constexpr int STAGE_DW = (NSLOT * 64 * 5 + 15) / 16 * 4;  // the gym mask's stage (5 bytes a tile) is the larger user of the army shadow
-  static_assert(STAGE_DW >= NSLOT * 64, "the stage also serves as the action phase's army shadow");
-  using B = Turn<MAXP, NSLOT>;
-};
-// env's board into registers; stage / scratch: this wave's STAGE_DW and ACT_SCRATCH_DW dwords of LDS
+// The two step kernels' geometry K is a VariantGeom (ODD: see step_kernel).
+// env's board into registers; stage / scratch: this wave's GYM_STAGE_DW and ACT_SCRATCH_DW dwords of LDS
 template <typename K>
-__device__ __forceinline__ ArmyRef gym_load_turn(typename K::B& b, const StepArgs& A, int env, int32_t* stage, uint32_t* scratch) {
+__device__ __forceinline__ ArmyRef gym_load_turn(Turn<K::MAXP, K::NSLOT>& b, const StepArgs& A, int env, int32_t* stage, uint32_t* scratch) {
   b.larmy = stage;
   b.lscr = scratch;
   const ArmyRef army_env = army_ref<K::NSLOT>(A.army16, A.army32, env);
-  load_turn<true, lean_half_last(K::NSLOT, K::ODD_FD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * K::ROW_DW, army_env, K::FD, A.zeros);
+  load_turn<true, lean_half_last(K::NSLOT, K::ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * K::ROW_DW, army_env, K::FD, A.zeros);
   b.small = !(b.hflags & HF_WIDE);
   return army_env;
 }
 // The turn (step_kernel's body): an env that is over or `rs` is re-dealt; every other one plays the on-device agent's moves
 // with the learners' lanes of the ActVec overwritten by learner_moves(av).  Then the state is stored.
 template <typename K, typename F>
-__device__ __forceinline__ void gym_play_turn(typename K::B& b, const StepArgs& A, int env, const ArmyRef& army_env, bool rs, F&& learner_moves) {
-  using B = typename K::B;
+__device__ __forceinline__ void gym_play_turn(Turn<K::MAXP, K::NSLOT>& b, const StepArgs& A, int env, const ArmyRef& army_env, bool rs, F&& learner_moves) {
   constexpr int MAXP = K::MAXP, NSLOT = K::NSLOT, FD = K::FD, ROW_DW = K::ROW_DW;
+  using B = Turn<MAXP, NSLOT>;
   uint32_t err = 0u;
   bool types_dirty = false;
   if ((b.hflags & HF_DONE) || rs) {
@@ -320,12 +309,12 @@ __device__ __forceinline__ void gym_play_turn(typename K::B& b, const StepArgs& 
     bool aborted;
     err = b.turn_step(av, A, aborted);
     b.refresh_gt1();
-    b.hdr_set(H_CNT_STEPS, b.hdr_get(H_CNT_STEPS) + 1u);
-    if (aborted) b.hdr_set(H_CNT_ABORT, b.hdr_get(H_CNT_ABORT) + 1u);
-    if (b.hflags & HF_DONE) b.hdr_set(H_CNT_DONE, b.hdr_get(H_CNT_DONE) + 1u);
+    hdr_set(b, H_CNT_STEPS, hdr_get(b, H_CNT_STEPS) + 1u);
+    if (aborted) hdr_set(b, H_CNT_ABORT, hdr_get(b, H_CNT_ABORT) + 1u);
+    if (b.hflags & HF_DONE) hdr_set(b, H_CNT_DONE, hdr_get(b, H_CNT_DONE) + 1u);
   }
-  b.store_army_staged(army_env);
-  b.settle_lists();
+  store_army<true>(b, army_env);
+  settle_lists(b);
   b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
   if (types_dirty) b.store_planes(A.rows + (size_t)env * ROW_DW, FD, ROW_DW, true);
   else b.store_planes_staged(A.rows + (size_t)env * ROW_DW, FD);
@@ -338,8 +327,7 @@ __device__ __forceinline__ void gym_play_turn(typename K::B& b, const StepArgs& 
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_kernel(GymArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6);
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
@@ -347,12 +335,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_kernel(GymAr
   uint32_t own_any, cnt[MAXP];
   board_totals<MAXP>(b, own_any, cnt);
   const GymMask m = gym_mask(b, v);
-  __shared__ uint32_t mask_stage[WAVES_PER_BLOCK][(NSLOT * 64 * 5 + 15) / 16 * 4];
+  __shared__ uint32_t mask_stage[WAVES_PER_BLOCK][VariantGeom<MAXP, NSLOT, false>::GYM_STAGE_DW];
   const bool flow = A.played != nullptr;
   const bool rs = flow && A.resetting[env] != 0, pl_ok = !flow || A.played[env] != 0;
   const int64_t turns = flow ? (rs ? 0 : A.turn_count[env] + (pl_ok ? 1 : 0)) : A.turn_count[env];
   gym_emit_player<NSLOT>(b, v, m, own_any, gym_turn_channel(turns, A.max_turns), A.obs, A.mask, (size_t)env,
-                         reinterpret_cast<uint8_t*>(mask_stage[wave]), A.stride);
+                         reinterpret_cast<uint8_t*>(mask_stage[block_wave()]), A.stride);
   const uint32_t tcl = pick<MAXP>(cnt, lane_id()), acl = army_counts<MAXP>(b);
   const GymFlowOut O{A.reward, A.done, A.winner, A.turn_io, A.turn_out, A.terminated, A.truncated, A.needs_reset};
   gym_bookkeeping<MAXP>(env, A.player, b.P, b.alive, (b.hflags & HF_DONE) != 0u, (int32_t)pick<MAXP>(cnt, A.player), (int32_t)rdlane(acl, A.player),
@@ -369,12 +357,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_kernel(GymAr
 // (73-80 VGPRs) gain on boards of up to 256 tiles and lose 8-15 % on every larger one.)
 template <int MAXP, int NSLOT, bool ODD>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) void gym_step_kernel(StepArgs A, GymStepArgs G) {
-  using K = GymStepGeom<MAXP, NSLOT, ODD>;
-  using B = typename K::B;
-  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][K::STAGE_DW];
+  using K = VariantGeom<MAXP, NSLOT, ODD>;
+  using B = Turn<MAXP, NSLOT>;
+  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][K::GYM_STAGE_DW];
   __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   const ArmyRef army_env = gym_load_turn<K>(b, A, env, army_shadow[wave], act_scratch[wave]);
@@ -418,8 +406,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) __attribute__((amdgpu_waves_p
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_players_kernel(GymArgs A, uint32_t learners) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
@@ -427,7 +415,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_players_kern
   uint32_t own_any, cnt[MAXP];
   board_totals<MAXP>(b, own_any, cnt);
   const uint32_t tcl = pick<MAXP>(cnt, lane), acl = army_counts<MAXP>(b);
-  __shared__ uint32_t mask_stage[WAVES_PER_BLOCK][(NSLOT * 64 * 5 + 15) / 16 * 4];
+  __shared__ uint32_t mask_stage[WAVES_PER_BLOCK][VariantGeom<MAXP, NSLOT, false>::GYM_STAGE_DW];
   const double tcn = gym_turn_channel(A.turn_count[env], A.max_turns);
   const bool over = (b.hflags & HF_DONE) != 0u;
   const int winner = gym_winner(over, b.P, b.alive);
@@ -464,12 +452,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void gym_observe_players_kern
 template <int MAXP, int NSLOT, bool ODD>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) __attribute__((amdgpu_waves_per_eu(GYM_PLAYERS_WAVES_OF(NSLOT), GYM_PLAYERS_WAVES_OF(NSLOT))))
 void gym_step_players_kernel(StepArgs A, GymPlayersArgs G) {
-  using K = GymStepGeom<MAXP, NSLOT, ODD>;
-  using B = typename K::B;
-  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][K::STAGE_DW];
+  using K = VariantGeom<MAXP, NSLOT, ODD>;
+  using B = Turn<MAXP, NSLOT>;
+  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][K::GYM_STAGE_DW];
   __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   const ArmyRef army_env = gym_load_turn<K>(b, A, env, army_shadow[wave], act_scratch[wave]);
@@ -553,7 +541,7 @@ __global__ void gym_actions_kernel(GymActArgs A) {
   const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (env >= A.num_envs) return;
   const uint32_t dims = A.hdr[(size_t)env * HDR_DW + H_DIMS];
-  const int w = (int)(dims & 0xFFu), h = (int)((dims >> 8) & 0xFFu);
+  const int w = (int)(dims & 0xFFu), h = (int)((dims >> 8) & 0xFFu);  // unpack_dims' W and H, spelled out: through it this kernel is scheduled differently
   const long long a = A.gym_actions[env];
   const long long n5 = 5ll * A.stride;
   const uint8_t* mask = A.mask + (size_t)env * 5 * (size_t)A.stride;

@@ -66,7 +66,7 @@ __device__ __forceinline__ void gym_emit(const BT& b, uint32_t seen, uint32_t ow
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
-      const uint32_t k0 = b.gather(m0, s), k1 = b.gather(m1, s), k2 = b.gather(m2, s), k3 = b.gather(m3, s), k4 = b.gather(many, s);
+      const uint32_t k0 = gather(m0, s), k1 = gather(m1, s), k2 = gather(m2, s), k3 = gather(m3, s), k4 = gather(many, s);
       if (t < stride) {
         uint8_t* mk = ms + t * 5;
         mk[0] = (uint8_t)k0;
@@ -150,9 +150,9 @@ __device__ __forceinline__ void gym_emit(const BT& b, uint32_t seen, uint32_t ow
   #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
-      const bool vis = b.gather(seen, s) != 0u, mine = b.gather(own_p, s) != 0u, owned = b.gather(own_any, s) != 0u;
-      const bool g = b.gather(b.gen, s) != 0u, c = b.gather(b.city, s) != 0u, mt = b.gather(b.mtn, s) != 0u;
-      const uint32_t k0 = b.gather(m0, s), k1 = b.gather(m1, s), k2 = b.gather(m2, s), k3 = b.gather(m3, s), k4 = b.gather(many, s);
+      const bool vis = gather(seen, s) != 0u, mine = gather(own_p, s) != 0u, owned = gather(own_any, s) != 0u;
+      const bool g = gather(b.gen, s) != 0u, c = gather(b.city, s) != 0u, mt = gather(b.mtn, s) != 0u;
+      const uint32_t k0 = gather(m0, s), k1 = gather(m1, s), k2 = gather(m2, s), k3 = gather(m3, s), k4 = gather(many, s);
       const int32_t army = vis ? b.army[s] : 0;                                    // hidden and fogged tiles: army 0
       // channel 2: np.log(army + 1) / 10.0 in float64, cast on store (:324-326)
       const float la = (army > 0) ? (float)(log((double)army + 1.0) / 10.0) : 0.0f;

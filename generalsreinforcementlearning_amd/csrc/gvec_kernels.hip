@@ -8,32 +8,31 @@ namespace gvec {
 
 // ONE engine turn per launch, straight-line (gvec_step; per-turn rollouts).  AGENT: actions are
 // sampled on device from the legal-move planes of the resident state.
+constexpr int waves_for_regs(int need) {  // the waves per SIMD that leave every wave `need` registers (allocated in eights)
+  const int alloc = (need + 7) / 8 * 8;
+  const int w = 512 / alloc;
+  return w > 8 ? 8 : (w < 2 ? 2 : w);
+}
 // Waves per SIMD asked of the register allocator: the board state a variant holds (planes, army
 // slots, mask planes) plus ~32 working registers.  <4,7> fits 64 registers = 8 waves/SIMD without a
 // spill, which is worth 7 % over 7 waves (one-process A/B): the turn is a long dependent chain of
 // short cross-lane operations, and the VALU only stays fed with every wave slot occupied.
-constexpr int step_waves(int maxp, int nslot) {
-  const int ppr = (nslot <= 7) ? 4 : 2;  // PBoard: players per plane register
-  const int nr = (maxp + ppr - 1) / ppr;
-  const int state = 3 * nr + 13 + nr + nslot + 4 * nr;  // packed planes, shared planes, rowbit, armies, mask planes
-  // 8 waves only where they fit with room to spare
-  const int need = state + (state + 32 <= 62 ? 32 : 40);
-  const int alloc = (need + 7) / 8 * 8;
-  const int w = 512 / alloc;
-  return w > 8 ? 8 : (w < 2 ? 2 : w);
+template <int MAXP, int NSLOT>
+constexpr int step_waves() {
+  const int state = Turn<MAXP, NSLOT>::STATE_REGS;
+  return waves_for_regs(state + (state + 32 <= 62 ? 32 : 40));  // 8 waves only where they fit with room to spare
 }
 
 // ODD: the planes are 2*NSLOT-1 dwords long (else 2*NSLOT): the plane stride is a compile-time
 // constant here, so every plane access is one instruction with an immediate offset.
 template <int MAXP, int NSLOT, bool AGENT, bool ODD>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, step_waves(MAXP, NSLOT)) void step_kernel(StepArgs A) {
-  constexpr int FD = 2 * NSLOT - (ODD ? 1 : 0);
-  constexpr int ROW_DW = (Planes<MAXP>::COUNT * FD + 3) / 4 * 4;
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (step_waves<MAXP, NSLOT>())) void step_kernel(StepArgs A) {
+  constexpr int FD = VariantGeom<MAXP, NSLOT, ODD>::FD, ROW_DW = VariantGeom<MAXP, NSLOT, ODD>::ROW_DW;
   __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];  // per wave: the action phase's army copy
   using B = Turn<MAXP, NSLOT>;
   __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   bool force_redeal = false;
   if constexpr (!AGENT) {
@@ -102,12 +101,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, step_waves(MAXP, NSLOT)) void
     err = b.turn_step(av, A, aborted);
     if (!(GVEC_PROFILE_SKIP & 32)) b.refresh_gt1();
     if (GVEC_PROFILE_DUP & 32) { b.opaque_v(); b.refresh_gt1(); }
-    b.hdr_set(H_CNT_STEPS, b.hdr_get(H_CNT_STEPS) + 1u);
-    if (aborted) b.hdr_set(H_CNT_ABORT, b.hdr_get(H_CNT_ABORT) + 1u);
-    if (b.hflags & HF_DONE) b.hdr_set(H_CNT_DONE, b.hdr_get(H_CNT_DONE) + 1u);
+    hdr_set(b, H_CNT_STEPS, hdr_get(b, H_CNT_STEPS) + 1u);
+    if (aborted) hdr_set(b, H_CNT_ABORT, hdr_get(b, H_CNT_ABORT) + 1u);
+    if (b.hflags & HF_DONE) hdr_set(b, H_CNT_DONE, hdr_get(b, H_CNT_DONE) + 1u);
   }
-  b.store_army_staged(army_env);  // picks the narrow / wide form: before the header, which records it
-  b.settle_lists();               // ... and so is whether the list planes are stored
+  store_army<true>(b, army_env);  // picks the narrow / wide form: before the header, which records it
+  settle_lists(b);                // ... and so is whether the list planes are stored
   b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
   if (types_dirty) b.store_planes(A.rows + (size_t)env * ROW_DW, FD, ROW_DW, true);
   else b.store_planes_staged(A.rows + (size_t)env * ROW_DW, FD);
@@ -121,24 +120,20 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, step_waves(MAXP, NSLOT)) void
 // Waves per SIMD to ask of the register allocator for the fused rollout kernel.  With no HBM traffic
 // inside the turn loop the kernel is latency / issue bound, and occupancy pays even at the price of
 // a few scratch spills; a spill inside the turn loop of the big variants costs far more than a wave.
-constexpr int rollout_waves(int maxp, int nslot) {
-  const int ppr = (nslot <= 7) ? 4 : 2;
-  const int nr = (maxp + ppr - 1) / ppr;
-  const int need = 3 * nr + 13 + nr + nslot + 4 * nr + (nslot >= 16 ? 100 : nslot >= 10 ? 68 : 44);
-  const int alloc = (need + 7) / 8 * 8;
-  const int w = 512 / alloc;
-  return w > 8 ? 8 : (w < 2 ? 2 : w);
+template <int MAXP, int NSLOT>
+constexpr int rollout_waves() {
+  return waves_for_regs(Turn<MAXP, NSLOT>::STATE_REGS + (NSLOT >= 16 ? 100 : NSLOT >= 10 ? 68 : 44));
 }
 
 // `turns` engine turns per launch with the board kept in registers / LDS (fused rollouts; always
 // with the on-device agent)
 template <int MAXP, int NSLOT>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rollout_waves(MAXP, NSLOT)) void rollout_kernel(StepArgs A) {
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>())) void rollout_kernel(StepArgs A) {
   __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
   using B = Turn<MAXP, NSLOT>;
   __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   b.larmy = army_shadow[wave];
@@ -174,11 +169,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rollout_waves(MAXP, NSLOT)) v
     err = 0u;
     ++k;
   }
-  b.hdr_set(H_CNT_STEPS, b.hdr_get(H_CNT_STEPS) + n_steps);
-  b.hdr_set(H_CNT_ABORT, b.hdr_get(H_CNT_ABORT) + n_abort);
-  b.hdr_set(H_CNT_DONE, b.hdr_get(H_CNT_DONE) + n_done);
-  b.store_army(army_env);
-  b.settle_lists();
+  hdr_set(b, H_CNT_STEPS, hdr_get(b, H_CNT_STEPS) + n_steps);
+  hdr_set(b, H_CNT_ABORT, hdr_get(b, H_CNT_ABORT) + n_abort);
+  hdr_set(b, H_CNT_DONE, hdr_get(b, H_CNT_DONE) + n_done);
+  store_army(b, army_env);
+  settle_lists(b);
   b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
   b.store_planes(A.rows + (size_t)env * A.row_dw, A.fd, A.row_dw, true);
   if (A.err && lane == 0) A.err[env] = (int32_t)err;
@@ -190,8 +185,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rollout_waves(MAXP, NSLOT)) v
 template <int MAXP, int NSLOT, int MODE>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void query_kernel(StepArgs A) {
   using B = Turn<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   b.larmy = nullptr;
@@ -237,7 +232,7 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 template <typename BT>
 __device__ __forceinline__ bool row_any(uint32_t x) {
   const unsigned long long bal = __builtin_amdgcn_ballot_w64(x != 0u);
-  return ((bal >> (BT::row() * BT::ROWL)) & (BT::ROWL == 32 ? 0xFFFFFFFFull : 0xFFFFull)) != 0ull;
+  return row_slice<BT::ROWL>(bal, BT::row()) != 0u;
 }
 
 // wave-uniform bit set: bit k*PPR + r <=> row r of register k satisfied `flag` on some lane
@@ -247,7 +242,7 @@ __device__ __forceinline__ uint32_t rows_to_bits(bool flag, int k) {
   uint32_t bits = 0u;
 #pragma unroll
   for (int r = 0; r < BT::PPR; ++r)
-    if ((bal >> (r * BT::ROWL)) & (BT::ROWL == 32 ? 0xFFFFFFFFull : 0xFFFFull)) bits |= 1u << (k * BT::PPR + r);
+    if (row_slice<BT::ROWL>(bal, r)) bits |= 1u << (k * BT::PPR + r);
   return bits;
 }
 
@@ -262,8 +257,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void bot_kernel(StepArgs A, B
   using B = Turn<MAXP, NSLOT>;
   constexpr int NR = B::NR, PPR = B::PPR, ROWL = B::ROWL;
   __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int wave = block_wave(), lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   b.larmy = &army_shadow[wave][0];
@@ -298,9 +293,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void bot_kernel(StepArgs A, B
       for (int s = 0; s < NSLOT; ++s) {
         int idx = 64 * s + lane + off;
         idx = idx < 0 ? 0 : (idx > 64 * NSLOT - 1 ? 64 * NSLOT - 1 : idx);   // off the board: masked by the legal planes
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(b.army[s] - 1 > b.larmy[idx]);
-        g = (uint32_t)gvec_llvm_writelane((int)(uint32_t)bal, 2 * s, (int)g);
-        g = (uint32_t)gvec_llvm_writelane((int)(uint32_t)(bal >> 32), 2 * s + 1, (int)g);
+        ballot_to_row0(g, __builtin_amdgcn_ballot_w64(b.army[s] - 1 > b.larmy[idx]), s);
       }
       mok[d] = B::replicate_row0(g);
     }
@@ -383,7 +376,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void bot_kernel(StepArgs A, B
 #pragma unroll
     for (int p = 0; p < MAXP; ++p) {
       if (!((movers >> p) & 1u)) continue;
-      const int k = p / PPR, rb = (p % PPR) * ROWL;
+      const int k = p / PPR, rb = player_row<ROWL>(p);
       const bool cap = (cap_bits >> p) & 1u;
       uint64_t best = 0ull;
 #pragma unroll
@@ -397,13 +390,13 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void bot_kernel(StepArgs A, B
             int idx = (int)t + off;
             idx = idx < 0 ? 0 : (idx > 64 * NSLOT - 1 ? 64 * NSLOT - 1 : idx);
             const uint64_t margin = (uint64_t)(uint32_t)(b.army[s] - 1 - b.larmy[idx]);
-            const uint64_t key = b.gather(sel[k][d], s, rb) ? ((margin << 12) | low | (uint64_t)(3 - d)) : 0ull;
+            const uint64_t key = gather(sel[k][d], s, rb) ? ((margin << 12) | low | (uint64_t)(3 - d)) : 0ull;
             best = key > best ? key : best;
           }
         } else {
           int dsel = -1;
 #pragma unroll
-          for (int d = 3; d >= 0; --d) dsel = b.gather(sel[k][d], s, rb) ? d : dsel;
+          for (int d = 3; d >= 0; --d) dsel = gather(sel[k][d], s, rb) ? d : dsel;
           const uint64_t key = dsel >= 0 ? (((uint64_t)(uint32_t)b.army[s] << 12) | low | (uint64_t)(3 - dsel)) : 0ull;
           best = key > best ? key : best;
         }
@@ -473,6 +466,20 @@ __global__ void selftest_kernel(int32_t* out) {
     if (row_scan_add<16>(v) != e16 || row_scan_add<32>(v) != e32) fail = fail ? fail : 8;
     if (row_scan_or<16>(1u << (lane & 31)) != o16 || row_scan_or<32>(1u << (lane & 31)) != o32) fail = fail ? fail : 9;
     if (row_last<16>(v) != (uint32_t)((lane | 15) * 3 + 1) || row_last<32>(v) != (uint32_t)((lane | 31) * 3 + 1)) fail = fail ? fail : 10;
+  }
+  {  // the packed layout's row idioms, 16- and 32-lane rows (6: the failure code nothing used)
+    int32_t m16 = -1, m32 = -1;
+    const int32_t x = (int32_t)((lane * 37) & 63) - 1;  // a permutation of -1 .. 62
+    for (int l = lane & ~15; l <= lane; ++l) m16 = max(m16, (int32_t)((l * 37) & 63) - 1);
+    for (int l = lane & ~31; l <= lane; ++l) m32 = max(m32, (int32_t)((l * 37) & 63) - 1);
+    if (row_scan_max<16>(x) != m16 || row_scan_max<32>(x) != m32) fail = fail ? fail : 6;
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(((lane * 5) & 7) < 3);  // lanes 0, 2, 5 of every 8
+    if (row_slice<16>(bal, lane >> 4) != 0x2525u || row_slice<32>(bal, lane >> 5) != 0x25252525u) fail = fail ? fail : 13;
+    // player p's row: row p % 4 of 16 lanes, p % 2 of 32
+    if (player_lane<16>(lane, 3) != (lane & 3) * 16 + 3 || player_lane<32>(lane, 3) != (lane & 1) * 32 + 3 || player_row<16>(lane) != (lane & 3) * 16 ||
+        player_row<32>(lane) != (lane & 1) * 32) fail = fail ? fail : 14;
+    if (row_result<16>(v, lane & 3) != (uint32_t)(((lane & 3) * 16 + 15) * 3 + 1) ||
+        row_result<32>(v, lane & 1) != (uint32_t)(((lane & 1) * 32 + 31) * 3 + 1)) fail = fail ? fail : 15;
   }
   if ((uint32_t)gvec_llvm_writelane(777, 5, (int)v) != (lane == 5 ? 777u : v)) fail = fail ? fail : 11;
   if (mad24(v, 3u, 5u) != v * 3u + 5u) fail = fail ? fail : 12;

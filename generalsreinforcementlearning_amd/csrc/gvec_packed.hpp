@@ -16,7 +16,8 @@
 //
 // All turn logic lives here (TurnProcessor.ProcessTurn and everything below it, the legal-action mask,
 // performInitialSetup); every routine cites the Go function it reproduces, paths relative to
-// /root/reference/internal/game/.  HBM layout, tile domain (armies) and header are Board's.
+// /root/reference/internal/game/.  HBM layout, tile domain (armies), header unpack / pack, the flat <-> tile crossings,
+// derive_targets and settle_lists are gvec_device.hpp's; the row idioms of this layout are the helpers below.
 #pragma once
 #include "gvec_device.hpp"
 
@@ -56,6 +57,29 @@ __device__ __forceinline__ uint32_t row_scan_or(uint32_t v) {  // inclusive pref
   if constexpr (ROWL == 32) v |= dpp0<0x142, 0xa>(v);
   return v;
 }
+template <int ROWL>
+__device__ __forceinline__ int32_t row_scan_max(int32_t v) {  // inclusive prefix maximum inside every row, of values >= -1
+  v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x111, 0xf, 0xf, false));  // row_shr:1, lanes without a source keep -1
+  v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x112, 0xf, 0xf, false));
+  v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x114, 0xf, 0xf, false));
+  v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x118, 0xf, 0xf, false));
+  if constexpr (ROWL == 32) v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x142, 0xa, 0xf, false));  // row_bcast15 into DPP rows 1, 3
+  return v;
+}
+// row r's slice of a ballot: bit c = lane c of that row
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_slice(unsigned long long ballot, int r) {
+  return (uint32_t)(ballot >> (r * ROWL)) & (ROWL == 32 ? 0xFFFFFFFFu : 0xFFFFu);
+}
+// the first lane of the row that holds player p (row p % PPR of register p / PPR), and its lane c: where a lane looks to
+// read dword c of player p's plane
+template <int ROWL>
+__device__ __forceinline__ int player_row(int p) { return (p % (64 / ROWL)) * ROWL; }
+template <int ROWL>
+__device__ __forceinline__ int player_lane(int p, int c) { return player_row<ROWL>(p) + c; }
+// what the LAST lane of row r holds (a row-wise scan's result), per lane: lane p asks for its player's row, r = p % PPR
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_result(uint32_t v, int r) { return bperm(((r * ROWL) + ROWL - 1) << 2, v); }
 // every lane receives the value of its row's LAST lane (ds_swizzle bit mode: lane = (lane & and) | or)
 template <int ROWL>
 __device__ __forceinline__ uint32_t row_last(uint32_t v) {
@@ -116,6 +140,8 @@ struct PBoard {
   uint32_t shp[NSR];                          // in flight between load_planes and spread_shared: row r of shp[k] = shared plane k*PPR + r
   int32_t army[NSLOT];                        // tile domain, as in Board
   uint32_t hv;
+  // registers of a wave's resident state: packed planes, shared planes, rowbit, armies, the kernels' mask planes
+  static constexpr int STATE_REGS = 3 * NR + NSHARED + NR + NSLOT + 4 * NR;
   int32_t* larmy;                             // LDS shadow of the armies during the action phase: tile t at larmy[t]
   uint32_t* lscr = nullptr;                   // ACT_SCRATCH_DW dwords of LDS for the vector action phase (null: sequential only)
   int W, H, P, N, turn, recipW;
@@ -166,7 +192,7 @@ struct PBoard {
     return x;
   }
 
-  // ---- header (Board's) ---------------------------------------------------------------------------
+  // ---- header (unpack_hdr / pack_hdr: gvec_device.hpp) ---------------------------------------------
   // Split in two so that a kernel can put every load of the board in flight BEFORE anything waits for the
   // header: issue_hdr, load_army_narrow, load_planes, land(), decode_hdr - one memory round trip per board
   // instead of two (the turn is a latency chain: a second round trip is ~15 % of a wave's life).
@@ -176,31 +202,11 @@ struct PBoard {
 #pragma unroll
     for (int k = 0; k < NR; ++k) rowbit[k] = 1u << lane_player(k);
   }
-  __device__ __forceinline__ void decode_hdr() {
-    turn = (int)rdlane(hv, H_TURN);
-    const uint32_t dims = rdlane(hv, H_DIMS);
-    W = (int)(dims & 0xFFu);
-    H = (int)((dims >> 8) & 0xFFu);
-    P = (int)((dims >> 16) & 0xFFu);
-    hflags = dims >> 24;
-    N = W * H;
-    alive = rdlane(hv, H_STATUS) & 0xFFu;
-    recipW = (int)rdlane(hv, H_RECIPW);
-  }
-  // The same fields through the scalar cache (s_load: no vector instruction, no cross-lane read).  The header
+  // The header fields through the scalar cache (s_load: no vector instruction, no cross-lane read).  The header
   // is only written by this wave's own final store, and the scalar cache is invalidated between launches.
   __device__ __forceinline__ void decode_hdr_scalar(const uint32_t* hdr_env) {
     typedef const __attribute__((address_space(4))) uint32_t* kptr;
-    kptr k = (kptr)hdr_env;
-    turn = (int)k[H_TURN];
-    const uint32_t dims = k[H_DIMS];
-    W = (int)(dims & 0xFFu);
-    H = (int)((dims >> 8) & 0xFFu);
-    P = (int)((dims >> 16) & 0xFFu);
-    hflags = dims >> 24;
-    N = W * H;
-    alive = k[H_STATUS] & 0xFFu;
-    recipW = (int)k[H_RECIPW];
+    unpack_hdr(*this, [k = (kptr)hdr_env](int i) { return k[i]; });
   }
   // keeps the scalar loads above from being sunk to their first use (a late s_load is a late round trip)
   __device__ __forceinline__ void land_scalars() {
@@ -208,7 +214,7 @@ struct PBoard {
   }
   __device__ __forceinline__ void load_hdr(const uint32_t* hdr_env) {
     issue_hdr(hdr_env);
-    decode_hdr();
+    decode_hdr(*this);
   }
   // Every register a load of this board writes is "touched" here: the compiler can neither sink those loads below a
   // later (header-dependent) branch nor split the wait - all of them are in flight together and land at this point.
@@ -244,14 +250,7 @@ struct PBoard {
     asm volatile("" : "+v"(vch));
     asm volatile("" : "+v"(gt1));
   }
-  __device__ __forceinline__ void hdr_set(int k, uint32_t v) { hv = (uint32_t)gvec_llvm_writelane((int)v, k, (int)hv); }
-  __device__ __forceinline__ uint32_t hdr_get(int k) const { return rdlane(hv, k); }
-  __device__ __forceinline__ void store_hdr(uint32_t* hdr_env, uint32_t last_err) {
-    hdr_set(H_TURN, (uint32_t)turn);
-    hdr_set(H_DIMS, (uint32_t)W | ((uint32_t)H << 8) | ((uint32_t)P << 16) | (hflags << 24));
-    hdr_set(H_STATUS, alive | (last_err << 16));  // (H_RECIPW is a function of W: it rides along in hv unchanged)
-    if (lane_id() < HDR_DW) st_stream<GVEC_NT_PLANE>(hdr_env + lane_id(), hv);
-  }
+  __device__ __forceinline__ void store_hdr(uint32_t* hdr_env, uint32_t last_err) { pack_hdr<false, GVEC_NT_PLANE>(*this, hdr_env, last_err); }
 
   // ---- planes: one load per PPR planes (row r of a register = plane base + r) ----------------------------
   // Lanes that hold no dword of the bit string (column >= fd, or a row without a plane) must read as zero.
@@ -318,8 +317,6 @@ struct PBoard {
       }
     }
   }
-  // Sets HF_LDIFF to what the lists are now: call BEFORE store_hdr; the plane stores write the lists accordingly.
-  __device__ __forceinline__ void settle_lists() { hflags = lists_match() ? (hflags & ~HF_LDIFF) : (hflags | HF_LDIFF); }
   __device__ __forceinline__ void store_lists(uint32_t* rows_env, int fd) const {
     if (!(hflags & HF_LDIFF)) return;
     uint32_t* gp = rows_env + row() * fd + col();
@@ -340,15 +337,7 @@ struct PBoard {
     ncol0 = shared_plane(PL::NCOL0 - PL::CHG);
     ncolL = shared_plane(PL::NCOLL - PL::CHG);
     if constexpr (DERIVE_OK) {
-      // Board::targets() in the packed domain: bit for bit the stored planes on every lane with col() < fd.  The lanes
-      // beyond hold zero in valid / ncol0 / ncolL (never loaded), so notm, ok[1] and ok[3] are zero there; ok[0] and ok[2]
-      // may carry the neighbouring lane's bits into column fd, where every plane they are ever ANDed with (own, lst, gt1:
-      // legal_planes) is zero.  Needs W (the header has landed) and wave-uniform control flow.
-      const uint32_t notm = valid & ~mtn;
-      ok[0] = upW(notm);
-      ok[1] = dn1(notm) & ncolL;
-      ok[2] = dnW(notm);
-      ok[3] = up1(notm) & ncol0;
+      derive_targets(*this);  // needs W: the header has landed
     } else {
 #pragma unroll
       for (int d = 0; d < 4; ++d) ok[d] = shared_plane(PL::OK + d - PL::CHG);
@@ -388,24 +377,11 @@ struct PBoard {
     }
     if (with_types && lane < row_dw - PL::COUNT * fd) rows_env[PL::COUNT * fd + lane] = 0u;  // the block's padding
   }
-  // narrow (u16 pairs) / wide (int32 escape) army storage: see gvec_device.hpp "army storage"
-  __device__ __forceinline__ void load_army(const ArmyCRef& a) {
-    army_load_narrow<NSLOT>(army, a.n);
-    if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
-  }
+  // narrow (u16 pairs) / wide (int32 escape) army storage: load_army / store_army, gvec_device.hpp "army storage"
   template <bool HALF_LAST = false>
   __device__ __forceinline__ void load_army_narrow(const ArmyCRef& a) { army_load_narrow<NSLOT, HALF_LAST>(army, a.n); }  // needs no header
   __device__ __forceinline__ void load_army_wide_if_flagged(const ArmyCRef& a) {
     if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
-  }
-  __device__ __forceinline__ void store_army(const ArmyRef& a) {  // sets / clears HF_WIDE: call BEFORE store_hdr
-    if (army_fits_narrow<NSLOT>(army)) {
-      hflags &= ~HF_WIDE;
-      army_store_narrow<NSLOT>(army, a.n);
-    } else {
-      hflags |= HF_WIDE;
-      army_store_wide<NSLOT>(army, a.w);
-    }
   }
 
   // ---- LDS army shadow of the action phase ---------------------------------------------------------
@@ -433,7 +409,7 @@ struct PBoard {
     uint32_t w = 0u;
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
-      const uint32_t r = rdlane(reg[k], (p % PPR) * ROWL + (t >> 5));
+      const uint32_t r = rdlane(reg[k], player_lane<ROWL>(p, t >> 5));
       w = (k == p / PPR) ? r : w;
     }
     return (w >> (t & 31)) & 1u;
@@ -441,39 +417,19 @@ struct PBoard {
   // the single bit of tile t, in every row
   __device__ __forceinline__ uint32_t tile_bit(int t) const { return (col() == (t >> 5)) ? (1u << (t & 31)) : 0u; }
 
-  // ---- flat <-> tile domain ---------------------------------------------------------------------------
-  // tile 64s+l is bit l&31 of dword 2s + (l>>5); row 0 of a replicated plane, row (p % PPR) of a packed one
-  __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s, int row_base = 0) const {
-    const int lane = lane_id();
-    return __builtin_amdgcn_sbfe((int32_t)bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
-  }
-  __device__ __forceinline__ uint32_t gather(uint32_t plane, int s, int row_base = 0) const {  // 0 / 1
-    const int lane = lane_id();
-    return __builtin_amdgcn_ubfe(bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
-  }
+  // ---- flat <-> tile domain (gather / gather_mask / ballot_to_row0: gvec_device.hpp) -----------------------
   static __device__ __forceinline__ uint32_t replicate_row0(uint32_t plane) { return bperm(col() << 2, plane); }
   // popcount of a replicated plane: row 0's lanes summed (the scan's zero fill keeps other rows out)
   __device__ __forceinline__ int count_shared(uint32_t plane) const {
     return (int)rdlane(row_scan_add<ROWL>((uint32_t)__builtin_popcount(plane)), ROWL - 1);
   }
   static __device__ __forceinline__ bool any_bit(uint32_t plane) { return __builtin_amdgcn_ballot_w64(plane != 0u) != 0ull; }
-  // OwnedTiles == board ownership for every player (no owned-but-unlisted tile, H6)
-  __device__ __forceinline__ bool lists_match() const {
-    uint32_t d = 0u;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) d |= lst[k] ^ own[k];
-    return !any_bit(d);
-  }
   // Tile.Army > 1 as a replicated flat plane: the ballot of slot s is dwords 2s, 2s+1 of the bit string
   // (written into row 0 with v_writelane: 2*NSLOT <= ROWL), one ds_bpermute copies row 0 into every row
   __device__ __forceinline__ void refresh_gt1() {
     uint32_t g = 0u;
 #pragma unroll
-    for (int s = 0; s < NSLOT; ++s) {
-      const unsigned long long b = __builtin_amdgcn_ballot_w64(army[s] > 1);
-      g = (uint32_t)gvec_llvm_writelane((int)(uint32_t)b, 2 * s, (int)g);
-      g = (uint32_t)gvec_llvm_writelane((int)(uint32_t)(b >> 32), 2 * s + 1, (int)g);
-    }
+    for (int s = 0; s < NSLOT; ++s) ballot_to_row0(g, __builtin_amdgcn_ballot_w64(army[s] > 1), s);
     gt1 = replicate_row0(g);
   }
 
@@ -511,8 +467,7 @@ struct PBoard {
       // affected: some lane of my row holds an owned tile near V - the row's slice of the ballot, looked at from the
       // lanes (a per-player scalar loop costs five scalar instructions a player; the scalar unit is the busier one)
       const unsigned long long hit = __builtin_amdgcn_ballot_w64((matched ? (d & near3) : (own[k] & near5)) != 0u);
-      const uint32_t mine = (uint32_t)(hit >> (row() * ROWL)) & (ROWL == 32 ? 0xFFFFFFFFu : 0xFFFFu);
-      const bool relit = mine != 0u && lane_flag(alive, k);
+      const bool relit = row_slice<ROWL>(hit, row()) != 0u && lane_flag(alive, k);
       vis[k] = (vis[k] & clr) | (relit ? d : 0u);
     }
   }
@@ -593,7 +548,7 @@ struct PBoard {
         for (int k = 0; k < NR; ++k) {
           const uint32_t sc = row_scan_add<ROWL>((uint32_t)__builtin_popcount(prod_mask & lst[k]));  // row totals in the rows' last lanes
           const int p = lane - H_ARMYCNT;
-          const uint32_t got = bperm((((p & (PPR - 1)) * ROWL) + ROWL - 1) << 2, sc);
+          const uint32_t got = row_result<ROWL>(sc, p & (PPR - 1));
           add += (p >= 0 && p < MAXP && p / PPR == k) ? __umul24(got, (uint32_t)prod_rate) : 0u;  // rates < 2^24 (gvec_create), got <= 1024
         }
       }
@@ -609,13 +564,13 @@ struct PBoard {
         for (int s = 0; s < NSLOT; ++s) {
 #pragma unroll
           for (int p = 0; p < MAXP; ++p)
-            acc[p] = (int32_t)mad24((uint32_t)army[s], gather(lst[p / PPR], s, (p % PPR) * ROWL), (uint32_t)acc[p]);
+            acc[p] = (int32_t)mad24((uint32_t)army[s], gather(lst[p / PPR], s, player_row<ROWL>(p)), (uint32_t)acc[p]);
         }
       } else {
 #pragma unroll
         for (int s = 0; s < NSLOT; ++s) {
 #pragma unroll
-          for (int p = 0; p < MAXP; ++p) acc[p] += army[s] & gather_mask(lst[p / PPR], s, (p % PPR) * ROWL);
+          for (int p = 0; p < MAXP; ++p) acc[p] += army[s] & gather_mask(lst[p / PPR], s, player_row<ROWL>(p));
         }
       }
       // Player.ArmyCount: header lanes H_ARMYCNT .. H_ARMYCNT+MAXP-1
@@ -625,19 +580,14 @@ struct PBoard {
     }
     // GeneralIdx / Alive (:46,52-54 / :101,122,133-135).  The reference keeps the last general in list order; with two or
     // more generals that order depends on Go map iteration.  Here: the highest listed general tile - found on lanes:
-    // every lane's candidate, the row's maximum by DPP, one ds_bpermute hands row p's result to header lane H_GIDX + p.
+    // every lane's candidate, the row's maximum by DPP (row_scan_max), one ds_bpermute hands row p's result to header lane H_GIDX + p.
     {
       const int hl = lane - H_GIDX;  // the player whose GeneralIdx this header lane holds
 #pragma unroll
       for (int k = 0; k < NR; ++k) {
         const uint32_t g = lst[k] & gen;
-        int32_t v = (g != 0u) ? (32 * col() + 31 - __builtin_clz(g)) : -1;
-        v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x111, 0xf, 0xf, false));  // row_shr:1, lanes without a source keep -1
-        v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x112, 0xf, 0xf, false));
-        v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x114, 0xf, 0xf, false));
-        v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x118, 0xf, 0xf, false));
-        if constexpr (ROWL == 32) v = max(v, (int32_t)__builtin_amdgcn_update_dpp(-1, v, 0x142, 0xa, 0xf, false));  // row_bcast15 into DPP rows 1, 3
-        const uint32_t got = bperm((((hl & (PPR - 1)) * ROWL) + ROWL - 1) << 2, (uint32_t)v);
+        const int32_t v = row_scan_max<ROWL>((g != 0u) ? (32 * col() + 31 - __builtin_clz(g)) : -1);
+        const uint32_t got = row_result<ROWL>((uint32_t)v, hl & (PPR - 1));
         hv = (hl >= 0 && hl < MAXP && hl / PPR == k) ? got : hv;
       }
       alive = (uint32_t)(__builtin_amdgcn_ballot_w64(hl >= 0 && hl < MAXP && (int32_t)hv >= 0) >> H_GIDX) & ((1u << MAXP) - 1u);
@@ -802,7 +752,7 @@ struct PBoard {
     if (distinct != 2 * ncand) return false;  // two moves meet on a tile: order matters
     // pre-turn facts of my move
     const int32_t fa = larmy[ft], ta = larmy[tt];
-    const int myrow = (lane % PPR) * ROWL;
+    const int myrow = (lane % PPR) * ROWL;  // player_row<ROWL>(lane), spelled out: through the helper the compiler folds it into the s_own index below and schedules the phase differently
     uint32_t w_ft = 0u;  // my own ownership row at the source dword
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
@@ -812,7 +762,7 @@ struct PBoard {
     uint32_t owner_bits = 0u;  // bit q: player q owns my target tile (pre-turn; none: neutral)
 #pragma unroll
     for (int q = 0; q < MAXP; ++q) {
-      const uint32_t g = bperm((((q % PPR) * ROWL) + tcol) << 2, own[q / PPR]);
+      const uint32_t g = bperm(player_lane<ROWL>(q, tcol) << 2, own[q / PPR]);
       owner_bits |= ((g >> (tt & 31)) & 1u) << q;
     }
     const bool own_ft = ((w_ft >> (ft & 31)) & 1u) != 0u;
@@ -894,7 +844,7 @@ struct PBoard {
         own[k] = (lane_player(k) == v) ? (own[k] & ~tiles) : own[k];
         own[k] = (lane_player(k) == nw) ? (own[k] | tiles) : own[k];
       }
-      hdr_set(H_GIDX + v, 0xFFFFFFFFu);  // :141 GeneralIdx = -1
+      hdr_set(*this, H_GIDX + v, 0xFFFFFFFFu);  // :141 GeneralIdx = -1
       chg |= tiles;                      // :133-134
       vch |= tiles;
       hflags &= ~HF_VSMALL;
@@ -912,7 +862,7 @@ struct PBoard {
   __device__ __forceinline__ uint32_t turn_step(const ActVec& av, const StepArgs& A, bool& aborted) {
     aborted = false;
     turn++;  // initializeTurn :124-135
-    const bool matched = lists_match();
+    const bool matched = lists_match(*this);
     if (!(GVEC_PROFILE_SKIP & 2)) update_fog(matched);
     if (GVEC_PROFILE_DUP & 2) { opaque(); update_fog(matched); }
     chg = 0u;
@@ -1053,15 +1003,6 @@ struct PBoard {
     if constexpr ((NSLOT & 1) != 0) reinterpret_cast<uint16_t*>(stage + 64 * (NSLOT / 2))[lane] = (uint16_t)army[NSLOT - 1];
     wave_lds_fence();
     flush_stage<GVEC_NT_ARMY>(n, NSLOT * 32);
-  }
-  __device__ __forceinline__ void store_army_staged(const ArmyRef& a) {  // sets / clears HF_WIDE: call BEFORE store_hdr
-    if (army_fits_narrow<NSLOT>(army)) {
-      hflags &= ~HF_WIDE;
-      store_army_narrow_staged(a.n);
-    } else {
-      hflags |= HF_WIDE;
-      army_store_wide<NSLOT>(army, a.w);
-    }
   }
   // The same bytes through the LDS army shadow (idle once the action phase is over): store_masks' instructions each
   // write one direction of every player - pieces of fd dwords, 4*fd dwords apart - and partial-line writes from four

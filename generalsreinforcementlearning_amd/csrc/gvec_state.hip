@@ -10,8 +10,8 @@ namespace gvec {
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.n) return;
   const int env = A.env_ids ? uni(A.env_ids[i]) : A.dst_begin + i;
   if (env < 0 || env >= A.dst_envs) {  // ids handed over in device memory were not seen by the host
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
       const int o = (t < b.N) ? (int)A.s_owner[to + t] : -1;
       bad_owner |= (o < -1) || (o >= b.P);
 #pragma unroll
-      for (int p = 0; p < MAXP; ++p) b.scatter(b.own[p], __builtin_amdgcn_ballot_w64(o == p), s);
+      for (int p = 0; p < MAXP; ++p) ballot_to_row0(b.own[p], __builtin_amdgcn_ballot_w64(o == p), s);
     }
   }
   if (wave_any(bad_owner)) {
@@ -74,9 +74,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
       const int ty = (t < b.N) ? (int)A.s_type[to + t] : GVEC_TILE_NORMAL;
-      b.scatter(b.gen, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_GENERAL), s);
-      b.scatter(b.city, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_CITY), s);
-      b.scatter(b.mtn, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_MOUNTAIN), s);
+      ballot_to_row0(b.gen, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_GENERAL), s);
+      ballot_to_row0(b.city, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_CITY), s);
+      ballot_to_row0(b.mtn, __builtin_amdgcn_ballot_w64(ty == GVEC_TILE_MOUNTAIN), s);
     }
   }
   if (A.s_visible) {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
       const int t = 64 * s + lane;
       const uint32_t v = (t < b.N) ? (uint32_t)A.s_visible[to + t] : 0u;
 #pragma unroll
-      for (int p = 0; p < MAXP; ++p) b.scatter(b.vis[p], __builtin_amdgcn_ballot_w64(((v >> p) & 1u) != 0u), s);
+      for (int p = 0; p < MAXP; ++p) ballot_to_row0(b.vis[p], __builtin_amdgcn_ballot_w64(((v >> p) & 1u) != 0u), s);
     }
   }
   if (A.s_listed) {
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
       const int t = 64 * s + lane;
       const int o = (t < b.N) ? (int)A.s_listed[to + t] : -1;
 #pragma unroll
-      for (int p = 0; p < MAXP; ++p) b.scatter(b.lst[p], __builtin_amdgcn_ballot_w64(o == p), s);
+      for (int p = 0; p < MAXP; ++p) ballot_to_row0(b.lst[p], __builtin_amdgcn_ballot_w64(o == p), s);
     }
   }
   if (A.s_changed) {
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
-      b.scatter(b.chg, __builtin_amdgcn_ballot_w64(t < b.N && A.s_changed[to + t] != 0), s);
+      ballot_to_row0(b.chg, __builtin_amdgcn_ballot_w64(t < b.N && A.s_changed[to + t] != 0), s);
     }
   }
   if (A.s_vis_changed) {
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const int t = 64 * s + lane;
-      b.scatter(b.vch, __builtin_amdgcn_ballot_w64(t < b.N && A.s_vis_changed[to + t] != 0), s);
+      ballot_to_row0(b.vch, __builtin_amdgcn_ballot_w64(t < b.N && A.s_vis_changed[to + t] != 0), s);
     }
   }
   if (A.s_army) {
@@ -132,17 +132,17 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
     b.alive = al;
   }
   for (int p = 0; p < b.P; ++p) {
-    if (A.s_army_count) b.hdr_set(H_ARMYCNT + p, (uint32_t)A.s_army_count[po + p]);
-    if (A.s_general_idx) b.hdr_set(H_GIDX + p, (uint32_t)A.s_general_idx[po + p]);
+    if (A.s_army_count) hdr_set(b, H_ARMYCNT + p, (uint32_t)A.s_army_count[po + p]);
+    if (A.s_general_idx) hdr_set(b, H_GIDX + p, (uint32_t)A.s_general_idx[po + p]);
   }
   // the planes that are functions of the board: rebuilt on every import (the type planes may have changed)
-  b.targets();
+  derive_targets(b);
   b.static_flags();
   b.refresh_gt1();
   if (A.init) b.hflags |= HF_SETUP;  // performInitialSetup runs in setup_kernel, on the turn engine's layout
-  b.store_army(army);
-  b.settle_lists();
-  b.store_hdr(hdr, A.fresh ? 0u : ((b.hdr_get(H_STATUS) >> 16) & 0xFFu));
+  store_army(b, army);
+  settle_lists(b);
+  b.store_hdr(hdr, A.fresh ? 0u : ((hdr_get(b, H_STATUS) >> 16) & 0xFFu));
   b.store_planes(rows, A.fd, A.row_dw, true);
 }
 
@@ -152,8 +152,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void import_kernel(ImportArgs
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void export_kernel(ExportArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.n) return;
   const int env = A.env_begin + i;
   B b;
@@ -172,16 +172,16 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void export_kernel(ExportArgs
     uint32_t visb = 0u;
 #pragma unroll
     for (int p = 0; p < MAXP; ++p) {
-      owner = b.gather(b.own[p], s) ? p : owner;
-      listed = b.gather(b.lst[p], s) ? p : listed;
-      visb |= b.gather(b.vis[p], s) << p;
+      owner = gather(b.own[p], s) ? p : owner;
+      listed = gather(b.lst[p], s) ? p : listed;
+      visb |= gather(b.vis[p], s) << p;
     }
     // every gather is a cross-lane ds_bpermute: evaluate them all convergently, never inside a
     // per-lane short-circuit (a masked-off source lane reads back as 0)
-    const uint32_t is_gen = b.gather(b.gen, s), is_city = b.gather(b.city, s), is_mtn = b.gather(b.mtn, s);
+    const uint32_t is_gen = gather(b.gen, s), is_city = gather(b.city, s), is_mtn = gather(b.mtn, s);
     const int type = is_gen ? GVEC_TILE_GENERAL : (is_city ? GVEC_TILE_CITY : (is_mtn ? GVEC_TILE_MOUNTAIN : GVEC_TILE_NORMAL));
-    const uint32_t c = b.gather(b.chg, s), vc = b.gather(b.vch, s);
-    const uint32_t pv = b.gather(pv_plane, s), sp = b.gather(special, s);
+    const uint32_t c = gather(b.chg, s), vc = gather(b.vch, s);
+    const uint32_t pv = gather(pv_plane, s), sp = gather(special, s);
     if (t < A.stride) {
       if (A.army_out) A.army_out[to + t] = in ? b.army[s] : 0;
       if (A.owner) A.owner[to + t] = (int8_t)(in ? owner : -1);
@@ -213,9 +213,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void export_kernel(ExportArgs
     if (lane == 0 && p < A.max_p) {
       const bool live = p < b.P;
       if (A.alive) A.alive[po + p] = (uint8_t)(live ? ((b.alive >> p) & 1u) : 0u);
-      if (A.army_count) A.army_count[po + p] = live ? (int32_t)b.hdr_get(H_ARMYCNT + p) : 0;
+      if (A.army_count) A.army_count[po + p] = live ? (int32_t)hdr_get(b, H_ARMYCNT + p) : 0;
       if (A.tile_count) A.tile_count[po + p] = live ? (int32_t)tcnt[p] : 0;
-      if (A.general_idx) A.general_idx[po + p] = live ? (int32_t)b.hdr_get(H_GIDX + p) : -1;
+      if (A.general_idx) A.general_idx[po + p] = live ? (int32_t)hdr_get(b, H_GIDX + p) : -1;
     }
   }
 }
@@ -229,8 +229,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void export_kernel(ExportArgs
 template <int MAXP, int NSLOT, bool IMPORT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void records_kernel(RecordArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.n) return;
   const int env = A.env_begin + i;
   uint32_t* rec_hdr = A.rec_hdr + (size_t)i * HDR_DW;
@@ -241,8 +241,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void records_kernel(RecordArg
     load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
     b.hflags &= ~HF_WIDE;
     army_store_wide<NSLOT>(b.army, rec_army);
-    b.settle_lists();
-    b.store_hdr(rec_hdr, (b.hdr_get(H_STATUS) >> 16) & 0xFFu);
+    settle_lists(b);
+    b.store_hdr(rec_hdr, (hdr_get(b, H_STATUS) >> 16) & 0xFFu);
     b.store_planes(rec_rows, A.fd, A.row_dw, true, true);  // a record carries its list planes whatever the flag says
   } else {
     b.load_hdr(rec_hdr);
@@ -271,12 +271,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void records_kernel(RecordArg
     b.mtn &= b.valid;
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) b.army[s] = (64 * s + lane < b.N) ? b.army[s] : 0;
-    b.targets();
+    derive_targets(b);
     b.static_flags();
     b.refresh_gt1();
-    b.store_army(army_ref<NSLOT>(A.army16, A.army32, env));
-    b.settle_lists();
-    b.store_hdr(A.hdr + (size_t)env * HDR_DW, (b.hdr_get(H_STATUS) >> 16) & 0xFFu);
+    store_army(b, army_ref<NSLOT>(A.army16, A.army32, env));
+    settle_lists(b);
+    b.store_hdr(A.hdr + (size_t)env * HDR_DW, (hdr_get(b, H_STATUS) >> 16) & 0xFFu);
     b.store_planes(A.rows + (size_t)env * A.row_dw, A.fd, A.row_dw, true);
   }
 }
@@ -290,8 +290,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void records_kernel(RecordArg
 // stay in L2 for the step that usually follows.
 // =========================================================================================
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void copy_envs_kernel(CopyArgs A) {
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int i = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int i = wave_item();
   if (i >= A.n) return;
   const int d = uni(A.dst_ids ? A.dst_ids[i] : i), s = uni(A.src_ids ? A.src_ids[i] : i);
   if (d < 0 || d >= A.dst_envs || s < 0 || s >= A.src_envs) {

@@ -18,8 +18,8 @@ namespace gvec {
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void stream_delta_kernel(StreamDeltaArgs A) {
   using B = Board<MAXP, NSLOT>;
-  const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int env = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int lane = lane_id();
+  const int env = wave_item();
   if (env >= A.num_envs) return;
   B b;
   load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
@@ -47,10 +47,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void stream_delta_kernel(Stre
       const int t = 64 * s + lane;
       int owner = -1;
 #pragma unroll
-      for (int p = 0; p < MAXP; ++p) owner = b.gather(b.own[p], s) ? p : owner;
-      const uint32_t is_gen = b.gather(b.gen, s), is_city = b.gather(b.city, s), is_mtn = b.gather(b.mtn, s);
-      const uint32_t pv = b.gather(vis_p, s);
-      const bool sel = b.gather(sel_plane, s) != 0u && t < b.N;
+      for (int p = 0; p < MAXP; ++p) owner = gather(b.own[p], s) ? p : owner;
+      const uint32_t is_gen = gather(b.gen, s), is_city = gather(b.city, s), is_mtn = gather(b.mtn, s);
+      const uint32_t pv = gather(vis_p, s);
+      const bool sel = gather(sel_plane, s) != 0u && t < b.N;
       int type = is_gen ? GVEC_TILE_GENERAL : (is_city ? GVEC_TILE_CITY : (is_mtn ? GVEC_TILE_MOUNTAIN : GVEC_TILE_NORMAL));
       const bool visible = !fog_on || pv != 0u;                        // ComputePlayerVisibility (visibility_optimized.go:166-195)
       const bool fogged = !visible && type != GVEC_TILE_NORMAL;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const int32_t* count,
 }
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void pack_updates_kernel(const unsigned long long* rows, const int32_t* count, const long long* offset,
                                                                             unsigned long long* packed, int32_t n, int32_t cap, long long capacity) {
-  const int env = (int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  const int env = (int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));  // per lane, not wave_item(): nothing here needs it uniform
   if (env >= n) return;
   const long long base = offset[env];
   const int c = count[env];
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(1024) void collect_scan_kernel(gvec_collect_args A)
 }
 // `wpe` wavefronts per worker (a power of two): ReplayBuffer.push of its transition, and its episode result
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void collect_push_kernel(gvec_collect_args A, int wpe_shift) {
-  const int gw = uni((int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6)));
+  const int gw = wave_item();
   const int w = gw >> wpe_shift, part = gw & ((1 << wpe_shift) - 1);
   if (w >= A.num_envs) return;
   const CollectScratch S = collect_scratch(A.scratch, A.num_envs);

@@ -59,8 +59,7 @@ __device__ __forceinline__ uint32_t agent_sample(const Turn<MAXP, NSLOT>& b, con
     const uint32_t fin = inv ? unchecked : pick;
     const bool go = act && (fin & 0x8000u) != 0u;
     const uint32_t out = (fin & 0xFFFu) | (go ? 0x1000u : 0u) | (half ? 0x2000u : 0u);
-    // lane p <- the last lane of row p % PPR of register p / PPR
-    const uint32_t got = bperm((((lane % PPR) * ROWL) + ROWL - 1) << 2, out);
+    const uint32_t got = row_result<ROWL>(out, lane % PPR);  // lane p <- the last lane of row p % PPR of register p / PPR
     mine = (lane / PPR == k) ? got : mine;
   }
   return mine;
@@ -106,7 +105,7 @@ __device__ __forceinline__ typename Turn<MAXP, NSLOT>::ActVec agent_actvec(const
 template <typename BT>
 __device__ __forceinline__ void load_board(BT& b, const uint32_t* hdr, const uint32_t* rows, const ArmyCRef& army, int fd) {
   b.load_hdr(hdr);
-  b.load_army(army);
+  load_army(b, army);
   b.load_planes(rows, fd);
 }
 // EARLY (the per-turn step kernel): every load of the board goes out before the header is decoded - one memory round
@@ -127,7 +126,7 @@ __device__ __forceinline__ void load_turn(BT& b, const uint32_t* hdr, const uint
     b.load_army_wide_if_flagged(army);
   } else {
     b.load_hdr(hdr);
-    b.load_army(army);
+    load_army(b, army);
     b.template load_planes<false>(rows, fd, zeros);
   }
 }
@@ -135,15 +134,15 @@ __device__ __forceinline__ void load_turn(BT& b, const uint32_t* hdr, const uint
 // vector-env auto-reset: this step re-deals the env from the board pool (no Go analogue)
 template <int MAXP, int NSLOT, typename BT>
 __device__ __forceinline__ void redeal(BT& b, const StepArgs& A, int env, int fd, int row_dw) {
-  const uint32_t episode = b.hdr_get(H_EPISODE) + 1u;
-  const uint32_t cs = b.hdr_get(H_CNT_STEPS), ca = b.hdr_get(H_CNT_ABORT), cd = b.hdr_get(H_CNT_DONE);
+  const uint32_t episode = hdr_get(b, H_EPISODE) + 1u;
+  const uint32_t cs = hdr_get(b, H_CNT_STEPS), ca = hdr_get(b, H_CNT_ABORT), cd = hdr_get(b, H_CNT_DONE);
   const uint32_t hk = fmix32(env_key_of(A.pool_seed_base, (uint32_t)env) ^ (episode * 0x9E3779B1u));
   const int j = (int)__umulhi(hk, (uint32_t)A.pool_size);
   load_turn(b, A.pool_hdr + (size_t)j * HDR_DW, A.pool_rows + (size_t)j * row_dw, army_cref<NSLOT>(A.pool_army16, A.pool_army32, j), fd, A.zeros);
-  b.hdr_set(H_EPISODE, episode);
-  b.hdr_set(H_CNT_STEPS, cs);
-  b.hdr_set(H_CNT_ABORT, ca);
-  b.hdr_set(H_CNT_DONE, cd);
+  hdr_set(b, H_EPISODE, episode);
+  hdr_set(b, H_CNT_STEPS, cs);
+  hdr_set(b, H_CNT_ABORT, ca);
+  hdr_set(b, H_CNT_DONE, cd);
 }
 
 }  // namespace gvec
