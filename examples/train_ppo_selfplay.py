@@ -15,6 +15,11 @@ learner for it; the code is this repo's own.  An example, not part of the measur
 --features adds the five strategic feature planes (features.strategic_features: distances to the own general, the nearest
 enemy, city and fogged tile, and the front line) to the nine of the observation.  The store keeps nine planes per row: the
 five are recomputed from them where they are consumed, while acting and on every minibatch.
+
+--memory adds the four fog-of-war memory planes (memory.ObservationMemory: seen, last owner, last army, age): what the learner
+last saw of every tile, which the observation forgets the moment the tile is fogged again.  They are state, not a function of
+one observation, so the rollout buffer stores them per step (SelfPlayRolloutBuffer(memory=)).  With --features as well the
+features are computed from remembered_observation: the distance to the nearest enemy tile seen so far.
 """
 import argparse
 import json
@@ -27,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from generalsreinforcementlearning_amd.features import NUM_STRATEGIC_FEATURES, strategic_features
+from generalsreinforcementlearning_amd.memory import NUM_MEMORY_PLANES, ObservationMemory, remembered_observation
 from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead
 from generalsreinforcementlearning_amd.rollout import SelfPlayRolloutBuffer
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
@@ -65,37 +71,47 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--features", action="store_true", help="feed the five strategic feature planes next to the observation's nine")
+    ap.add_argument("--memory", action="store_true", help="feed the four fog-of-war memory planes (what each tile last showed, and how long ago)")
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
     dev = torch.device("cuda", 0)
     obs_shape, n_actions = (9, a.board, a.board), a.board * a.board * 5
-    channels = 9 + (NUM_STRATEGIC_FEATURES if a.features else 0)
+    channels = 9 + (NUM_MEMORY_PLANES if a.memory else 0) + (NUM_STRATEGIC_FEATURES if a.features else 0)
     net = ActorCritic((channels,) + obs_shape[1:], n_actions).to(dev)
-    # the network's input of observations [N, 9, H, W]: a pure function of them, so stored rows need no extra planes
-    inputs = (lambda o: torch.cat([o, strategic_features(o)], dim=1)) if a.features else (lambda o: o)
+
+    def inputs(o, m):
+        """the network's input of observations [N, 9, H, W] and their memory planes [N, 4, H, W] (None without --memory).
+        The features are a pure function of those, so stored rows need no planes for them."""
+        planes = [o] if m is None else [o, m]
+        if a.features:
+            planes.append(strategic_features(o if m is None else remembered_observation(o, m)))
+        return torch.cat(planes, dim=1) if len(planes) > 1 else o
+
     opt = torch.optim.Adam(net.parameters(), lr=a.lr)
     start = [p.detach().clone() for p in net.parameters()]
     env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
                                  seed=a.seed, device_outputs=True)
-    buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda)
-    head = MaskedCategoricalHead(dev)
     B, L = env.num_envs, env.num_learners
+    memory = ObservationMemory((B, L), a.board, a.board, device=dev) if a.memory else None
+    buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda, memory=memory)
+    head = MaskedCategoricalHead(dev)
+    current = lambda: inputs(buf.obs.view(B * L, *obs_shape), buf.memory.view(B * L, NUM_MEMORY_PLANES, *obs_shape[1:]) if a.memory else None)
     buf.begin(*env.reset())
     out, draws, t0 = [], 0, time.perf_counter()
     for it in range(a.iterations):
         with torch.no_grad():
             while not buf.full:
-                logits, value = net(inputs(buf.obs.view(B * L, *obs_shape)))
+                logits, value = net(current())
                 draws += 1                          # one seed per step: a draw is keyed by (seed, row, action index)
                 actions, logp, _ = head.sample(logits.view(B, L, n_actions), buf.valid_actions_mask, seed=(a.seed << 32) + draws)
                 buf.step(actions, logp, value)
-            buf.finish(net(inputs(buf.obs.view(B * L, *obs_shape)))[1])
+            buf.finish(net(current())[1])
         sums = torch.zeros(5, device=dev)           # policy loss, value loss, entropy, clipped share, batches
         for batch in buf.minibatches(a.batch_size, epochs=a.epochs, seed=a.seed + it):
             w = batch["weight"]
             n = w.sum().clamp_min(1.0)
-            logits, value = net(inputs(batch["obs"]))
+            logits, value = net(inputs(batch["obs"], batch.get("memory")))
             logp, entropy = head.evaluate(logits, batch["valid_actions_mask"], batch["action"])
             ratio = (logp - batch["logp"]).exp()
             adv = batch["advantages"]

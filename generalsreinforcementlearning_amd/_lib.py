@@ -94,6 +94,12 @@ class ObsFeaturesArgs(C.Structure):
                 + [("obs_row_stride", C.c_int64), ("obs", C.c_void_p), ("out", C.c_void_p)])
 
 
+class ObsMemoryArgs(C.Structure):
+    """gvec_obs_memory_args (include/generals_vec.h): obs, prev, reset and out are device memory; prev and reset may be None."""
+    _fields_ = ([("rows", C.c_int64)] + [(n, C.c_int32) for n in ("width", "height", "cap", "rows_per_flag")]
+                + [("obs_row_stride", C.c_int64)] + [(n, C.c_void_p) for n in ("obs", "prev", "reset", "out")])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -163,6 +169,7 @@ SYMBOLS = {
     "gvec_policy_evaluate": (_i32, [_i32, _vp, C.POINTER(PolicyEvaluateArgs)]),
     "gvec_policy_backward": (_i32, [_i32, _vp, C.POINTER(PolicyBackwardArgs)]),
     "gvec_obs_features": (_i32, [_i32, _vp, C.POINTER(ObsFeaturesArgs)]),
+    "gvec_obs_memory_update": (_i32, [_i32, _vp, C.POINTER(ObsMemoryArgs)]),
     "gvec_gym_observe":(_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -310,4 +310,7 @@ hipError_t launch_policy_backward(const gvec_policy_backward_args& a, hipStream_
 // strategic feature planes (gvec_features.hip; generals_vec.h "strategic feature planes")
 hipError_t launch_obs_features(const gvec_obs_features_args& a, hipStream_t s);
 
+// fog-of-war memory planes (gvec_memory.hip; generals_vec.h "fog-of-war memory planes")
+hipError_t launch_obs_memory(const gvec_obs_memory_args& a, hipStream_t s);
+
 }  // namespace gvec

@@ -25,6 +25,10 @@ Precondition: every board holds max_players players (GeneralsSelfPlayVecEnv alwa
         buf.next_rollout()
 
 Nothing here synchronises with the host, except minibatches(compact=True): one 8-byte read per rollout.
+
+memory=ObservationMemory((num_envs, num_learners), H, W) carries the fog-of-war memory planes (memory.py, DESIGN.md section
+4.14) along: every step's update writes straight into slot t + 1 of a store beside the observations', `buf.memory` is the
+current slot's view and every batch has a "memory" entry.  Without it nothing is allocated or launched.
 """
 import ctypes as C
 
@@ -32,7 +36,7 @@ from ._lib import TRAJ_VALID, TrajCompactArgs, TrajGaeArgs, TrajGatherArgs, Traj
 
 
 class SelfPlayRolloutBuffer:
-    def __init__(self, env, horizon, gamma=0.99, gae_lambda=0.95):
+    def __init__(self, env, horizon, gamma=0.99, gae_lambda=0.95, memory=None):
         import torch
         if not getattr(env, "device_outputs", False):
             raise ValueError("SelfPlayRolloutBuffer needs an env built with device_outputs=True")
@@ -40,6 +44,9 @@ class SelfPlayRolloutBuffer:
             raise ValueError(f"horizon must be >= 1: {horizon}")
         if not (0.0 <= gamma <= 1.0 and 0.0 <= gae_lambda <= 1.0):
             raise ValueError(f"gamma and gae_lambda must lie in [0, 1]: {gamma}, {gae_lambda}")
+        want = ((env.num_envs, env.num_learners), env.board_height, env.board_width)
+        if memory is not None and (getattr(memory, "rows_shape", None), getattr(memory, "height", None), getattr(memory, "width", None)) != want:
+            raise ValueError(f"memory must be an ObservationMemory of rows_shape {want[0]} on a {want[2]}x{want[1]} board")
         self._t = t = torch
         self.env = env
         self.horizon = T = int(horizon)
@@ -49,7 +56,7 @@ class SelfPlayRolloutBuffer:
         self._dev = dev = env._dev
         self._L = load()
         H, W, nb = env.board_height, env.board_width, env.board_size
-        self.obs_floats, self.mask_bytes = 9 * nb, 5 * nb
+        self.obs_floats, self.mask_bytes, self.mem_floats = 9 * nb, 5 * nb, 4 * nb
         z = lambda shape, dt: t.zeros(shape, dtype=dt, device=dev)
         self.obs_store = z((T + 1, B, L, 9, H, W), t.float32)
         self.mask_store = z((T + 1, B, L, 5 * nb), t.uint8)
@@ -68,6 +75,8 @@ class SelfPlayRolloutBuffer:
                                    action=self.action.data_ptr(), logp=self.logp.data_ptr(), value=self.value.data_ptr(),
                                    reward=self.reward.data_ptr(), flags=self.flags.data_ptr())
         self._rec_ref = C.byref(self._rec)
+        self._memory = memory
+        self.mem_store = None if memory is None else z((T + 1, N, 4, nb), t.float32)
 
     # ---- collection ---------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -83,6 +92,13 @@ class SelfPlayRolloutBuffer:
         return self.obs_store[self._step]
 
     @property
+    def memory(self):
+        """The memory planes of the current observation [B, L, 4, H, W]: a view of slot t (None without memory=)."""
+        if self.mem_store is None:
+            return None
+        return self.mem_store[self._step].view(self._memory.shape)
+
+    @property
     def valid_actions_mask(self):
         return self.mask_store[self._step].view(self._t.bool)
 
@@ -91,6 +107,9 @@ class SelfPlayRolloutBuffer:
         self.obs_store[0].copy_(obs)
         self.mask_store[0].copy_(info["valid_actions_mask"].view(self._t.uint8))
         self.alive_state.fill_(1)
+        if self._memory is not None:
+            self._memory.reset_all()
+            self._memory.update(self.obs_store[0], out=self.mem_store[0])
         self._restart()
 
     def _restart(self):
@@ -119,6 +138,8 @@ class SelfPlayRolloutBuffer:
         r.reset, r.terminated, r.truncated, r.alive = (info["reset"].data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
                                                        info["alive"].data_ptr())
         check(self._L.gvec_traj_record(self._dev.index, self._stream(), self._rec_ref), "gvec_traj_record")
+        if self._memory is not None:                                    # a re-dealt env's rows restart from blank
+            self._memory.update(self.obs_store[k + 1], info["reset"], out=self.mem_store[k + 1])
         self._step = k + 1
         return out
 
@@ -161,13 +182,16 @@ class SelfPlayRolloutBuffer:
             o = self._out[m] = {"obs": e((m, 9, env.board_height, env.board_width), t.float32), "mask": e((m, self.mask_bytes), t.uint8),
                                 "action": e(m, t.int64), "logp": e(m, t.float32), "value": e(m, t.float32), "ret": e(m, t.float32),
                                 "adv": e(m, t.float32), "weight": e(m, t.float32)}
+            if self.mem_store is not None:
+                o["memory"] = e((m, 4, env.board_height, env.board_width), t.float32)
         return o
 
     def gather(self, pos, normalize=True):
         """The rows at positions pos (int64 CUDA tensor [M], p = t * N + b * L + l) as one batch: a dict of obs [M, 9, H, W],
         valid_actions_mask bool [M, 5 * H * W], action, logp, value, returns, advantages (normalised over the rollout's valid
         rows when `normalize`) and weight (1 for a valid row, 0 otherwise) [M].  The tensors are reused by the next gather of
-        the same M."""
+        the same M.  With memory=: also memory [M, 4, H, W], the planes stored at the same positions (a position outside the
+        rollout, which `rejected` counts and whose weight is 0, gets those of the nearest row)."""
         self._done()
         m = int(pos.numel())
         o = self._outputs(m)
@@ -179,8 +203,13 @@ class SelfPlayRolloutBuffer:
                            out_value=o["value"].data_ptr(), out_ret=o["ret"].data_ptr(), out_adv=o["adv"].data_ptr(),
                            out_weight=o["weight"].data_ptr(), rejected=self.rejected.data_ptr())
         check(self._L.gvec_traj_gather(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_gather")
-        return {"obs": o["obs"], "valid_actions_mask": o["mask"].view(self._t.bool), "action": o["action"], "logp": o["logp"],
-                "value": o["value"], "returns": o["ret"], "advantages": o["adv"], "weight": o["weight"], "index": pos}
+        batch = {"obs": o["obs"], "valid_actions_mask": o["mask"].view(self._t.bool), "action": o["action"], "logp": o["logp"],
+                 "value": o["value"], "returns": o["ret"], "advantages": o["adv"], "weight": o["weight"], "index": pos}
+        if self.mem_store is not None:
+            rows = self.mem_store.view(-1, self.mem_floats)[:self.horizon * self.num_streams]
+            self._t.index_select(rows, 0, pos.clamp(0, rows.shape[0] - 1), out=o["memory"].view(m, self.mem_floats))
+            batch["memory"] = o["memory"]
+        return batch
 
     def valid_positions(self):
         """(idx, count): the ascending positions of the valid rows in idx[:count] (gvec_traj_compact), count a Python int -
@@ -225,4 +254,6 @@ class SelfPlayRolloutBuffer:
         T = self.horizon
         self.obs_store[0].copy_(self.obs_store[T])
         self.mask_store[0].copy_(self.mask_store[T])
+        if self._memory is not None:
+            self._memory.move_to(self.mem_store[0])                     # its planes are slot T's: the last step wrote them there
         self._restart()

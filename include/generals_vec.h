@@ -770,6 +770,42 @@ typedef struct gvec_obs_features_args {
 } gvec_obs_features_args;
 int32_t gvec_obs_features(int32_t device, void* hip_stream, const gvec_obs_features_args* args);
 
+/* ---- fog-of-war memory planes: what a learner last saw of every tile -----------------------------------
+ * An observation shows owner and army of the tiles visible this turn only.  A memory row keeps, per tile, what the learner's
+ * last sight of it showed and how long ago that was: state that outlives one observation, carried by the caller from update to
+ * update.  Handle-free like the feature planes: DEVICE pointers on `device`, enqueued on hip_stream, nothing synchronises.
+ * One memory row, float32 [4][H*W], belongs to one learner's view; tile t = y*W + x:
+ *   0 seen        1.0 once the tile has been visible in this episode, else 0.0
+ *   1 last_owner  plane 1 of the observation in which the tile was last visible (0.5 mine, 1.0 somebody else's, 0.0 nobody's)
+ *   2 last_army   plane 2 (log(army + 1) / 10) of that same observation
+ *   3 age         min(k, cap) / cap, k the number of updates since the tile was last visible: 0 while it is visible, 1.0 while
+ *                 seen is 0
+ * The blank row is seen = 0, last_owner = 0, last_army = 0, age = 1.0.
+ * One update, (prev, obs, reset) -> out, per row r and tile:
+ *   base = the blank row when prev is NULL or reset[r / rows_per_flag] != 0, else prev[r].
+ *   visible (obs[r][0] != 0):  seen = 1.0, last_owner = obs[r][1], last_army = obs[r][2] (both copied bit for bit), age = 0.0.
+ *   not visible:               seen, last_owner and last_army are base's; age = min(base.age * cap + 1, cap) / cap when
+ *                              base.seen != 0, else 1.0.
+ * Planes 3 to 8 of the observation are not read.  EVERY element of out is written.  cap is a power of two, so every age is an
+ * exact float32 and base.age * cap an exact integer: the result is defined to the bit.
+ * obs float32 [rows][9][H*W], consecutive observations obs_row_stride floats apart; prev and out float32 [rows][4][H*W], dense.
+ * prev == out (in place) is allowed: a tile's result depends on that tile's inputs alone.  reset uint8 [rows / rows_per_flag]:
+ * one flag per rows_per_flag consecutive rows (the learners of one self-play env share its re-deal flag); NULL = no row restarts.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args, obs or out NULL, rows < 0 or
+ *   rows >= 2^31, width or height outside [1, GVEC_MAX_DIM], cap not a power of two in [2, 1024], rows_per_flag < 1 or not a
+ *   divisor of rows, obs_row_stride < 9*width*height, prev overlapping out without being equal to it.  rows == 0 is a no-op
+ *   that needs no device. */
+typedef struct gvec_obs_memory_args {
+  int64_t rows;
+  int32_t width, height, cap, rows_per_flag;
+  int64_t obs_row_stride;                                                                  /* floats, >= 9*width*height */
+  const float* obs;
+  const float* prev;                                                                       /* NULL: every row starts blank */
+  const uint8_t* reset;                                                                    /* NULL: no row restarts */
+  float* out;
+} gvec_obs_memory_args;
+int32_t gvec_obs_memory_update(int32_t device, void* hip_stream, const gvec_obs_memory_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
