@@ -10,6 +10,11 @@ observation, Huber loss, gradient clipping at 1.0, a hard target update, fixed p
 geometrically over the workers); the code is this repo's own.  An example, not part of the measured hot path.
 
     python examples/train_dqn_resident.py --num-envs 4096 --updates 200 [--prioritized] [--n-step 3]
+        [--masked-targets | --double | --categorical --atoms 51 --v-min -110 --v-max 110]
+
+--masked-targets bootstraps from the best LEGAL action of the next state (the mask is rebuilt from the sampled next
+observation: the ring stores none), --double picks that action with the online network (Double DQN), --categorical learns a
+distribution over --atoms returns per action (C51) with the same masked Double selection: q_targets.py, one launch per batch.
 """
 import argparse
 import json
@@ -23,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
+from generalsreinforcementlearning_amd.q_targets import categorical_target, double_q_target
 from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
@@ -38,6 +44,26 @@ class QNet(nn.Module):
     def forward(self, x):
         # five action planes (up, right, down, left, half) per tile -> the env's index tile * 5 + d
         return self.body(x).permute(0, 2, 3, 1).reshape(x.shape[0], self.n_actions)
+
+
+class CategoricalQNet(nn.Module):
+    """N atom logits per action.  The last 1x1 convolution has 5 * N channels and runs in channels_last, so its output read
+    as [B, H, W, 5, N] - which is [B, A, N] with the env's action index, atoms innermost - is a view: no permute copy."""
+
+    def __init__(self, obs_shape, n_actions, atoms, v_min, v_max, width=64):
+        super().__init__()
+        c, h, w = obs_shape
+        self.body = nn.Sequential(nn.Conv2d(c, width, 3, padding=1), nn.ReLU(), nn.Conv2d(width, width, 3, padding=1), nn.ReLU(),
+                                  nn.Conv2d(width, 5 * atoms, 1)).to(memory_format=torch.channels_last)
+        self.n_actions, self.atoms = n_actions, atoms
+        self.register_buffer("support", torch.linspace(v_min, v_max, atoms))
+
+    def forward(self, x):
+        y = self.body(x.contiguous(memory_format=torch.channels_last))
+        return y.permute(0, 2, 3, 1).reshape(x.shape[0], self.n_actions, self.atoms)
+
+    def expected(self, logits):
+        return (torch.softmax(logits, -1) * self.support).sum(-1)
 
 
 def main(argv=None):
@@ -59,12 +85,21 @@ def main(argv=None):
     ap.add_argument("--per-alpha", type=float, default=0.6)
     ap.add_argument("--per-beta", type=float, default=0.4)
     ap.add_argument("--n-step", type=int, default=1, help="multi-step targets: returns + discounts * (1 - dones) * max Q(next), from the ring's links")
+    ap.add_argument("--masked-targets", action="store_true", help="bootstrap from the best LEGAL action of the next state")
+    ap.add_argument("--double", action="store_true", help="Double DQN: the online network picks the next action among the legal ones")
+    ap.add_argument("--categorical", action="store_true", help="C51: a distribution over --atoms returns per action, masked Double targets")
+    ap.add_argument("--atoms", type=int, default=51)
+    ap.add_argument("--v-min", type=float, default=-110.0, help="the support's bounds: the default covers the env's terminal +-100")
+    ap.add_argument("--v-max", type=float, default=110.0)
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
     dev = torch.device("cuda", 0)
     B, n_actions, obs_shape = a.num_envs, a.board * a.board * 5, (9, a.board, a.board)
-    q, target = QNet(obs_shape, n_actions).to(dev), QNet(obs_shape, n_actions).to(dev)
+    if a.categorical:
+        q, target = (CategoricalQNet(obs_shape, n_actions, a.atoms, a.v_min, a.v_max).to(dev) for _ in range(2))
+    else:
+        q, target = QNet(obs_shape, n_actions).to(dev), QNet(obs_shape, n_actions).to(dev)
     target.load_state_dict(q.state_dict())
     opt = torch.optim.Adam(q.parameters(), lr=a.lr)
     # one fixed exploration rate per worker, eps_base ** (1 .. 8) across the pool
@@ -72,7 +107,10 @@ def main(argv=None):
 
     def policy(states, masks, _workers, gen):
         with torch.no_grad():
-            qv = q(states).masked_fill(~masks, float("-inf"))
+            qv = q(states)
+            if a.categorical:
+                qv = q.expected(qv)             # greedy over expected values
+            qv = qv.masked_fill(~masks, float("-inf"))
             greedy = qv.argmax(1)
             explore = (masks * torch.rand(masks.shape, device=dev, generator=gen)).argmax(1)      # a uniform valid action
             return torch.where(torch.rand(B, device=dev, generator=gen) < eps, explore, greedy)
@@ -100,14 +138,28 @@ def main(argv=None):
             else:
                 s, act, r, ns, d = buf.sample_arrays(a.batch_size)
             disc = a.gamma
-        with torch.no_grad():
-            tq = r.float() + disc * target(ns).max(1).values * (~d).float()
-        qsa = q(s).gather(1, act[:, None]).squeeze(1)
-        if a.prioritized:
-            loss = (weights * F.smooth_l1_loss(qsa, tq, reduction="none")).mean()
-            buf.update_priorities(slots, (qsa.detach() - tq))
+        if a.categorical:
+            with torch.no_grad():               # the projected distribution of the best legal next action (picked by the online net)
+                m, _ = categorical_target(ns, target(ns), r, disc, d, a.v_min, a.v_max, logits_select=q(ns))
+            logp = F.log_softmax(q(s)[torch.arange(len(act), device=dev), act], -1)
+            ce = -(m * logp).sum(-1)            # per row: the loss, and the priority
+            if a.prioritized:
+                loss = (weights * ce).mean()
+                buf.update_priorities(slots, ce.detach())
+            else:
+                loss = ce.mean()
         else:
-            loss = F.smooth_l1_loss(qsa, tq)
+            with torch.no_grad():
+                if a.masked_targets or a.double:
+                    tq, _ = double_q_target(ns, target(ns), r, disc, d, q_select=q(ns) if a.double else None)
+                else:
+                    tq = r.float() + disc * target(ns).max(1).values * (~d).float()
+            qsa = q(s).gather(1, act[:, None]).squeeze(1)
+            if a.prioritized:
+                loss = (weights * F.smooth_l1_loss(qsa, tq, reduction="none")).mean()
+                buf.update_priorities(slots, (qsa.detach() - tq))
+            else:
+                loss = F.smooth_l1_loss(qsa, tq)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         nn.utils.clip_grad_norm_(q.parameters(), 1.0)
@@ -122,6 +174,8 @@ def main(argv=None):
     out = {"updates": a.updates, "env_steps": pool.total_env_steps, "episodes": pool.total_episodes, "seconds": dt,
            "env_steps_per_s": a.updates * a.collect_per_update * B / dt, "updates_per_s": a.updates / dt, "loss": losses,
            "mean_episode_reward": sum(x[0] for x in results) / max(len(results), 1), "ring_fill": len(buf), "n_step": a.n_step}
+    if a.categorical or a.masked_targets or a.double:
+        out["targets"] = f"categorical{a.atoms}" if a.categorical else "double" if a.double else "masked"
     pool._env.close()
     print(json.dumps(out))
     return out

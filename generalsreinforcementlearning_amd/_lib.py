@@ -100,6 +100,27 @@ class ObsMemoryArgs(C.Structure):
                 + [("obs_row_stride", C.c_int64)] + [(n, C.c_void_p) for n in ("obs", "prev", "reset", "out")])
 
 
+class ObsValidMaskArgs(C.Structure):
+    """gvec_obs_valid_mask_args (include/generals_vec.h): obs and mask are device memory."""
+    _fields_ = [("rows", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("obs_row_stride", C.c_int64), ("obs", C.c_void_p),
+                ("mask", C.c_void_p)]
+
+
+class QTargetArgs(C.Structure):
+    """gvec_q_target_args (include/generals_vec.h): every pointer is device memory; q_select, discount and next_value may be None."""
+    _fields_ = ([("rows", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("obs_row_stride", C.c_int64), ("gamma", C.c_float),
+                 ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("next_obs", "q_eval", "q_select", "reward", "discount", "done", "target", "next_action",
+                                             "next_value")])
+
+
+class CategoricalTargetArgs(C.Structure):
+    """gvec_categorical_target_args (include/generals_vec.h): every pointer is device memory; logits_select and discount may be None."""
+    _fields_ = ([("rows", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("obs_row_stride", C.c_int64), ("num_atoms", C.c_int32),
+                 ("gamma", C.c_float), ("v_min", C.c_float), ("v_max", C.c_float)]
+                + [(n, C.c_void_p) for n in ("next_obs", "logits_eval", "logits_select", "reward", "discount", "done", "m", "next_action")])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -170,6 +191,9 @@ SYMBOLS = {
     "gvec_policy_backward": (_i32, [_i32, _vp, C.POINTER(PolicyBackwardArgs)]),
     "gvec_obs_features": (_i32, [_i32, _vp, C.POINTER(ObsFeaturesArgs)]),
     "gvec_obs_memory_update": (_i32, [_i32, _vp, C.POINTER(ObsMemoryArgs)]),
+    "gvec_obs_valid_mask": (_i32, [_i32, _vp, C.POINTER(ObsValidMaskArgs)]),
+    "gvec_q_target": (_i32, [_i32, _vp, C.POINTER(QTargetArgs)]),
+    "gvec_categorical_target": (_i32, [_i32, _vp, C.POINTER(CategoricalTargetArgs)]),
     "gvec_gym_observe":(_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -334,6 +334,31 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return rdlane(wave_scan_add(v), 63); }
 __device__ __forceinline__ bool wave_any(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
+// float reductions as fixed xor butterflies: every lane ends with the same value, and the same input gives the same bits
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float o = __shfl_xor(x, off, 64);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+  return x;
+}
+// the greatest value, the lowest index among equals; every lane ends with the same pair
+__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(idx, off, 64);
+    const bool take = ov > v || (ov == v && oi < idx);
+    v = take ? ov : v;
+    idx = take ? oi : idx;
+  }
+}
 __device__ __forceinline__ uint32_t bperm(int byte_addr, uint32_t v) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
 }

@@ -313,4 +313,9 @@ hipError_t launch_obs_features(const gvec_obs_features_args& a, hipStream_t s);
 // fog-of-war memory planes (gvec_memory.hip; generals_vec.h "fog-of-war memory planes")
 hipError_t launch_obs_memory(const gvec_obs_memory_args& a, hipStream_t s);
 
+// masked Q targets from next observations (gvec_qtarget.hip; generals_vec.h "masked Q targets")
+hipError_t launch_obs_valid_mask(const gvec_obs_valid_mask_args& a, hipStream_t s);
+hipError_t launch_q_target(const gvec_q_target_args& a, hipStream_t s);
+hipError_t launch_categorical_target(const gvec_categorical_target_args& a, hipStream_t s);
+
 }  // namespace gvec

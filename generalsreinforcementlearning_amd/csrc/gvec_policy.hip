@@ -19,31 +19,6 @@ constexpr int NO_INDEX = 0x7FFFFFFF;
 
 __device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63u); }
 
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float o = __shfl_xor(x, off, 64);
-    x = o > x ? o : x;
-  }
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-  return x;
-}
-// the greatest value, the lowest index among equals; every lane ends with the same pair
-__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float ov = __shfl_xor(v, off, 64);
-    const int oi = __shfl_xor(idx, off, 64);
-    const bool take = ov > v || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-  }
-}
-
 // ---- the draws (DESIGN.md §6 "Policy head") ----
 __host__ __device__ __forceinline__ uint32_t policy_row_key(uint32_t base, long long row) {
   const uint32_t lo = (uint32_t)(unsigned long long)row, hi = (uint32_t)((unsigned long long)row >> 32);

@@ -806,6 +806,70 @@ typedef struct gvec_obs_memory_args {
 } gvec_obs_memory_args;
 int32_t gvec_obs_memory_update(int32_t device, void* hip_stream, const gvec_obs_memory_args* args);
 
+/* ---- masked Q targets from next observations: Double DQN and categorical (C51) ----------------------
+ * A replay row holds (s, a, r, ns, d) and no legal-action mask of ns; the mask is a pure function of ns, so the bootstrap can
+ * run over the legal actions alone.  Handle-free like the feature planes: DEVICE pointers on `device`, enqueued on hip_stream,
+ * nothing synchronises.  Observations are float32 [rows][9][H*W], obs_row_stride floats apart, tile t = y*W + x; A = 5*H*W.
+ * The legal set S of an observation (GeneralsEnv._get_valid_actions_mask restated on planes 1, 2 and 4, the others unread):
+ *   tile t is a source iff obs[1][t] == 0.5 and obs[2][t] > 0.09 (an army of 1 shows as ln(2)/10 = 0.0693, of 2 as 0.1099);
+ *   a tile is passable iff obs[4][tile] == 0;  action 5*t + d, d < 4 (up, right, down, left: (x, y-1), (x+1, y), (x, y+1),
+ *   (x-1, y)), is legal iff t is a source and that neighbour is on the board and passable;  5*t + 4 (the half move) iff any of
+ *   the four is.
+ * The argmax of both targets: over i in S in any order, i wins iff v_i > best or (v_i == best and i < index), starting from
+ *   (-inf, none): the greatest value, the lowest index among equals; a NaN never wins; an all -inf legal set picks its lowest.
+ * Values at actions outside S are never loaded: they may hold anything.  discount float32 [rows] (gamma ** steps of an n-step
+ * row), or NULL = the scalar gamma for every row.  done uint8 [rows].  The same input gives the same bits on every call.
+ * gvec_obs_valid_mask: mask uint8 [rows][A], 1 where the action is in S else 0 - the bytes of info["valid_actions_mask"].
+ * gvec_q_target: q_eval, q_select float32 [rows][A]; q_select NULL = q_eval (plain masked DQN; given = Double DQN).
+ *   a* = argmax_S q_select.  next_action int64 [rows] = a*, or -1 when nothing won.  When nothing won or done[r] != 0:
+ *   next_value = 0 and target = reward[r].  Otherwise next_value = q_eval[a*], target = reward + discount * next_value: one
+ *   rounded float32 multiply, then one rounded float32 add (never an fma).  next_value float32 [rows] may be NULL.
+ * gvec_categorical_target: logits_eval, logits_select float32 [rows][A][N], atoms innermost, finite at the legal actions;
+ *   logits_select NULL = logits_eval.  N = num_atoms in [2, 64], support z_j = v_min + j * D, D = (v_max - v_min) / (N - 1).
+ *   For i in S: p_i = softmax(logits_select[i]), Q_i = sum_j p_ij z_j;  a* = argmax_S Q_i;  p* = softmax(logits_eval[a*]).
+ *   Tz_j = clamp(reward + discount * z_j, v_min, v_max), b_j = (Tz_j - v_min) / D, m_k = sum_j p*_j max(0, 1 - |b_j - k|),
+ *   summed in ascending j: the gather form of the C51 projection, no atomics.  done[r] != 0 or nothing won: m is the projected
+ *   point mass at clamp(reward, v_min, v_max), and no logits of a done row are read: its next_action is -1.
+ *   m float32 [rows][N], next_action int64 [rows].  float32 throughout.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL (all but
+ *   q_select / logits_select, discount and next_value), rows < 0 or rows >= 2^31, width or height outside [1, GVEC_MAX_DIM],
+ *   obs_row_stride < 9*width*height, reserved != 0, num_atoms outside [2, 64], v_min or v_max not finite or v_min >= v_max.
+ *   rows == 0 is a no-op that needs no device. */
+typedef struct gvec_obs_valid_mask_args {
+  int64_t rows;
+  int32_t width, height;
+  int64_t obs_row_stride;                                                                  /* floats, >= 9*width*height */
+  const float* obs; uint8_t* mask;
+} gvec_obs_valid_mask_args;
+typedef struct gvec_q_target_args {
+  int64_t rows;
+  int32_t width, height;
+  int64_t obs_row_stride;
+  float gamma; int32_t reserved;
+  const float* next_obs; const float* q_eval;
+  const float* q_select;                                                                   /* NULL: q_eval */
+  const float* reward;
+  const float* discount;                                                                   /* NULL: gamma */
+  const uint8_t* done;
+  float* target; int64_t* next_action;
+  float* next_value;                                                                       /* NULL: not wanted */
+} gvec_q_target_args;
+typedef struct gvec_categorical_target_args {
+  int64_t rows;
+  int32_t width, height;
+  int64_t obs_row_stride;
+  int32_t num_atoms; float gamma, v_min, v_max;
+  const float* next_obs; const float* logits_eval;
+  const float* logits_select;                                                              /* NULL: logits_eval */
+  const float* reward;
+  const float* discount;                                                                   /* NULL: gamma */
+  const uint8_t* done;
+  float* m; int64_t* next_action;
+} gvec_categorical_target_args;
+int32_t gvec_obs_valid_mask(int32_t device, void* hip_stream, const gvec_obs_valid_mask_args* args);
+int32_t gvec_q_target(int32_t device, void* hip_stream, const gvec_q_target_args* args);
+int32_t gvec_categorical_target(int32_t device, void* hip_stream, const gvec_categorical_target_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
