@@ -132,7 +132,7 @@ class GymVecEnvBase:
         """The cap when the option is on, else None.  Checked before anything touches a device."""
         if not strategic_features:
             return None
-        from .features import check_cap
+        from ._obs_batch import check_cap
         if not device_outputs:
             raise ValueError("strategic_features=True needs device_outputs=True: the planes are computed on the device from the "
                              "observation tensor the step wrote")

@@ -21,7 +21,7 @@ SRCS = ["gvec_kernels.hip", "gvec_gym.hip", "gvec_experience.hip", "gvec_state.h
         "gvec_qtarget.hip",
         # the C ABI, host only: an edit to an entry point's checks recompiles no kernel
         "gvec_api.hip", "gvec_api_engine.hip", "gvec_api_state.hip", "gvec_api_experience.hip", "gvec_api_gym.hip", "gvec_api_replay.hip",
-        "gvec_api_features.hip", "gvec_api_memory.hip", "gvec_api_qtarget.hip"]
+        "gvec_api_obs.hip"]
 DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_handle.hpp", "gvec_dispatch.hpp", "gvec_turn.hpp", "gvec_gym_emit.hpp", "gvec_collect.hpp",
         "go_rand_cooked.inc", os.path.join(ROOT, "include", "generals_vec.h")]
 HOST_DEPS = ["gvec_handle.hpp"]  # included by the gvec_api* units alone: an edit to it recompiles no kernel either

@@ -15,20 +15,11 @@ stream; nothing synchronises with the host.
 """
 import ctypes as C
 
+from . import _obs_batch as ob
 from ._lib import ObsFeaturesArgs, check, load
 
 NUM_STRATEGIC_FEATURES = 5
 STRATEGIC_FEATURE_NAMES = ("dist_own_general", "dist_enemy", "dist_city", "dist_fog", "front_line")
-MAX_DIM = 32          # GVEC_MAX_DIM
-
-
-def check_cap(cap):
-    """cap as an int, or ValueError: a power of two in [2, 1024] (what makes every output value an exact float32)."""
-    if isinstance(cap, bool) or not isinstance(cap, int):
-        raise TypeError(f"cap must be an int, not {type(cap).__name__}")
-    if cap < 2 or cap > 1024 or cap & (cap - 1):
-        raise ValueError(f"cap must be a power of two in [2, 1024], not {cap}")
-    return cap
 
 
 def strategic_features(obs, cap=64, out=None, width=None, height=None):
@@ -41,67 +32,22 @@ def strategic_features(obs, cap=64, out=None, width=None, height=None):
     The features are not differentiable with respect to obs: the result carries no autograd graph.
     ValueError / TypeError before any launch: a CPU tensor, another dtype, a plane count other than 9, a bad cap."""
     import torch
-    cap = check_cap(cap)
-    if not isinstance(obs, torch.Tensor):
-        raise TypeError(f"obs must be a torch.Tensor, not {type(obs).__name__}")
-    if obs.dtype != torch.float32:
-        raise TypeError(f"obs must be float32, not {obs.dtype}")
-    if not obs.is_cuda:
-        raise ValueError("obs must be a CUDA tensor: the features are computed by a HIP kernel (there is no host path)")
+    cap = ob.check_cap(cap)
+    ob.check_tensor(obs, "obs", (torch.float32,))
+    # the device before the shape: a CPU tensor is refused as such
+    dev = ob.check_device("the features are computed by a HIP kernel", "obs", obs=obs)
     flat = width is not None or height is not None
-    if flat:
-        if width is None or height is None:
-            raise ValueError("width and height go together")
-        W, H = int(width), int(height)
-        if obs.dim() < 2 or obs.shape[-2] != 9 or obs.shape[-1] != W * H:
-            raise ValueError(f"obs {tuple(obs.shape)} is not [..., 9, {H} * {W}]")
-        lead, tail = tuple(obs.shape[:-2]), 2
-    else:
-        if obs.dim() < 3 or obs.shape[-3] != 9:
-            raise ValueError(f"obs {tuple(obs.shape)} is not [..., 9, H, W]")
-        H, W = int(obs.shape[-2]), int(obs.shape[-1])
-        lead, tail = tuple(obs.shape[:-3]), 3
-    if not (1 <= W <= MAX_DIM and 1 <= H <= MAX_DIM):
-        raise ValueError(f"board {W}x{H}: width and height must be in [1, {MAX_DIM}]")
-    rows = 1
-    for d in lead:
-        rows *= int(d)
+    if flat and (width is None or height is None):
+        raise ValueError("width and height go together")
+    lead, rows, H, W = ob.read_shape(obs, "obs", width, height)
     out_shape = lead + ((5, W * H) if flat else (5, H, W))
-    obs = obs.detach()
-    stride = _row_stride(obs, tail, 9 * W * H)
-    if stride is None:
-        obs = obs.contiguous()
-        stride = 9 * W * H
+    obs, stride = ob.in_place(obs, 2 if flat else 3, H, W)
     if out is None:
-        out = torch.empty(out_shape, dtype=torch.float32, device=obs.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == obs.device and out.dtype == torch.float32
-              and out.is_contiguous() and out.numel() == rows * 5 * W * H):
-        raise ValueError(f"out must be a contiguous float32 CUDA tensor of {rows * 5 * W * H} elements on {obs.device}")
+        out = torch.empty(out_shape, dtype=torch.float32, device=dev)
+    else:
+        ob.check_out(out, "out", (torch.float32,), "float32", rows * 5 * W * H, dev)
     if rows:
         a = ObsFeaturesArgs(rows=rows, width=W, height=H, cap=cap, reserved=0, obs_row_stride=stride, obs=obs.data_ptr(),
                             out=out.data_ptr())
-        check(load().gvec_obs_features(obs.device.index, torch.cuda.current_stream(obs.device).cuda_stream, C.byref(a)),
-              "gvec_obs_features")
+        check(load().gvec_obs_features(dev.index, ob.stream(dev), C.byref(a)), "gvec_obs_features")
     return out.view(out_shape)
-
-
-def _row_stride(obs, tail, row_floats):
-    """Floats between consecutive observations when obs can be read in place, else None."""
-    shape, strides = tuple(obs.shape), tuple(obs.stride())
-    expect = 1
-    for n, s in zip(reversed(shape[-tail:]), reversed(strides[-tail:])):      # the planes of one observation: dense
-        if n != 1 and s != expect:
-            return None
-        expect *= n
-    lead = [(n, s) for n, s in zip(shape[:-tail], strides[:-tail]) if n != 1]
-    if not lead:
-        return row_floats
-    stride = lead[-1][1]
-    if stride < row_floats:
-        return None
-    expect = stride
-    for n, s in reversed(lead):                                                  # the leading dimensions: one common stride
-        if s != expect:
-            return None
-        expect *= n
-    return stride

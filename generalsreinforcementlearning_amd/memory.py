@@ -19,8 +19,8 @@ observations.
 """
 import ctypes as C
 
+from . import _obs_batch as ob
 from ._lib import ObsMemoryArgs, check, load
-from .features import MAX_DIM, _row_stride, check_cap
 
 NUM_MEMORY_PLANES = 4
 MEMORY_PLANE_NAMES = ("seen", "last_owner", "last_army", "age")
@@ -44,15 +44,14 @@ class ObservationMemory:
         the first observation's).  Nothing is allocated until the planes are read or updated."""
         import torch
         self._t = torch
-        self.cap = check_cap(cap)
+        self.cap = ob.check_cap(cap)
         if isinstance(rows_shape, int) and not isinstance(rows_shape, bool):
             rows_shape = (rows_shape,)
         if not all(isinstance(n, int) and not isinstance(n, bool) and n >= 0 for n in rows_shape):
             raise ValueError(f"rows_shape {rows_shape!r} must be a tuple of ints >= 0")
         self.rows_shape = tuple(rows_shape)
         self.height, self.width = H, W = int(height), int(width)
-        if not (1 <= W <= MAX_DIM and 1 <= H <= MAX_DIM):
-            raise ValueError(f"board {W}x{H}: width and height must be in [1, {MAX_DIM}]")
+        ob.check_board(W, H)
         self.rows = 1
         for n in self.rows_shape:
             self.rows *= n
@@ -95,12 +94,7 @@ class ObservationMemory:
         return self._planes
 
     def _check_out(self, out, dev):
-        t = self._t
-        n = self.rows * NUM_MEMORY_PLANES * self.height * self.width
-        if not (isinstance(out, t.Tensor) and out.is_cuda and out.device == dev and out.dtype == t.float32 and out.is_contiguous()
-                and out.numel() == n):
-            raise ValueError(f"out must be a contiguous float32 CUDA tensor of {n} elements on {dev}")
-        return out
+        return ob.check_out(out, "out", (self._t.float32,), "float32", self.rows * NUM_MEMORY_PLANES * self.height * self.width, dev)
 
     # ---- the update ---------------------------------------------------------------------------------------------------
     def update(self, obs, reset=None, out=None):
@@ -113,25 +107,18 @@ class ObservationMemory:
         t = self._t
         H, W = self.height, self.width
         # types and shapes first, devices after: a wrong shape is reported as such whatever holds the tensor
-        if not isinstance(obs, t.Tensor):
-            raise TypeError(f"obs must be a torch.Tensor, not {type(obs).__name__}")
-        if obs.dtype != t.float32:
-            raise TypeError(f"obs must be float32, not {obs.dtype}")
+        ob.check_tensor(obs, "obs", (t.float32,))
         if tuple(obs.shape) != self.rows_shape + (9, H, W):
             raise ValueError(f"obs {tuple(obs.shape)} is not {self.rows_shape + (9, H, W)}")
         rows_per_flag = 1
         if reset is not None:
-            if not isinstance(reset, t.Tensor):
-                raise TypeError(f"reset must be a torch.Tensor, not {type(reset).__name__}")
-            if reset.dtype not in (t.bool, t.uint8):
-                raise TypeError(f"reset must be bool or uint8, not {reset.dtype}")
+            ob.check_tensor(reset, "reset", (t.bool, t.uint8))
             k = reset.dim()
             if tuple(reset.shape) != self.rows_shape[:k]:
                 raise ValueError(f"reset {tuple(reset.shape)} is no leading prefix of rows_shape {self.rows_shape}")
             for n in self.rows_shape[k:]:
                 rows_per_flag *= n
-        if not obs.is_cuda:
-            raise ValueError("obs must be a CUDA tensor: the planes are updated by a HIP kernel (there is no host path)")
+        ob.check_device("the planes are updated by a HIP kernel", "obs", obs=obs)
         if self._dev is None or self._dev.index is None:
             self._dev = obs.device
         dev = self._dev
@@ -143,19 +130,14 @@ class ObservationMemory:
             reset = reset.contiguous()
         if out is not None:
             out = self._check_out(out, dev)
-        obs = obs.detach()
-        stride = _row_stride(obs, 3, 9 * W * H)
-        if stride is None:
-            obs = obs.contiguous()
-            stride = 9 * W * H
+        obs, stride = ob.in_place(obs, 3, H, W)
         prev = self._planes
         if out is None:
             out = prev if prev is not None else t.empty(self.shape, dtype=t.float32, device=dev)
         if self.rows:
             a = ObsMemoryArgs(rows=self.rows, width=W, height=H, cap=self.cap, rows_per_flag=rows_per_flag, obs_row_stride=stride,
-                              obs=obs.data_ptr(), prev=None if prev is None else prev.data_ptr(),
-                              reset=None if reset is None else reset.data_ptr(), out=out.data_ptr())
-            check(load().gvec_obs_memory_update(dev.index, t.cuda.current_stream(dev).cuda_stream, C.byref(a)), "gvec_obs_memory_update")
+                              obs=obs.data_ptr(), prev=ob.ptr(prev), reset=ob.ptr(reset), out=out.data_ptr())
+            check(load().gvec_obs_memory_update(dev.index, ob.stream(dev), C.byref(a)), "gvec_obs_memory_update")
         self._planes = out.view(self.shape)
         return self._planes
 

@@ -15,8 +15,8 @@ The categorical loss stays in torch: gather the taken action's N logits, log_sof
 import ctypes as C
 import math
 
+from . import _obs_batch as ob
 from ._lib import CategoricalTargetArgs, ObsValidMaskArgs, QTargetArgs, check, load
-from .features import MAX_DIM, _row_stride
 
 MAX_ATOMS = 64        # one lane per atom
 
@@ -24,39 +24,19 @@ MAX_ATOMS = 64        # one lane per atom
 def _observations(obs, name):
     """(leading shape, rows, H, W) of observations [..., 9, H, W], or TypeError / ValueError"""
     import torch
-    if not isinstance(obs, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor, not {type(obs).__name__}")
-    if obs.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, not {obs.dtype}")
-    if obs.dim() < 3 or obs.shape[-3] != 9:
-        raise ValueError(f"{name} {tuple(obs.shape)} is not [..., 9, H, W]")
-    H, W = int(obs.shape[-2]), int(obs.shape[-1])
-    if not (1 <= W <= MAX_DIM and 1 <= H <= MAX_DIM):
-        raise ValueError(f"board {W}x{H}: width and height must be in [1, {MAX_DIM}]")
-    lead = tuple(obs.shape[:-3])
-    rows = 1
-    for d in lead:
-        rows *= int(d)
-    return lead, rows, H, W
+    ob.check_tensor(obs, name, (torch.float32,))
+    return ob.read_shape(obs, name)
 
 
-def _in_place(obs, H, W):
-    """(obs to read, its row stride in floats): obs itself where strategic_features would read it in place, else a copy"""
-    obs = obs.detach()
-    stride = _row_stride(obs, 3, 9 * W * H)
-    return (obs, stride) if stride is not None else (obs.contiguous(), 9 * W * H)
+def _same_device(obs_name, **tensors):
+    """every tensor is on the CUDA device of the first (the observations): checked last, so that a CPU-only box still sees
+    every other refusal"""
+    return ob.check_device("the targets are computed by HIP kernels", obs_name, **tensors)
 
 
 def _shaped(t, name, shape, dtypes):
     """checks the type, dtype (a tuple of dtypes, or None = any floating-point) and shape of one argument"""
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
-    if dtypes is None:
-        if not t.is_floating_point():
-            raise TypeError(f"{name} must be a floating-point tensor, not {t.dtype}")
-    elif t.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, not {t.dtype}")
+    ob.check_tensor(t, name, dtypes)
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} {tuple(t.shape)} is not {tuple(shape)}")
 
@@ -76,21 +56,6 @@ def _per_row(reward, discount, done, lead):
     return discount, gamma
 
 
-def _same_device(obs_name, **tensors):
-    """every tensor is on the CUDA device of the first (the observations): checked last, so that a CPU-only box still sees
-    every other refusal"""
-    dev = None
-    for name, t in tensors.items():
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a CUDA tensor: the targets are computed by HIP kernels (there is no host path)")
-        dev = dev or t.device
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, {obs_name} on {dev}")
-    return dev
-
-
 def _f32(t):
     import torch
     return None if t is None else t.detach().to(torch.float32).contiguous()
@@ -100,15 +65,6 @@ def _u8(done):
     import torch
     done = done.detach().contiguous()
     return done.view(torch.uint8) if done.dtype == torch.bool else done
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    import torch
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def valid_actions_mask_from_observation(obs, out=None):
@@ -122,16 +78,15 @@ def valid_actions_mask_from_observation(obs, out=None):
     import torch
     lead, rows, H, W = _observations(obs, "obs")
     dev = _same_device("obs", obs=obs)
-    obs, stride = _in_place(obs, H, W)
+    obs, stride = ob.in_place(obs, 3, H, W)
     A = 5 * H * W
     if out is None:
         out = torch.empty(lead + (A,), dtype=torch.bool, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype in (torch.bool, torch.uint8)
-              and out.is_contiguous() and out.numel() == rows * A):
-        raise ValueError(f"out must be a contiguous bool or uint8 CUDA tensor of {rows * A} elements on {dev}")
+    else:
+        ob.check_out(out, "out", (torch.bool, torch.uint8), "bool or uint8", rows * A, dev)
     if rows:
         a = ObsValidMaskArgs(rows=rows, width=W, height=H, obs_row_stride=stride, obs=obs.data_ptr(), mask=out.data_ptr())
-        check(load().gvec_obs_valid_mask(dev.index, _stream(dev), C.byref(a)), "gvec_obs_valid_mask")
+        check(load().gvec_obs_valid_mask(dev.index, ob.stream(dev), C.byref(a)), "gvec_obs_valid_mask")
     out = out.view(lead + (A,))
     return out if out.dtype == torch.bool else out.view(torch.bool)
 
@@ -155,16 +110,16 @@ def double_q_target(next_obs, q_eval, reward, discount, done, q_select=None, ret
         _shaped(q_select, "q_select", lead + (A,), (torch.float32,))
     disc, gamma = _per_row(reward, discount, done, lead)
     dev = _same_device("next_obs", next_obs=next_obs, q_eval=q_eval, q_select=q_select, reward=reward, discount=disc, done=done)
-    obs, stride = _in_place(next_obs, H, W)
+    obs, stride = ob.in_place(next_obs, 3, H, W)
     q_eval, q_select, reward, disc, done = _f32(q_eval), _f32(q_select), _f32(reward), _f32(disc), _u8(done)
     target = torch.empty(lead, dtype=torch.float32, device=dev)
     action = torch.empty(lead, dtype=torch.int64, device=dev)
     value = torch.empty(lead, dtype=torch.float32, device=dev) if return_next_value else None
     if rows:
         a = QTargetArgs(rows=rows, width=W, height=H, obs_row_stride=stride, gamma=gamma, reserved=0, next_obs=obs.data_ptr(),
-                        q_eval=q_eval.data_ptr(), q_select=_ptr(q_select), reward=reward.data_ptr(), discount=_ptr(disc),
-                        done=done.data_ptr(), target=target.data_ptr(), next_action=action.data_ptr(), next_value=_ptr(value))
-        check(load().gvec_q_target(dev.index, _stream(dev), C.byref(a)), "gvec_q_target")
+                        q_eval=q_eval.data_ptr(), q_select=ob.ptr(q_select), reward=reward.data_ptr(), discount=ob.ptr(disc),
+                        done=done.data_ptr(), target=target.data_ptr(), next_action=action.data_ptr(), next_value=ob.ptr(value))
+        check(load().gvec_q_target(dev.index, ob.stream(dev), C.byref(a)), "gvec_q_target")
     return (target, action, value) if return_next_value else (target, action)
 
 
@@ -204,14 +159,14 @@ def categorical_target(next_obs, logits_eval, reward, discount, done, v_min, v_m
     disc, gamma = _per_row(reward, discount, done, lead)
     dev = _same_device("next_obs", next_obs=next_obs, logits_eval=logits_eval, logits_select=logits_select, reward=reward,
                        discount=disc, done=done)
-    obs, stride = _in_place(next_obs, H, W)
+    obs, stride = ob.in_place(next_obs, 3, H, W)
     logits_eval, logits_select, reward, disc, done = _f32(logits_eval), _f32(logits_select), _f32(reward), _f32(disc), _u8(done)
     m = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
     action = torch.empty(lead, dtype=torch.int64, device=dev)
     if rows:
         a = CategoricalTargetArgs(rows=rows, width=W, height=H, obs_row_stride=stride, num_atoms=N, gamma=gamma, v_min=v_min,
                                   v_max=v_max, next_obs=obs.data_ptr(), logits_eval=logits_eval.data_ptr(),
-                                  logits_select=_ptr(logits_select), reward=reward.data_ptr(), discount=_ptr(disc),
+                                  logits_select=ob.ptr(logits_select), reward=reward.data_ptr(), discount=ob.ptr(disc),
                                   done=done.data_ptr(), m=m.data_ptr(), next_action=action.data_ptr())
-        check(load().gvec_categorical_target(dev.index, _stream(dev), C.byref(a)), "gvec_categorical_target")
+        check(load().gvec_categorical_target(dev.index, ob.stream(dev), C.byref(a)), "gvec_categorical_target")
     return m, action

@@ -21,6 +21,7 @@ import numpy as np
 
 from ._gym_base import GymVecEnvBase
 from ._lib import check
+from ._obs_batch import check_out
 
 
 class GeneralsSelfPlayVecEnv(GymVecEnvBase):
@@ -73,13 +74,8 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
     def _slot_args(self, k, obs_out, mask_out):
         """_step_args for a step that writes its observation and mask into the caller's tensors (zero-copy slots)."""
         t, B, L = self._t, self.num_envs, self.num_learners
-        n = B * L * 9 * self.board_size
-        if not (isinstance(obs_out, t.Tensor) and obs_out.is_cuda and obs_out.device == self._dev and obs_out.dtype == t.float32
-                and obs_out.is_contiguous() and obs_out.numel() == n):
-            raise ValueError(f"obs_out must be a contiguous float32 CUDA tensor of {n} elements on {self._dev}")
-        if not (isinstance(mask_out, t.Tensor) and mask_out.is_cuda and mask_out.device == self._dev
-                and mask_out.dtype in (t.uint8, t.bool) and mask_out.is_contiguous() and mask_out.numel() == B * L * self.board_size * 5):
-            raise ValueError(f"mask_out must be a contiguous uint8 / bool CUDA tensor of {B * L * self.board_size * 5} elements on {self._dev}")
+        check_out(obs_out, "obs_out", (t.float32,), "float32", B * L * 9 * self.board_size, self._dev)
+        check_out(mask_out, "mask_out", (t.uint8, t.bool), "uint8 / bool", B * L * self.board_size * 5, self._dev)
         ptrs, _, out, info = self._step_args(k, self._obs_flip)
         obs = obs_out.view(B, L, 9, self.board_height, self.board_width)
         info = dict(info)

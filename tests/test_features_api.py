@@ -1,5 +1,6 @@
 """The argument checks of gvec_obs_features and of its Python front (features.strategic_features, the envs' option).  They run
-before anything touches a device, so they are pinned here without one."""
+before anything touches a device, so they are pinned here without one.  The checks it shares with the other observation-batch
+entry points (null arguments, rows, board, row stride) are in test_qtarget_api.py's table."""
 import ctypes as C
 
 import pytest
@@ -35,22 +36,6 @@ def test_struct_layout_matches_the_header():
             f.out.offset) == (0, 8, 12, 16, 20, 24, 32, 40)
 
 
-def test_null_arguments(L):
-    _rejected(L, None, "args or a required pointer is NULL")
-    _rejected(L, _args(obs=None), "args or a required pointer is NULL")
-    _rejected(L, _args(out=None), "args or a required pointer is NULL")
-
-
-@pytest.mark.parametrize("rows", [-1, 2 ** 31, 2 ** 40])
-def test_rows_out_of_range(L, rows):
-    _rejected(L, _args(rows=rows), f"rows {rows} outside [0, 2^31)")
-
-
-@pytest.mark.parametrize("w,h", [(0, 15), (33, 15), (15, 0), (15, 33), (-1, 15)])
-def test_board_out_of_range(L, w, h):
-    _rejected(L, _args(width=w, height=h, obs_row_stride=9 * 33 * 33), "outside [1, 32]")
-
-
 @pytest.mark.parametrize("cap", [0, 1, 3, 48, 2048, -64])
 def test_cap_not_a_power_of_two_in_range(L, cap):
     _rejected(L, _args(cap=cap), f"cap {cap} is not a power of two in [2, 1024]")
@@ -58,11 +43,6 @@ def test_cap_not_a_power_of_two_in_range(L, cap):
 
 def test_reserved_must_be_zero(L):
     _rejected(L, _args(reserved=1), "reserved 1 must be 0")
-
-
-def test_row_stride_too_small(L):
-    _rejected(L, _args(obs_row_stride=9 * 225 - 1), "obs_row_stride 2024 < 9 * width * height = 2025")
-    _rejected(L, _args(obs_row_stride=0), "obs_row_stride 0 <")
 
 
 def test_zero_rows_is_a_no_op_without_a_device(L):
@@ -99,7 +79,7 @@ def test_strategic_features_rejects_bad_input_before_any_launch():
 def test_row_stride_detection():
     """which layouts are read in place (no copy) and which fall back to .contiguous()"""
     import torch
-    from generalsreinforcementlearning_amd.features import _row_stride
+    from generalsreinforcementlearning_amd._obs_batch import row_stride as _row_stride
     n = 9 * 4 * 5
     x = torch.zeros(6, 2, 9, 4, 5)
     assert _row_stride(x, 3, n) == n

@@ -192,6 +192,46 @@ def test_python_front_shapes_and_outputs():
         strategic_features(x.detach(), out=t.empty(5, dtype=t.float32, device=_dev()))
 
 
+FORMS = [(1, 1), (5, 6), (32, 32)]                                       # W x H
+
+
+@pytest.mark.parametrize("W,H", FORMS, ids=[f"{w}x{h}" for w, h in FORMS])
+def test_python_front_reads_every_form_of_a_batch(W, H):
+    """six observations, handed over in every form the front accepts: the reference's planes whichever way they reach the kernel"""
+    t = _torch()
+    from generalsreinforcementlearning_amd import strategic_features
+    from generalsreinforcementlearning_amd._obs_batch import in_place
+    obs, ref = _random_case(W, H, 0.2)
+    want, n, nan = _expected(ref, 6, 16), 9 * W * H, float("nan")
+    x = t.from_numpy(obs[:6].copy()).to(_dev())
+    got = lambda o, **k: strategic_features(o, cap=16, **k).cpu().numpy()
+    assert np.array_equal(got(x.view(2, 3, 9, H, W)), want.reshape(2, 3, 5, H, W))          # leading shape (2, 3)
+    assert np.array_equal(got(x.view(2, 3, 9, H * W), width=W, height=H), want.reshape(2, 3, 5, H * W))
+    assert np.array_equal(got(x[0]), want[0])                                              # no leading shape
+    assert np.array_equal(got(x[0].view(9, H * W), width=W, height=H), want[0].reshape(5, H * W))
+    # rows of a wider tensor, NaN between them: read where they are
+    wide = t.full((6, n + 13), nan, dtype=t.float32, device=_dev())
+    wide[:, :n] = x.view(6, n)
+    for view, tail in ((wide[:, :n].view(6, 9, H, W), 3), (wide[:, :n].view(6, 9, H * W), 2)):
+        read, stride = in_place(view, tail, H, W)
+        assert not view.is_contiguous() and read.data_ptr() == view.data_ptr() and stride == n + 13
+        kw = dict(width=W, height=H) if tail == 2 else {}
+        assert np.array_equal(got(view, **kw).reshape(6, 5, H, W), want)
+    assert bool(wide[:, n:].isnan().all())
+    # three of every four rows: no common stride, copied
+    gappy = t.full((2, 4, 9, H, W), nan, dtype=t.float32, device=_dev())
+    gappy[:, :3] = x.view(2, 3, 9, H, W)
+    assert in_place(gappy[:, :3], 3, H, W)[0].data_ptr() != gappy.data_ptr()
+    assert np.array_equal(got(gappy[:, :3]), want.reshape(2, 3, 5, H, W))
+    # one observation expanded to six rows: stride 0, copied
+    assert np.array_equal(got(x[:1].expand(6, 9, H, W)), np.repeat(want[:1], 6, axis=0))
+    out = t.full((6 * 5 * H * W,), nan, dtype=t.float32, device=_dev())
+    r = strategic_features(x.view(2, 3, 9, H, W), cap=16, out=out)
+    assert r.data_ptr() == out.data_ptr() and r.shape == (2, 3, 5, H, W) and np.array_equal(out.cpu().numpy().reshape(6, 5, H, W), want)
+    assert strategic_features(x[:0]).shape == (0, 5, H, W)
+    assert strategic_features(x[:0].view(0, 3, 9, H * W), width=W, height=H, out=out[:0]).shape == (0, 3, 5, H * W)
+
+
 # ---- the envs' option ----------------------------------------------------------------------------------------------
 
 def _random_legal(t, mask, gen):

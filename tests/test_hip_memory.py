@@ -297,6 +297,59 @@ def test_copy_envs_and_state_dict():
             other.load_state_dict(bad)
 
 
+FORMS = [(1, 1), (5, 6), (32, 32)]                                       # W x H
+
+
+@pytest.mark.parametrize("W,H", FORMS, ids=[f"{w}x{h}" for w, h in FORMS])
+def test_python_front_reads_every_form_of_a_batch(W, H):
+    """the second of two observations of six rows, handed over in every form update accepts: the reference's state whichever way
+    the rows reach the kernel"""
+    t = _torch()
+    from generalsreinforcementlearning_amd import ObservationMemory
+    from generalsreinforcementlearning_amd._obs_batch import in_place
+    cap, n, nan = 16, 9 * W * H, float("nan")
+    obs, reset = R.random_sequence(np.random.default_rng(100 * W + H), 2, 6, H, W, rows_per_flag=3, p_reset=0.5)
+    reset[1] = (1, 0)
+    first = R.update(None, obs[0], None, cap)
+    want = R.update(first, obs[1], None, cap)
+    want_reset = R.update(first, obs[1], reset[1], cap, rows_per_flag=3)
+    assert not np.array_equal(want, want_reset) or W * H == 1
+    x0, x1 = _up(obs[0]), _up(obs[1])
+
+    def after_first(rows_shape, src=x0):
+        m = ObservationMemory(rows_shape, H, W, cap=cap)
+        m.update(src.view(rows_shape + (9, H, W)))
+        return m
+
+    def same(planes, expected):
+        return np.array_equal(planes.cpu().numpy().reshape(expected.shape).view(np.uint32), expected.view(np.uint32))
+
+    p = after_first((2, 3)).update(x1.view(2, 3, 9, H, W), _up(reset[1]))                  # leading shape (2, 3), a flag per env
+    assert p.shape == (2, 3, 4, H, W) and same(p, want_reset)
+    p = after_first((), x0[0]).update(x1[0])                                                     # no leading shape
+    assert p.shape == (4, H, W) and same(p, want[0])
+    # rows of a wider tensor, NaN between them: read where they are
+    wide = t.full((6, n + 13), nan, dtype=t.float32, device=_dev())
+    wide[:, :n] = x1.view(6, n)
+    view = wide[:, :n].view(6, 9, H, W)
+    read, stride = in_place(view, 3, H, W)
+    assert not view.is_contiguous() and read.data_ptr() == view.data_ptr() and stride == n + 13
+    assert same(after_first((6,)).update(view), want) and bool(wide[:, n:].isnan().all())
+    # three of every four rows: no common stride, copied
+    gappy = t.full((2, 4, 9, H, W), nan, dtype=t.float32, device=_dev())
+    gappy[:, :3] = x1.view(2, 3, 9, H, W)
+    assert in_place(gappy[:, :3], 3, H, W)[0].data_ptr() != gappy.data_ptr()
+    assert same(after_first((2, 3)).update(gappy[:, :3], _up(reset[1]).bool()), want_reset)
+    # one observation expanded to six rows: stride 0, copied
+    m = after_first((6,), x0[:1].expand(6, 9, H, W).contiguous())
+    assert same(m.update(x1[:1].expand(6, 9, H, W)), np.repeat(want[:1], 6, axis=0))
+    m, out = after_first((2, 3)), t.full((6 * 4 * H * W,), nan, dtype=t.float32, device=_dev())
+    p = m.update(x1.view(2, 3, 9, H, W), out=out)
+    assert p.data_ptr() == out.data_ptr() == m.planes.data_ptr() and same(out, want)
+    empty = ObservationMemory((0, 3), H, W, cap=cap)
+    assert empty.update(x1[:0].view(0, 3, 9, H, W), out=out[:0]).shape == (0, 3, 4, H, W)
+
+
 # ---- a real env --------------------------------------------------------------------------------------------------------
 
 def _random_legal(t, mask, gen):

@@ -1,5 +1,6 @@
 """The argument checks of gvec_obs_memory_update and of its Python front (memory.ObservationMemory).  They run before
-anything touches a device, so they are pinned here without one."""
+anything touches a device, so they are pinned here without one.  The checks it shares with the other observation-batch entry
+points (null arguments, rows, board, row stride) are in test_qtarget_api.py's table."""
 import ctypes as C
 
 import pytest
@@ -36,22 +37,6 @@ def test_struct_layout_matches_the_header():
             f.obs.offset, f.prev.offset, f.reset.offset, f.out.offset) == (0, 8, 12, 16, 20, 24, 32, 40, 48, 56)
 
 
-def test_null_arguments(L):
-    _rejected(L, None, "args or a required pointer is NULL")
-    _rejected(L, _args(obs=None), "args or a required pointer is NULL")
-    _rejected(L, _args(out=None), "args or a required pointer is NULL")
-
-
-@pytest.mark.parametrize("rows", [-1, 2 ** 31, 2 ** 40])
-def test_rows_out_of_range(L, rows):
-    _rejected(L, _args(rows=rows), f"rows {rows} outside [0, 2^31)")
-
-
-@pytest.mark.parametrize("w,h", [(0, 15), (33, 15), (15, 0), (15, 33), (-1, 15)])
-def test_board_out_of_range(L, w, h):
-    _rejected(L, _args(width=w, height=h, obs_row_stride=9 * 33 * 33), "outside [1, 32]")
-
-
 @pytest.mark.parametrize("cap", [0, 1, 3, 48, 2048, -64])
 def test_cap_not_a_power_of_two_in_range(L, cap):
     _rejected(L, _args(cap=cap), f"cap {cap} is not a power of two in [2, 1024]")
@@ -60,11 +45,6 @@ def test_cap_not_a_power_of_two_in_range(L, cap):
 @pytest.mark.parametrize("rows,rpf", [(3, 0), (3, -1), (3, 2), (4, 3), (0, 0)])
 def test_rows_per_flag_must_divide_rows(L, rows, rpf):
     _rejected(L, _args(rows=rows, rows_per_flag=rpf), f"rows_per_flag {rpf} is not a divisor >= 1 of rows {rows}")
-
-
-def test_row_stride_too_small(L):
-    _rejected(L, _args(obs_row_stride=9 * 225 - 1), "obs_row_stride 2024 < 9 * width * height = 2025")
-    _rejected(L, _args(obs_row_stride=0), "obs_row_stride 0 <")
 
 
 @pytest.mark.parametrize("delta", [4, -4, STATE - 4, 4 - STATE, 900])

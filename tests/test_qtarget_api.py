@@ -1,5 +1,10 @@
 """The argument checks of gvec_obs_valid_mask, gvec_q_target and gvec_categorical_target and of their Python front
-(q_targets.py).  They run before anything touches a device, so they are pinned here without one."""
+(q_targets.py).  They run before anything touches a device, so they are pinned here without one.
+
+The checks that all five observation-batch entry points of gvec_api_obs.hip share (null arguments, rows, board, row stride,
+zero rows, the bounds, valid arguments reaching the device) are one table here, ENTRY / REQUIRED / OPTIONAL, which also
+lists gvec_obs_features and gvec_obs_memory_update; what only those two check is in test_features_api.py and
+test_memory_api.py."""
 import ctypes as C
 
 import pytest
@@ -37,12 +42,27 @@ def _c_args(**over):
     return lib.CategoricalTargetArgs(**kw)
 
 
-ENTRY = {"gvec_obs_valid_mask": _mask_args, "gvec_q_target": _q_args, "gvec_categorical_target": _c_args}
+def _feat_args(**over):
+    kw = dict(rows=3, width=15, height=15, cap=64, reserved=0, obs_row_stride=9 * 225, obs=P, out=2 * P)
+    kw.update(over)
+    return lib.ObsFeaturesArgs(**kw)
+
+
+def _mem_args(**over):
+    kw = dict(rows=3, width=15, height=15, cap=64, rows_per_flag=1, obs_row_stride=9 * 225, obs=P, prev=None, reset=None, out=2 * P)
+    kw.update(over)
+    return lib.ObsMemoryArgs(**kw)
+
+
+ENTRY = {"gvec_obs_valid_mask": _mask_args, "gvec_q_target": _q_args, "gvec_categorical_target": _c_args,
+         "gvec_obs_features": _feat_args, "gvec_obs_memory_update": _mem_args}
 REQUIRED = {"gvec_obs_valid_mask": ("obs", "mask"),
             "gvec_q_target": ("next_obs", "q_eval", "reward", "done", "target", "next_action"),
-            "gvec_categorical_target": ("next_obs", "logits_eval", "reward", "done", "m", "next_action")}
+            "gvec_categorical_target": ("next_obs", "logits_eval", "reward", "done", "m", "next_action"),
+            "gvec_obs_features": ("obs", "out"), "gvec_obs_memory_update": ("obs", "out")}
 OPTIONAL = {"gvec_obs_valid_mask": (), "gvec_q_target": ("q_select", "discount", "next_value"),
-            "gvec_categorical_target": ("logits_select", "discount")}
+            "gvec_categorical_target": ("logits_select", "discount"), "gvec_obs_features": (),
+            "gvec_obs_memory_update": ("prev", "reset")}
 
 
 def _rejected(L, fn, a, text):
