@@ -328,13 +328,18 @@ __device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c) {
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, int lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
 }
+__device__ __forceinline__ float rdlane(float v, int lane) { return __uint_as_float(rdlane(__float_as_uint(v), lane)); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint64_t uni64(uint64_t v) {
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
+// the signed form under a name of its own: an int64_t argument would not choose between two overloads
+__device__ __forceinline__ long long uni_ll(long long v) { return (long long)uni64((uint64_t)v); }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return rdlane(wave_scan_add(v), 63); }
 __device__ __forceinline__ bool wave_any(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
 // float reductions as fixed xor butterflies: every lane ends with the same value, and the same input gives the same bits
+constexpr float NEG_INF = -__builtin_inff();  // what a masked-out entry holds, and the identity of wave_max
+constexpr int NO_INDEX = 0x7FFFFFFF;          // wave_argmax's index of "no entry": loses every tie
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
@@ -344,6 +349,11 @@ __device__ __forceinline__ float wave_max(float x) {
   return x;
 }
 __device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+  return x;
+}
+__device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
   return x;

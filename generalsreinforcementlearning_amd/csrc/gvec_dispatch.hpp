@@ -1,14 +1,12 @@
-// gvec_dispatch.hpp — host side of the board-kernel units: the launch shape (one wavefront per board, WAVES_PER_BLOCK boards
-// per workgroup), the <MAXP, NSLOT> dispatch, and what their launchers share.  The only device code is the launch shape's
-// other half: which wave of its block a kernel is, and which item it owns.
+// gvec_dispatch.hpp — host side of the board-kernel units: the <MAXP, NSLOT> dispatch and what their launchers share.  The
+// launch shape (one wavefront per board, WAVES_PER_BLOCK boards per workgroup) is gvec_waves.hpp's.
 #pragma once
 #include "gvec_launch.hpp"
+#include "gvec_waves.hpp"
 
 #include <type_traits>
 
 namespace gvec {
-
-constexpr int WAVES_PER_BLOCK = 4;
 
 // f(MAXP, NSLOT) of the handle's variant, both as std::integral_constant: usable as template arguments
 template <typename F>
@@ -20,20 +18,6 @@ static hipError_t dispatch(const Variant& v, F&& f) {
 #undef GVEC_ROW
 #undef GVEC_CASE
   return hipErrorInvalidValue;
-}
-
-// device side of launch_waves: this wave's index in its block, and the item it owns (wave-uniform) - none when it is not
-// below the launch's n (the spare waves of the last block), and the kernel leaves
-__device__ __forceinline__ int block_wave() { return (int)(threadIdx.x >> 6); }
-__device__ __forceinline__ int wave_item() { return uni((int)blockIdx.x * WAVES_PER_BLOCK + block_wave()); }
-
-static inline dim3 wave_grid(int n) { return dim3((unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)); }
-
-// kernel k with one wavefront per item, n items
-template <typename... P, typename... A>
-static hipError_t launch_waves(void (*k)(P...), int n, hipStream_t s, const A&... a) {
-  hipLaunchKernelGGL(k, wave_grid(n), dim3(64 * WAVES_PER_BLOCK), 0, s, a...);
-  return hipGetLastError();
 }
 
 // the resident format keeps planes of 2*S-1 or 2*S dwords (gvec_api.hip: set_geometry), and the kernels that take the plane

@@ -541,8 +541,7 @@ hipError_t launch_expand_records(const void* records, int32_t n, const int32_t* 
   a.ns = layout8[3];
   a.stride = layout8[5];
   const size_t lds = (size_t)WAVES_PER_BLOCK * (a.record_dw + 2 * a.fd) * 4;   // <= 52 KB (32x32 8P)
-  hipLaunchKernelGGL(expand_records_kernel, wave_grid(n), dim3(64 * WAVES_PER_BLOCK), lds, s, a);
-  return hipGetLastError();
+  return launch_waves(expand_records_kernel, n, lds, s, a);
 }
 
 }  // namespace gvec

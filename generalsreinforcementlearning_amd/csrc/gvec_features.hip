@@ -14,12 +14,12 @@
 //            unreached one) or to the fixpoint, a wave-wide any.
 //   store    reached words and slices go to LDS; lane = tile reads its row's words back, rebuilds d and stores min(d, cap) / cap.
 #include "gvec_launch.hpp"
+#include "gvec_waves.hpp"
 
 namespace gvec {
 
 namespace {
 
-constexpr int FEAT_WAVES = 4;                    // observations per workgroup
 constexpr int FEAT_SLICES = 10;                  // levels 1 .. cap - 1 <= 1023
 constexpr int FEAT_PRED_DW = 34;                 // 1,024 bits, and the dword after the last row's (read, then masked off)
 enum { PRED_PASS, PRED_MINE, PRED_SRC0, PRED_SRC1, PRED_SRC2, PRED_SRC3, PRED_COUNT };   // SRC1 = enemy
@@ -34,13 +34,13 @@ __device__ __forceinline__ uint32_t dilate(uint32_t f, uint32_t has_above, uint3
   return (f << 1) | (f >> 1) | (above & has_above) | (below & has_below);
 }
 
-__global__ __launch_bounds__(64 * FEAT_WAVES) void obs_features_kernel(gvec_obs_features_args P, int cap_log2) {
-  __shared__ uint32_t feat_lds[FEAT_WAVES * FEAT_WAVE_DW];
-  const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-  const long long r = (long long)blockIdx.x * FEAT_WAVES + wave;
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void obs_features_kernel(gvec_obs_features_args P, int cap_log2) {
+  __shared__ uint32_t feat_lds[WAVES_PER_BLOCK * FEAT_WAVE_DW];
+  const int lane = lane_id();
+  const long long r = wave_item64();
   if (r >= P.rows) return;                       // the whole wave leaves: everything below is wave-uniform control flow
   const int W = P.width, H = P.height, HW = W * H, slots = (HW + 63) >> 6;
-  uint32_t* L = feat_lds + wave * FEAT_WAVE_DW;
+  uint32_t* L = feat_lds + block_wave() * FEAT_WAVE_DW;
   const float* __restrict__ o = P.obs + (size_t)r * (size_t)P.obs_row_stride;
 
   // ---- load: predicates per tile, one ballot each ----
@@ -148,9 +148,7 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) void obs_features_kernel(gvec_obs_
 hipError_t launch_obs_features(const gvec_obs_features_args& a, hipStream_t s) {
   int cap_log2 = 0;
   while ((1 << cap_log2) < a.cap) ++cap_log2;
-  const dim3 grid((unsigned)((a.rows + FEAT_WAVES - 1) / FEAT_WAVES));
-  hipLaunchKernelGGL(obs_features_kernel, grid, dim3(64 * FEAT_WAVES), 0, s, a, cap_log2);
-  return hipGetLastError();
+  return launch_waves(obs_features_kernel, a.rows, s, a, cap_log2);
 }
 
 }  // namespace gvec

@@ -9,18 +9,20 @@
 // result depends on that tile's inputs alone and the lane that stores a tile is the lane that loaded it, so in place is safe.
 // The row's reset flag is wave-uniform: a restarted row (and every row when prev is null) skips the four loads of prev.
 #include "gvec_launch.hpp"
+#include "gvec_waves.hpp"
 
 namespace gvec {
 
 namespace {
 
-constexpr int MEM_WAVES = 4;   // rows per workgroup
 constexpr int MEM_TILES = 2;   // tiles per lane and pass
 
-__global__ __launch_bounds__(64 * MEM_WAVES) void obs_memory_kernel(gvec_obs_memory_args P, float capf, float inv) {
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void obs_memory_kernel(gvec_obs_memory_args P, float capf, float inv) {
   const int lane = lane_id();
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t r = blockIdx.x * (uint32_t)MEM_WAVES + wave;       // rows < 2^31: no wrap
+  // not wave_item(): with it the 8,192-row shape of scripts/bench_memory.py measured 1-2 % slower than the parent in each
+  // of three parent / result / parent runs (profiles/learner_units_ab.json), so the opening keeps its own spelling
+  const uint32_t wave = (uint32_t)uni(block_wave());
+  const uint32_t r = blockIdx.x * (uint32_t)WAVES_PER_BLOCK + wave;   // rows < 2^31: no wrap
   if (r >= (uint32_t)P.rows) return;                                 // the whole wave leaves
   const int HW = P.width * P.height;
   const bool blank = !P.prev || (P.reset && P.reset[r / (uint32_t)P.rows_per_flag] != 0);   // wave-uniform
@@ -77,9 +79,7 @@ __global__ __launch_bounds__(64 * MEM_WAVES) void obs_memory_kernel(gvec_obs_mem
 }  // namespace
 
 hipError_t launch_obs_memory(const gvec_obs_memory_args& a, hipStream_t s) {
-  const dim3 grid((unsigned)((a.rows + MEM_WAVES - 1) / MEM_WAVES));
-  hipLaunchKernelGGL(obs_memory_kernel, grid, dim3(64 * MEM_WAVES), 0, s, a, (float)a.cap, 1.0f / (float)a.cap);
-  return hipGetLastError();
+  return launch_waves(obs_memory_kernel, a.rows, s, a, (float)a.cap, 1.0f / (float)a.cap);
 }
 
 }  // namespace gvec

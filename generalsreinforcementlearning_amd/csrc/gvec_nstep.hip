@@ -3,18 +3,11 @@
 // scratch, and the one fused gather that walks them and moves a sample's two rows, which come from two different slots.
 #include "gvec_launch.hpp"
 #include "gvec_collect.hpp"
+#include "gvec_rows.hpp"
 
 namespace gvec {
 
 namespace {
-
-constexpr int NSTEP_WAVES = 4;            // wavefronts per workgroup of the gather
-
-__device__ __forceinline__ long long uni_ll(long long v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
 
 // one thread per worker, one wavefront per 64-worker group of the collect scratch: the rank of a live worker among the live
 // ones is the group's prefix count plus the live lanes below it - exactly collect_push_kernel's slot
@@ -44,12 +37,10 @@ __global__ __launch_bounds__(256) void nstep_link_kernel(gvec_collect_args A, co
 
 // `1 << shift` wavefronts per sample: each walks the links for itself (wave-uniform: at most n_step - 1 dependent loads), then
 // they share the two rows
-__global__ __launch_bounds__(64 * NSTEP_WAVES) void nstep_gather_kernel(gvec_nstep_gather_args A, int shift) {
-  const long long gw = uni_ll((long long)blockIdx.x * NSTEP_WAVES + (threadIdx.x >> 6));
-  const long long j = gw >> shift;
-  const int part = (int)(gw & ((1 << shift) - 1));
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void nstep_gather_kernel(gvec_nstep_gather_args A, int shift) {
+  const WaveSplit w = wave_split(shift);
+  const long long j = w.item;
   if (j >= A.k) return;
-  const int lane = lane_id();
   const int n = A.obs_floats;
   float* d0 = A.state + (size_t)j * n;
   float* d1 = A.next_state + (size_t)j * n;
@@ -57,11 +48,11 @@ __global__ __launch_bounds__(64 * NSTEP_WAVES) void nstep_gather_kernel(gvec_nst
   long long size = uni_ll(A.ring_counters[1]);
   if (size > A.capacity) size = A.capacity;
   if (first < 0 || first >= size) {                              // no such transition: the zero record
-    for (int i = part * 64 + lane; i < n; i += 64 << shift) {
+    for (int i = w.first; i < n; i += w.stride) {
       d0[i] = 0.0f;
       d1[i] = 0.0f;
     }
-    if (part == 0 && lane == 0) {
+    if (w.first == 0) {
       A.action[j] = -1;
       A.ret[j] = 0.0;
       A.discount[j] = 0.0;
@@ -82,9 +73,9 @@ __global__ __launch_bounds__(64 * NSTEP_WAVES) void nstep_gather_kernel(gvec_nst
     ret = ret + disc * A.ring_reward[cur];
     ++steps;
   }
-  copy_row(A.ring_state + (size_t)first * n, d0, n, part, lane, shift);
-  copy_row(A.ring_next_state + (size_t)cur * n, d1, n, part, lane, shift);
-  if (part == 0 && lane == 0) {
+  copy_row(A.ring_state + (size_t)first * n, d0, n, w);
+  copy_row(A.ring_next_state + (size_t)cur * n, d1, n, w);
+  if (w.first == 0) {
     A.action[j] = A.ring_action[first];
     A.ret[j] = ret;
     A.discount[j] = disc * A.gamma;
@@ -97,16 +88,11 @@ __global__ __launch_bounds__(64 * NSTEP_WAVES) void nstep_gather_kernel(gvec_nst
 }  // namespace
 
 hipError_t launch_nstep_link(const gvec_collect_args& a, const long long* before, long long* ring_succ, long long* nstep_last, hipStream_t s) {
-  const int padded = collect_groups(a.num_envs) * 64;
-  hipLaunchKernelGGL(nstep_link_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, s, a, before, ring_succ, nstep_last);
-  return hipGetLastError();
+  return launch_threads(nstep_link_kernel, collect_groups(a.num_envs) * 64, s, a, before, ring_succ, nstep_last);
 }
 hipError_t launch_nstep_gather(const gvec_nstep_gather_args& a, hipStream_t s) {
-  int shift = 0;                                   // enough wavefronts to fill 256 CUs when there are few samples: collect's rule
-  while (shift < 3 && (a.k << shift) < 16384) ++shift;
-  const long long waves = a.k << shift;
-  hipLaunchKernelGGL(nstep_gather_kernel, dim3((unsigned)((waves + NSTEP_WAVES - 1) / NSTEP_WAVES)), dim3(64 * NSTEP_WAVES), 0, s, a, shift);
-  return hipGetLastError();
+  const int shift = split_shift(a.k);
+  return launch_waves(nstep_gather_kernel, a.k << shift, s, a, shift);
 }
 
 }  // namespace gvec

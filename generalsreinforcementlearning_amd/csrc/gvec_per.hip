@@ -13,30 +13,23 @@
 // A node is only ever recomputed from its children - no differences, no float atomics - so the tree cannot drift and a
 // refresh is idempotent (duplicate indices need no deduplication).
 #include "gvec_launch.hpp"
+#include "gvec_waves.hpp"
 
 namespace gvec {
 
 namespace {
 
-constexpr int PER_WAVES = 4;              // wavefronts per workgroup of the wave-per-item kernels
 constexpr uint32_t F32_INF = 0x7F800000u;
 
-__device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63u); }
-__device__ __forceinline__ float rdlane_f(float v, int l) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), l)); }
-__device__ __forceinline__ long long uni_ll(long long v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
 // Lane j receives P[j] = ((c[0] + c[1]) + ...) + c[j], the additions in exactly this order in every lane (wave-uniform
 // control flow: all 64 lanes take part).  Non-negative inputs make P non-decreasing.
 __device__ __forceinline__ float seq_prefix(float c) {
-  const int me = lane();
-  float acc = rdlane_f(c, 0);
+  const int me = lane_id();
+  float acc = rdlane(c, 0);
   float p = acc;
 #pragma unroll
   for (int j = 1; j < 64; ++j) {
-    acc = acc + rdlane_f(c, j);
+    acc = acc + rdlane(c, j);
     p = (me >= j) ? acc : p;
   }
   return p;
@@ -44,9 +37,9 @@ __device__ __forceinline__ float seq_prefix(float c) {
 
 // one wavefront: node `node` of level `lvl` (>= 1) := the last sequential prefix over its 64 children
 __device__ __forceinline__ void refresh_node(float* tree, const PerLayout& Y, int lvl, long long node) {
-  const float c = tree[Y.off[lvl - 1] + node * 64 + lane()];
+  const float c = tree[Y.off[lvl - 1] + node * 64 + lane_id()];
   const float p = seq_prefix(c);
-  if (lane() == 63) tree[Y.off[lvl] + node] = p;
+  if (lane_id() == 63) tree[Y.off[lvl] + node] = p;
 }
 
 __global__ __launch_bounds__(256) void per_init_kernel(float* tree, long long total_floats) {
@@ -98,14 +91,14 @@ __device__ __forceinline__ long long touched_node(const PerRuns& r, int lvl, lon
 
 // push, level 0 and 1 together: one wavefront per touched level-1 node writes the node's new leaves (the running maximum)
 // and the node itself from the 64 leaves it holds in registers - no other wavefront's store is needed
-__global__ __launch_bounds__(64 * PER_WAVES) void per_push_leaves_kernel(float* tree, PerLayout Y, const long long* before, const long long* after,
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void per_push_leaves_kernel(float* tree, PerLayout Y, const long long* before, const long long* after,
                                                                          long long max_count) {
-  const long long w = uni_ll((long long)blockIdx.x * PER_WAVES + (threadIdx.x >> 6));
+  const long long w = wave_item64();
   uint32_t* hdr = reinterpret_cast<uint32_t*>(tree);
-  const PerRuns r = push_runs(before, after, Y.capacity, max_count, hdr, w == 0 && lane() == 0);
+  const PerRuns r = push_runs(before, after, Y.capacity, max_count, hdr, w == 0 && lane_id() == 0);
   const long long node = touched_node(r, 1, w);
   if (node < 0) return;
-  const long long slot = node * 64 + lane();
+  const long long slot = node * 64 + lane_id();
   const bool hit = (slot >= r.a0 && slot < r.a1) || slot < r.b1;      // both runs: they may meet inside one node
   float* leaf = tree + Y.off[0] + slot;
   const float top = __uint_as_float(hdr[GVEC_PER_HDR_MAX]);
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(64 * PER_WAVES) void per_push_leaves_kernel(float* 
     *leaf = c;
   }
   const float p = seq_prefix(c);
-  if (lane() == 63) tree[Y.off[1] + node] = p;
+  if (lane_id() == 63) tree[Y.off[1] + node] = p;
 }
 
 // one workgroup: levels lvl0 .. root, each level's touched nodes (whole != 0: all of them) before the next level's
@@ -159,8 +152,8 @@ __global__ __launch_bounds__(256) void per_update_leaves_kernel(float* tree, Per
   if (bits > hdr[GVEC_PER_HDR_MAX]) atomicMax(hdr + GVEC_PER_HDR_MAX, bits);
 }
 // update, level lvl: one wavefront per index refreshes that slot's ancestor (a duplicate rewrites the same value)
-__global__ __launch_bounds__(64 * PER_WAVES) void per_refresh_touched_kernel(float* tree, PerLayout Y, int lvl, const long long* idx, long long n) {
-  const long long w = uni_ll((long long)blockIdx.x * PER_WAVES + (threadIdx.x >> 6));
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void per_refresh_touched_kernel(float* tree, PerLayout Y, int lvl, const long long* idx, long long n) {
+  const long long w = wave_item64();
   if (w >= n) return;
   const long long slot = uni_ll(idx[w]);
   if (slot < 0 || slot >= Y.capacity) return;
@@ -168,13 +161,13 @@ __global__ __launch_bounds__(64 * PER_WAVES) void per_refresh_touched_kernel(flo
 }
 
 // sample, the draws: one wavefront per draw descends from the root
-__global__ __launch_bounds__(64 * PER_WAVES) void per_draw_kernel(float* tree, PerLayout Y, const long long* ring_counters, long long k, const double* u_in,
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void per_draw_kernel(float* tree, PerLayout Y, const long long* ring_counters, long long k, const double* u_in,
                                                                   unsigned long long seed, long long* idx, float* weight) {
-  const long long j = uni_ll((long long)blockIdx.x * PER_WAVES + (threadIdx.x >> 6));
+  const long long j = wave_item64();
   uint32_t* hdr = reinterpret_cast<uint32_t*>(tree);
   const uint32_t call = hdr[GVEC_PER_HDR_DRAWS];               // the RNG's draw counter: a caller may zero it
   const uint32_t seq = hdr[GVEC_PER_HDR_SEQ];                  // the kernels' own call count: picks the minimum word, never reset
-  if (j == 0 && lane() == 0) {
+  if (j == 0 && lane_id() == 0) {
     hdr[GVEC_PER_HDR_DRAWS + 1] = call;                       // the weights kernel's copies (this kernel only reads the others)
     hdr[GVEC_PER_HDR_SEQ + 1] = seq;
     hdr[GVEC_PER_HDR_MIN0 + ((seq + 1u) & 1u)] = F32_INF;     // the next call's minimum; this call's was reset by the last one
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(64 * PER_WAVES) void per_draw_kernel(float* tree, P
   if (j >= k) return;
   const float total = tree[Y.off[Y.levels]];
   if (!(total > 0.0f) || ring_counters[1] <= 0) {             // nothing to draw from
-    if (lane() == 0) {
+    if (lane_id() == 0) {
       idx[j] = -1;
       weight[j] = 0.0f;
     }
@@ -203,17 +196,17 @@ __global__ __launch_bounds__(64 * PER_WAVES) void per_draw_kernel(float* tree, P
   long long node = 0;
   float leaf = 0.0f;
   for (int lvl = Y.levels; lvl >= 1; --lvl) {
-    const float c = tree[Y.off[lvl - 1] + node * 64 + lane()];
+    const float c = tree[Y.off[lvl - 1] + node * 64 + lane_id()];
     const float p = seq_prefix(c);
     int child = __popcll(__builtin_amdgcn_ballot_w64(p <= r));        // P is non-decreasing: the lanes that vote are a prefix
     child = child < 63 ? child : 63;                                  // (only a tree that breaks its invariant gets here with 64)
-    const float below = child > 0 ? rdlane_f(p, child - 1) : 0.0f;
-    leaf = rdlane_f(c, child);
+    const float below = child > 0 ? rdlane(p, child - 1) : 0.0f;
+    leaf = rdlane(c, child);
     r = r - below;
     if (r >= leaf) r = leaf > 0.0f ? __uint_as_float(__float_as_uint(leaf) - 1u) : 0.0f;   // P[child] was rounded up: stay inside the child
     node = node * 64 + child;
   }
-  if (lane() == 0) {
+  if (lane_id() == 0) {
     idx[j] = node;
     weight[j] = leaf;                                                 // the weights kernel turns it into the weight
     const uint32_t bits = __float_as_uint(leaf);
@@ -235,8 +228,6 @@ __global__ __launch_bounds__(256) void per_weights_kernel(float* tree, long long
   const float leaf = weight[j];
   weight[j] = leaf > 0.0f ? powf(leaf / least, -beta) : 0.0f;
 }
-
-inline dim3 waves(long long n) { return dim3((unsigned)((n + PER_WAVES - 1) / PER_WAVES)); }
 
 }  // namespace
 
@@ -263,24 +254,25 @@ hipError_t launch_per_init(float* tree, const PerLayout& y, hipStream_t s) {
 }
 hipError_t launch_per_push(float* tree, const PerLayout& y, const long long* before, const long long* after, long long max_count, hipStream_t s) {
   if (max_count > y.capacity) max_count = y.capacity;
-  hipLaunchKernelGGL(per_push_leaves_kernel, waves(max_count / 64 + 4), dim3(64 * PER_WAVES), 0, s, tree, y, before, after, max_count);
-  if (y.levels >= 2) hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, tree, y, 2, 0, before, after, max_count);
+  const hipError_t e = launch_waves(per_push_leaves_kernel, max_count / 64 + 4, s, tree, y, before, after, max_count);
+  if (e != hipSuccess || y.levels < 2) return e;
+  hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, tree, y, 2, 0, before, after, max_count);
   return hipGetLastError();
 }
 hipError_t launch_per_update(float* tree, const PerLayout& y, const long long* idx, const float* td, long long n, float alpha, float eps, hipStream_t s) {
-  hipLaunchKernelGGL(per_update_leaves_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tree, y, idx, td, n, alpha, eps);
+  hipError_t e = launch_threads(per_update_leaves_kernel, n, s, tree, y, idx, td, n, alpha, eps);
   int lvl = 1;
   // a level of more than 64 nodes: only the touched ones, one launch per level; the few levels above: whole, in one workgroup
-  for (long long nodes = (y.capacity + 63) / 64; lvl <= y.levels && nodes > 64; ++lvl, nodes = (nodes + 63) / 64)
-    hipLaunchKernelGGL(per_refresh_touched_kernel, waves(n), dim3(64 * PER_WAVES), 0, s, tree, y, lvl, idx, n);
-  if (lvl <= y.levels) hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, tree, y, lvl, 1, nullptr, nullptr, 0);
+  for (long long nodes = (y.capacity + 63) / 64; e == hipSuccess && lvl <= y.levels && nodes > 64; ++lvl, nodes = (nodes + 63) / 64)
+    e = launch_waves(per_refresh_touched_kernel, n, s, tree, y, lvl, idx, n);
+  if (e != hipSuccess || lvl > y.levels) return e;
+  hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, tree, y, lvl, 1, nullptr, nullptr, 0);
   return hipGetLastError();
 }
 hipError_t launch_per_sample(float* tree, const PerLayout& y, const long long* ring_counters, long long k, float beta, const double* u,
                              unsigned long long seed, long long* idx, float* weight, hipStream_t s) {
-  hipLaunchKernelGGL(per_draw_kernel, waves(k), dim3(64 * PER_WAVES), 0, s, tree, y, ring_counters, k, u, seed, idx, weight);
-  hipLaunchKernelGGL(per_weights_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, tree, k, beta, weight);
-  return hipGetLastError();
+  const hipError_t e = launch_waves(per_draw_kernel, k, s, tree, y, ring_counters, k, u, seed, idx, weight);
+  return e != hipSuccess ? e : launch_threads(per_weights_kernel, k, s, tree, k, beta, weight);
 }
 
 }  // namespace gvec

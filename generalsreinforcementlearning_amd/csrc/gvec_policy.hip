@@ -14,10 +14,6 @@ namespace gvec {
 namespace {
 
 constexpr int POLICY_STAGE_MAX = 5 * 32 * 32;   // the largest board the engine deals: 20.5 KB of LDS per row
-constexpr float NEG_INF = -__builtin_inff();
-constexpr int NO_INDEX = 0x7FFFFFFF;
-
-__device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63u); }
 
 // ---- the draws (DESIGN.md §6 "Policy head") ----
 __host__ __device__ __forceinline__ uint32_t policy_row_key(uint32_t base, long long row) {
@@ -71,7 +67,7 @@ __device__ __forceinline__ Row<STAGED> open_row(const float* __restrict__ l, con
   const float4* __restrict__ lq = reinterpret_cast<const float4*>(l + head);
   float4* xq = reinterpret_cast<float4*>(x + head);
 #pragma unroll 4
-  for (int j = lane(); j < quads; j += 64) {
+  for (int j = lane_id(); j < quads; j += 64) {
     float4 v = lq[j];
     uint32_t mb;
     __builtin_memcpy(&mb, k + head + 4 * j, 4);
@@ -81,9 +77,9 @@ __device__ __forceinline__ Row<STAGED> open_row(const float* __restrict__ l, con
     v.w = (mb & 0xFF000000u) ? v.w : NEG_INF;
     xq[j] = v;
   }
-  const int i0 = lane();                       // head: at most three floats
+  const int i0 = lane_id();                       // head: at most three floats
   if (i0 < head) x[i0] = k[i0] ? l[i0] : NEG_INF;
-  const int i1 = head + 4 * quads + lane();    // tail: at most three floats
+  const int i1 = head + 4 * quads + lane_id();    // tail: at most three floats
   if (i1 < A) x[i1] = k[i1] ? l[i1] : NEG_INF;
   __syncthreads();
   row.x = x;
@@ -101,7 +97,7 @@ __device__ __forceinline__ RowStats row_stats(const Row<STAGED>& row, int A, flo
   RowStats s{m, 0.0f, 0.0f, !(m > NEG_INF)};
   if (s.dead) return s;
   float z = 0.0f, w = 0.0f;
-  for (int i = lane(); i < A; i += 64) {
+  for (int i = lane_id(); i < A; i += 64) {
     const float d = row(i) - m;
     if (d > NEG_INF) {
       const float e = expf(d);
@@ -118,7 +114,7 @@ __device__ __forceinline__ RowStats row_stats(const Row<STAGED>& row, int A, flo
 template <bool STAGED>
 __device__ __forceinline__ float row_max(const Row<STAGED>& row, int A) {
   float m = NEG_INF;
-  for (int i = lane(); i < A; i += 64) {
+  for (int i = lane_id(); i < A; i += 64) {
     const float v = row(i);
     m = v > m ? v : m;
   }
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(64) void policy_sample_kernel(gvec_policy_sample_ar
   const uint32_t rk = policy_row_key(key_base, P.row_base + r);
   float m = NEG_INF, best = NEG_INF;
   int pick = NO_INDEX;
-  for (int i = lane(); i < A; i += 64) {
+  for (int i = lane_id(); i < A; i += 64) {
     const float v = row(i);
     if (v > NEG_INF) {                         // i in S: only these cost a draw
       m = v > m ? v : m;
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(64) void policy_sample_kernel(gvec_policy_sample_ar
   m = wave_max(m);
   wave_argmax(best, pick);
   const RowStats s = row_stats(row, A, m);
-  if (lane() == 0) {
+  if (lane_id() == 0) {
     const float lp = s.dead ? 0.0f : (row(s.dead ? 0 : pick) - m) - s.logz;
     P.action[r] = s.dead ? 0 : pick;
     P.logp[r] = lp;
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(64) void policy_evaluate_kernel(gvec_policy_evaluat
   const int A = P.num_actions;
   const Row<STAGED> row = open_row<STAGED>(P.logits + (size_t)r * A, P.mask + (size_t)r * A, A);
   const RowStats s = row_stats(row, A, row_max(row, A));
-  if (lane() == 0) {
+  if (lane_id() == 0) {
     const float xa = action_logit(row, A, P.action[r]);
     const bool ok = xa > NEG_INF;              // on a dead row no action is legal and none is counted
     P.logp[r] = ok ? (xa - s.m) - s.logz : 0.0f;
@@ -199,14 +195,14 @@ __global__ __launch_bounds__(64) void policy_backward_kernel(gvec_policy_backwar
   int head, quads;
   quad_split(g, A, head, quads);
   float4* gq = reinterpret_cast<float4*>(g + head);
-  for (int j = lane(); j < quads; j += 64) {
+  for (int j = lane_id(); j < quads; j += 64) {
     const int i = head + 4 * j;
     gq[j] = make_float4(grad_of(row, s, i, a, gl, ge), grad_of(row, s, i + 1, a, gl, ge), grad_of(row, s, i + 2, a, gl, ge),
                         grad_of(row, s, i + 3, a, gl, ge));
   }
-  const int i0 = lane();
+  const int i0 = lane_id();
   if (i0 < head) g[i0] = grad_of(row, s, i0, a, gl, ge);
-  const int i1 = head + 4 * quads + lane();
+  const int i1 = head + 4 * quads + lane_id();
   if (i1 < A) g[i1] = grad_of(row, s, i1, a, gl, ge);
 }
 

@@ -17,18 +17,16 @@
 #include <math.h>
 
 #include "gvec_launch.hpp"
+#include "gvec_waves.hpp"
 
 namespace gvec {
 
 namespace {
 
-constexpr int QT_WAVES = 4;                      // rows per workgroup
 constexpr int QT_PRED_DW = 32;                   // 1,024 bits: GVEC_MAX_DIM squared
 constexpr int QT_MAX_TILES = 32 * 32;
 constexpr int QT_MAX_LEGAL = 5 * QT_MAX_TILES;   // every action of the largest board
 constexpr int QT_UNROLL = 4;                     // atom rows in flight in the categorical loop
-constexpr float NEG_INF = -__builtin_inff();
-constexpr int NO_INDEX = 0x7FFFFFFF;
 
 // ---- the legal set of an observation (generals_vec.h "masked Q targets") ----
 // L[0 .. 31]: source bits (plane 1 == 0.5 and plane 2 > 0.09), L[32 .. 63]: passable bits (plane 4 == 0); bit t = tile t.
@@ -64,26 +62,17 @@ __device__ __forceinline__ uint32_t legal_code(const uint32_t* L, int t, int W, 
   return code ? code | 16u : 0u;
 }
 
-struct RowId {
-  long long r;
-  int wave;
-};
-__device__ __forceinline__ RowId row_of_wave() {
-  const int wave = (int)(threadIdx.x >> 6);
-  return RowId{(long long)blockIdx.x * QT_WAVES + wave, wave};
-}
-
 // ---- gvec_obs_valid_mask ----
 constexpr int MASK_WAVE_DW = 2 * QT_PRED_DW + QT_MAX_TILES / 4;   // the predicates, then one code byte per tile
 
-__global__ __launch_bounds__(64 * QT_WAVES) void obs_valid_mask_kernel(gvec_obs_valid_mask_args P) {
-  __shared__ uint32_t mask_lds[QT_WAVES * MASK_WAVE_DW];
-  const RowId id = row_of_wave();
-  if (id.r >= P.rows) return;                    // the whole wave leaves: everything below is wave-uniform control flow
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void obs_valid_mask_kernel(gvec_obs_valid_mask_args P) {
+  __shared__ uint32_t mask_lds[WAVES_PER_BLOCK * MASK_WAVE_DW];
+  const long long r = wave_item64();
+  if (r >= P.rows) return;                       // the whole wave leaves: everything below is wave-uniform control flow
   const int lane = lane_id(), W = P.width, H = P.height, HW = W * H, A = 5 * HW, slots = (HW + 63) >> 6;
-  uint32_t* L = mask_lds + id.wave * MASK_WAVE_DW;
+  uint32_t* L = mask_lds + block_wave() * MASK_WAVE_DW;
   uint8_t* codes = reinterpret_cast<uint8_t*>(L + 2 * QT_PRED_DW);
-  legal_planes(P.obs + (size_t)id.r * (size_t)P.obs_row_stride, HW, L);
+  legal_planes(P.obs + (size_t)r * (size_t)P.obs_row_stride, HW, L);
   for (int s = 0; s < slots; ++s) {
     const int t = 64 * s + lane;                 // < 1024: the codes of the tiles beyond the board are 0
     codes[t] = (uint8_t)legal_code(L, t, W, H);
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(64 * QT_WAVES) void obs_valid_mask_kernel(gvec_obs_
     const uint32_t t = (uint32_t)i / 5u;
     return ((uint32_t)codes[t] >> ((uint32_t)i - 5u * t)) & 1u;
   };
-  uint8_t* __restrict__ out = P.mask + (size_t)id.r * (size_t)A;
+  uint8_t* __restrict__ out = P.mask + (size_t)r * (size_t)A;
   const int h = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(out) & 3u)) & 3u);
   const int head = h < A ? h : A, dwords = (A - head) >> 2;
   uint32_t* outw = reinterpret_cast<uint32_t*>(out + head);
@@ -111,15 +100,15 @@ template <typename ARGS>
 __device__ __forceinline__ float discount_of(const ARGS& P, long long r) { return P.discount ? P.discount[r] : P.gamma; }
 
 // ---- gvec_q_target ----
-__global__ __launch_bounds__(64 * QT_WAVES) void q_target_kernel(gvec_q_target_args P) {
-  __shared__ uint32_t q_lds[QT_WAVES * 2 * QT_PRED_DW];
-  const RowId id = row_of_wave();
-  if (id.r >= P.rows) return;
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void q_target_kernel(gvec_q_target_args P) {
+  __shared__ uint32_t q_lds[WAVES_PER_BLOCK * 2 * QT_PRED_DW];
+  const long long r = wave_item64();
+  if (r >= P.rows) return;
   const int lane = lane_id(), W = P.width, H = P.height, HW = W * H, slots = (HW + 63) >> 6;
   const size_t A = 5u * (size_t)HW;
-  uint32_t* L = q_lds + id.wave * 2 * QT_PRED_DW;
-  legal_planes(P.next_obs + (size_t)id.r * (size_t)P.obs_row_stride, HW, L);
-  const float* __restrict__ qs = (P.q_select ? P.q_select : P.q_eval) + (size_t)id.r * A;
+  uint32_t* L = q_lds + block_wave() * 2 * QT_PRED_DW;
+  legal_planes(P.next_obs + (size_t)r * (size_t)P.obs_row_stride, HW, L);
+  const float* __restrict__ qs = (P.q_select ? P.q_select : P.q_eval) + (size_t)r * A;
   float best = NEG_INF;
   int pick = NO_INDEX;
   for (int s = 0; s < slots; ++s) {
@@ -139,21 +128,18 @@ __global__ __launch_bounds__(64 * QT_WAVES) void q_target_kernel(gvec_q_target_a
   }
   wave_argmax(best, pick);
   if (lane == 0) {
-    const bool won = pick != NO_INDEX, boot = won && P.done[id.r] == 0;
-    const float nv = boot ? P.q_eval[(size_t)id.r * A + (size_t)(won ? pick : 0)] : 0.0f;
-    const float rw = P.reward[id.r];
-    P.target[id.r] = boot ? __fadd_rn(rw, __fmul_rn(discount_of(P, id.r), nv)) : rw;
-    P.next_action[id.r] = won ? (long long)pick : -1ll;
-    if (P.next_value) P.next_value[id.r] = nv;
+    const bool won = pick != NO_INDEX, boot = won && P.done[r] == 0;
+    const float nv = boot ? P.q_eval[(size_t)r * A + (size_t)(won ? pick : 0)] : 0.0f;
+    const float rw = P.reward[r];
+    P.target[r] = boot ? __fadd_rn(rw, __fmul_rn(discount_of(P, r), nv)) : rw;
+    P.next_action[r] = won ? (long long)pick : -1ll;
+    if (P.next_value) P.next_value[r] = nv;
   }
 }
 
 // ---- gvec_categorical_target ----
 constexpr int C51_WAVE_DW = 2 * QT_PRED_DW + QT_MAX_LEGAL / 2;   // the predicates, then the legal indices as uint16
 
-__device__ __forceinline__ float lane_value(float v, int j) {     // j wave-uniform: v_readlane
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-}
 // softmax over the wave's first N lanes of x (the others hold -inf and get 0)
 __device__ __forceinline__ float wave_softmax(float x, bool on) {
   const float m = wave_max(x);
@@ -161,21 +147,25 @@ __device__ __forceinline__ float wave_softmax(float x, bool on) {
   return e / wave_sum(e);
 }
 
-__global__ __launch_bounds__(64 * QT_WAVES) void categorical_target_kernel(gvec_categorical_target_args P) {
-  __shared__ uint32_t c51_lds[QT_WAVES * C51_WAVE_DW];
-  const RowId id = row_of_wave();
-  if (id.r >= P.rows) return;
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void categorical_target_kernel(gvec_categorical_target_args P) {
+  __shared__ uint32_t c51_lds[WAVES_PER_BLOCK * C51_WAVE_DW];
+  // not wave_item64(): with the row index wave-uniform the 16,384-row shapes of scripts/bench_qtarget.py measured 0.6-0.9 %
+  // slower than the parent in each of three parent / result / parent runs (profiles/learner_units_ab.json), so this
+  // kernel keeps the per-lane spelling
+  const int wave = block_wave();
+  const long long r = (long long)blockIdx.x * WAVES_PER_BLOCK + wave;
+  if (r >= P.rows) return;
   const int lane = lane_id(), W = P.width, H = P.height, HW = W * H, slots = (HW + 63) >> 6, N = P.num_atoms;
   const size_t AN = 5u * (size_t)HW * (size_t)N;
   const bool on = lane < N;
   const float vmin = P.v_min, vmax = P.v_max, delta = (vmax - vmin) / (float)(N - 1);
   const float z = __fadd_rn(vmin, __fmul_rn((float)lane, delta));
-  const float rw = P.reward[id.r];
+  const float rw = P.reward[r];
   int pick = NO_INDEX;
-  if (uni((int)P.done[id.r]) == 0) {             // wave-uniform: a done row reads neither its observation nor any logits
-    uint32_t* L = c51_lds + id.wave * C51_WAVE_DW;
+  if (uni((int)P.done[r]) == 0) {                // wave-uniform: a done row reads neither its observation nor any logits
+    uint32_t* L = c51_lds + wave * C51_WAVE_DW;
     uint16_t* list = reinterpret_cast<uint16_t*>(L + 2 * QT_PRED_DW);
-    legal_planes(P.next_obs + (size_t)id.r * (size_t)P.obs_row_stride, HW, L);
+    legal_planes(P.next_obs + (size_t)r * (size_t)P.obs_row_stride, HW, L);
     // compaction: the legal indices in ascending order
     int count = 0;
     for (int s = 0; s < slots; ++s) {
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(64 * QT_WAVES) void categorical_target_kernel(gvec_
     }
     wave_lds_fence();
     // Q_i = sum_j softmax(logits_select[i])_j z_j over the legal i
-    const float* __restrict__ sel = (P.logits_select ? P.logits_select : P.logits_eval) + (size_t)id.r * AN;
+    const float* __restrict__ sel = (P.logits_select ? P.logits_select : P.logits_eval) + (size_t)r * AN;
     float best = NEG_INF;
     for (int k0 = 0; k0 < count; k0 += QT_UNROLL) {
       int a[QT_UNROLL];
@@ -218,9 +208,9 @@ __global__ __launch_bounds__(64 * QT_WAVES) void categorical_target_kernel(gvec_
   const bool boot = pick != NO_INDEX;
   float p = lane == 0 ? 1.0f : 0.0f, tz = rw;
   if (boot) {
-    const float xe = on ? P.logits_eval[(size_t)id.r * AN + (size_t)pick * (size_t)N + (size_t)lane] : NEG_INF;
+    const float xe = on ? P.logits_eval[(size_t)r * AN + (size_t)pick * (size_t)N + (size_t)lane] : NEG_INF;
     p = wave_softmax(xe, on);
-    tz = __fadd_rn(rw, __fmul_rn(discount_of(P, id.r), z));
+    tz = __fadd_rn(rw, __fmul_rn(discount_of(P, r), z));
   }
   tz = tz < vmin ? vmin : (tz > vmax ? vmax : tz);
   float b = (tz - vmin) / delta;
@@ -229,28 +219,19 @@ __global__ __launch_bounds__(64 * QT_WAVES) void categorical_target_kernel(gvec_
   const float k = (float)lane;
   float acc = 0.0f;
   for (int j = 0; j < N; ++j) {
-    const float w = 1.0f - fabsf(lane_value(b, j) - k);
-    acc = acc + lane_value(p, j) * (w > 0.0f ? w : 0.0f);
+    const float w = 1.0f - fabsf(rdlane(b, j) - k);
+    acc = acc + rdlane(p, j) * (w > 0.0f ? w : 0.0f);
   }
-  if (on) P.m[(size_t)id.r * (size_t)N + (size_t)lane] = acc;
-  if (lane == 0) P.next_action[id.r] = boot ? (long long)pick : -1ll;
+  if (on) P.m[(size_t)r * (size_t)N + (size_t)lane] = acc;
+  if (lane == 0) P.next_action[r] = boot ? (long long)pick : -1ll;
 }
-
-inline dim3 qt_grid(long long rows) { return dim3((unsigned)((rows + QT_WAVES - 1) / QT_WAVES)); }
 
 }  // namespace
 
-hipError_t launch_obs_valid_mask(const gvec_obs_valid_mask_args& a, hipStream_t s) {
-  hipLaunchKernelGGL(obs_valid_mask_kernel, qt_grid(a.rows), dim3(64 * QT_WAVES), 0, s, a);
-  return hipGetLastError();
-}
-hipError_t launch_q_target(const gvec_q_target_args& a, hipStream_t s) {
-  hipLaunchKernelGGL(q_target_kernel, qt_grid(a.rows), dim3(64 * QT_WAVES), 0, s, a);
-  return hipGetLastError();
-}
+hipError_t launch_obs_valid_mask(const gvec_obs_valid_mask_args& a, hipStream_t s) { return launch_waves(obs_valid_mask_kernel, a.rows, s, a); }
+hipError_t launch_q_target(const gvec_q_target_args& a, hipStream_t s) { return launch_waves(q_target_kernel, a.rows, s, a); }
 hipError_t launch_categorical_target(const gvec_categorical_target_args& a, hipStream_t s) {
-  hipLaunchKernelGGL(categorical_target_kernel, qt_grid(a.rows), dim3(64 * QT_WAVES), 0, s, a);
-  return hipGetLastError();
+  return launch_waves(categorical_target_kernel, a.rows, s, a);
 }
 
 }  // namespace gvec

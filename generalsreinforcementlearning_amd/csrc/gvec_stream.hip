@@ -2,6 +2,7 @@
 // collector that pushes every worker's transition into the replay ring.
 #include "gvec_dispatch.hpp"
 #include "gvec_collect.hpp"
+#include "gvec_rows.hpp"
 #include "gvec_turn.hpp"
 
 namespace gvec {
@@ -72,31 +73,21 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void stream_delta_kernel(Stre
 
 // gvec_stream_deltas_packed: exclusive prefix sum of the per-env update counts (one workgroup: B is a few hundred thousand
 // small integers) and the row-to-stream compaction that follows it.
-__global__ __launch_bounds__(1024) void scan_counts_kernel(const int32_t* count, long long* offset, int32_t n) {
-  __shared__ long long part[1024];
-  const int tid = (int)threadIdx.x;
-  const int per = (n + 1023) / 1024;
-  const int lo = tid * per, hi = (lo + per < n) ? lo + per : n;
-  long long sum = 0;
-  for (int i = lo; i < hi; ++i) sum += count[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan of the 1,024 partial sums
-    const long long add = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
+__global__ __launch_bounds__(SCAN_THREADS) void scan_counts_kernel(const int32_t* count, long long* offset, int32_t n) {
+  __shared__ long long part[1][SCAN_THREADS];
+  const ScanRun r = scan_run(n);
+  long long run[1] = {0};
+  for (long long i = r.lo; i < r.hi; ++i) run[0] += count[i];
+  block_scan(part, run);
+  for (long long i = r.lo; i < r.hi; ++i) {
+    offset[i] = run[0];
+    run[0] += count[i];
   }
-  long long run = part[tid] - sum;             // exclusive base of this thread's chunk
-  for (int i = lo; i < hi; ++i) {
-    offset[i] = run;
-    run += count[i];
-  }
-  if (tid == 1023) offset[n] = part[1023];
+  if (threadIdx.x == SCAN_THREADS - 1) offset[n] = part[0][SCAN_THREADS - 1];
 }
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void pack_updates_kernel(const unsigned long long* rows, const int32_t* count, const long long* offset,
                                                                             unsigned long long* packed, int32_t n, int32_t cap, long long capacity) {
-  const int env = (int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));  // per lane, not wave_item(): nothing here needs it uniform
+  const int env = wave_item();
   if (env >= n) return;
   const long long base = offset[env];
   const int c = count[env];
@@ -137,49 +128,32 @@ __global__ __launch_bounds__(256) void collect_flags_kernel(gvec_collect_args A)
   A.episode_reward[w] = er;
   A.episode_length[w] = el;
 }
+// run[0] += the live bits, run[1] += the over bits of the 64 flag bytes of group g
+__device__ __forceinline__ void add_group_flags(const CollectScratch& S, long long g, long long (&run)[2]) {
+  const uint4* f = reinterpret_cast<const uint4*>(S.flag + (size_t)g * 64);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint4 v = f[q];
+    run[0] += __popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) + __popc(v.w & 0x01010101u);
+    run[1] += __popc(v.x & 0x02020202u) + __popc(v.y & 0x02020202u) + __popc(v.z & 0x02020202u) + __popc(v.w & 0x02020202u);
+  }
+}
 // one workgroup: exclusive prefix counts per 64-worker group (a thread owns a run of consecutive groups, 64 flag bytes each),
 // then the counters move on - the push works from the snapshot
-__global__ __launch_bounds__(1024) void collect_scan_kernel(gvec_collect_args A) {
-  __shared__ long long part[2][1024];
+__global__ __launch_bounds__(SCAN_THREADS) void collect_scan_kernel(gvec_collect_args A) {
+  __shared__ long long part[2][SCAN_THREADS];
   const CollectScratch S = collect_scratch(A.scratch, A.num_envs);
-  const int G = collect_groups(A.num_envs);
-  const int tid = (int)threadIdx.x;
-  const int per = (G + 1023) / 1024;
-  const int lo = tid * per < G ? tid * per : G, hi = (lo + per < G) ? lo + per : G;
-  long long nl = 0, no = 0;
-  for (int g = lo; g < hi; ++g) {
-    const uint4* f = reinterpret_cast<const uint4*>(S.flag + (size_t)g * 64);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint4 v = f[q];
-      nl += __popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) + __popc(v.w & 0x01010101u);
-      no += __popc(v.x & 0x02020202u) + __popc(v.y & 0x02020202u) + __popc(v.z & 0x02020202u) + __popc(v.w & 0x02020202u);
-    }
+  const ScanRun r = scan_run(collect_groups(A.num_envs));
+  long long run[2] = {0, 0};                   // live, over: both counts ride one scan
+  for (long long g = r.lo; g < r.hi; ++g) add_group_flags(S, g, run);
+  block_scan(part, run);
+  for (long long g = r.lo; g < r.hi; ++g) {
+    S.base_live[g] = run[0];
+    S.base_over[g] = run[1];
+    add_group_flags(S, g, run);
   }
-  part[0][tid] = nl;
-  part[1][tid] = no;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan of the 1,024 partial sums, both counts at once
-    const long long a0 = (tid >= off) ? part[0][tid - off] : 0, a1 = (tid >= off) ? part[1][tid - off] : 0;
-    __syncthreads();
-    part[0][tid] += a0;
-    part[1][tid] += a1;
-    __syncthreads();
-  }
-  long long rl = part[0][tid] - nl, ro = part[1][tid] - no;
-  for (int g = lo; g < hi; ++g) {
-    S.base_live[g] = rl;
-    S.base_over[g] = ro;
-    const uint4* f = reinterpret_cast<const uint4*>(S.flag + (size_t)g * 64);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint4 v = f[q];
-      rl += __popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) + __popc(v.w & 0x01010101u);
-      ro += __popc(v.x & 0x02020202u) + __popc(v.y & 0x02020202u) + __popc(v.z & 0x02020202u) + __popc(v.w & 0x02020202u);
-    }
-  }
-  if (tid == 1023) {
-    const long long pushed = part[0][1023], ended = part[1][1023];
+  if (threadIdx.x == SCAN_THREADS - 1) {
+    const long long pushed = part[0][SCAN_THREADS - 1], ended = part[1][SCAN_THREADS - 1];
     long long* R = reinterpret_cast<long long*>(A.ring_counters);
     long long* P = reinterpret_cast<long long*>(A.pool_counters);
     S.snap[0] = R[0];
@@ -196,11 +170,10 @@ __global__ __launch_bounds__(1024) void collect_scan_kernel(gvec_collect_args A)
 }
 // `wpe` wavefronts per worker (a power of two): ReplayBuffer.push of its transition, and its episode result
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void collect_push_kernel(gvec_collect_args A, int wpe_shift) {
-  const int gw = wave_item();
-  const int w = gw >> wpe_shift, part = gw & ((1 << wpe_shift) - 1);
-  if (w >= A.num_envs) return;
+  const WaveSplit sp = wave_split(wpe_shift);
+  if (sp.item >= A.num_envs) return;
   const CollectScratch S = collect_scratch(A.scratch, A.num_envs);
-  const int lane = lane_id();
+  const int w = (int)sp.item, part = sp.part, lane = lane_id();
   const int g = w >> 6, at = w & 63;
   const uint32_t mine = S.flag[(size_t)g * 64 + lane];
   const unsigned long long below = (1ull << at) - 1;
@@ -212,8 +185,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void collect_push_kernel(gvec
     const float* s1 = A.next_state + (size_t)w * A.obs_floats;
     float* d0 = A.ring_state + (size_t)slot * A.obs_floats;
     float* d1 = A.ring_next_state + (size_t)slot * A.obs_floats;
-    copy_row(s0, d0, A.obs_floats, part, lane, wpe_shift);
-    copy_row(s1, d1, A.obs_floats, part, lane, wpe_shift);
+    copy_row(s0, d0, A.obs_floats, sp);
+    copy_row(s1, d1, A.obs_floats, sp);
     if (part == 0) {
       if (lane == 0) {
         A.ring_action[slot] = A.action[w];
@@ -240,7 +213,7 @@ hipError_t launch_stream_deltas(const Variant& v, const StreamDeltaArgs& a, hipS
 }
 hipError_t launch_pack_updates(const unsigned long long* rows, const int32_t* count, long long* offset, unsigned long long* packed, int32_t n,
                                int32_t cap, long long capacity, hipStream_t s) {
-  hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, s, count, offset, n);
+  hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, count, offset, n);
   return launch_waves(pack_updates_kernel, n, s, rows, count, offset, packed, n, cap, capacity);
 }
 size_t pool_collect_scratch_bytes(int32_t n) {
@@ -248,12 +221,11 @@ size_t pool_collect_scratch_bytes(int32_t n) {
   return (2 * (g + 1) + 2) * 8 + (size_t)n * 8 + (size_t)n * 4 + g * 64;
 }
 hipError_t launch_pool_collect(const gvec_collect_args& a, hipStream_t s) {
-  const int padded = collect_groups(a.num_envs) * 64;
-  hipLaunchKernelGGL(collect_flags_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(collect_scan_kernel, dim3(1), dim3(1024), 0, s, a);
-  int shift = 0;                                   // enough wavefronts to fill 256 CUs when there are few workers
-  while (shift < 3 && ((long long)a.num_envs << shift) < 16384) ++shift;
-  return launch_waves(collect_push_kernel, a.num_envs << shift, s, a, shift);
+  const hipError_t e = launch_threads(collect_flags_kernel, collect_groups(a.num_envs) * 64, s, a);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(collect_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, a);
+  const int shift = split_shift(a.num_envs);
+  return launch_waves(collect_push_kernel, (long long)a.num_envs << shift, s, a, shift);
 }
 
 }  // namespace gvec

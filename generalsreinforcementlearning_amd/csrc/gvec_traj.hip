@@ -5,22 +5,14 @@
 // position p = t * N + n of every store.  flags[p] carries the episode protocol (GVEC_TRAJ_VALID / _TERMINAL / _CUT), so the
 // recurrence and the gather never look at the env's own arrays again.
 #include "gvec_launch.hpp"
+#include "gvec_rows.hpp"
 
 namespace gvec {
 
 namespace {
 
-constexpr int TRAJ_WAVES = 4;          // wavefronts per workgroup of the row mover
 constexpr int GAE_ROWS = 32;           // rows a lane has in flight: the loads do not depend on the recurrence
 constexpr int COMPACT_BLOCK = 1024;    // positions per workgroup of the compaction (256 threads, four each)
-
-__device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63u); }
-__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long uni_ll(long long v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
 
 // ---- record: one thread per stream ----
 __global__ __launch_bounds__(256) void traj_record_kernel(gvec_traj_record_args A) {
@@ -42,14 +34,9 @@ __global__ __launch_bounds__(256) void traj_record_kernel(gvec_traj_record_args 
 }
 
 // ---- GAE: one lane per stream walks t = T-1 .. 0; a wavefront's loads of a row are one coalesced line per array ----
-__device__ __forceinline__ double wave_sum(double x) {   // a fixed butterfly: the same bits on every run
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-  return x;
-}
 __global__ __launch_bounds__(64) void traj_gae_kernel(gvec_traj_gae_args A) {
   const long long N = A.N, T = A.T;
-  const long long n0 = (long long)blockIdx.x * 64 + lane();
+  const long long n0 = (long long)blockIdx.x * 64 + lane_id();
   const bool act = n0 < N;
   const long long n = act ? n0 : N - 1;             // the tail lanes of the last wavefront read a real stream and store nothing
   const double* __restrict__ reward = A.reward;
@@ -97,10 +84,10 @@ __global__ __launch_bounds__(64) void traj_gae_kernel(gvec_traj_gae_args A) {
       }
     }
   }
-  cnt = wave_sum(cnt);
+  cnt = wave_sum(cnt);                              // fixed butterflies: the same bits on every run
   s1 = wave_sum(s1);
   s2 = wave_sum(s2);
-  if (lane() == 0) {
+  if (lane_id() == 0) {
     double* part = static_cast<double*>(A.scratch) + (size_t)blockIdx.x * 3;
     part[0] = cnt;
     part[1] = s1;
@@ -143,7 +130,7 @@ __device__ __forceinline__ void compact_ballots(const uint8_t* flags, long long 
     const long long p = blk * COMPACT_BLOCK + k * 256 + tid;
     const bool v = p < total && (flags[p < total ? p : 0] & GVEC_TRAJ_VALID);
     m[k] = __ballot(v);
-    if (lane() == 0) runs[k * 4 + wave] = __popcll(m[k]);
+    if (lane_id() == 0) runs[k * 4 + wave] = __popcll(m[k]);
   }
   __syncthreads();
 }
@@ -158,30 +145,20 @@ __global__ __launch_bounds__(256) void traj_compact_count_kernel(gvec_traj_compa
   }
 }
 // one workgroup: exclusive prefix of cnt[G] (a thread owns a run of consecutive groups), and the total
-__global__ __launch_bounds__(1024) void traj_compact_scan_kernel(gvec_traj_compact_args A) {
-  __shared__ long long part[1024];
+__global__ __launch_bounds__(SCAN_THREADS) void traj_compact_scan_kernel(gvec_traj_compact_args A) {
+  __shared__ long long part[1][SCAN_THREADS];
   const long long G = compact_groups(A.T * A.N);
   const long long* cnt = static_cast<const long long*>(A.scratch);
   long long* base = static_cast<long long*>(A.scratch) + G;
-  const int tid = (int)threadIdx.x;
-  const long long per = (G + 1023) / 1024;
-  const long long lo = tid * per < G ? tid * per : G, hi = lo + per < G ? lo + per : G;
-  long long mine = 0;
-  for (long long gi = lo; gi < hi; ++gi) mine += cnt[gi];
-  part[tid] = mine;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {        // Hillis-Steele inclusive scan of the 1,024 partial sums
-    const long long a = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += a;
-    __syncthreads();
+  const ScanRun r = scan_run(G);
+  long long run[1] = {0};
+  for (long long gi = r.lo; gi < r.hi; ++gi) run[0] += cnt[gi];
+  block_scan(part, run);
+  for (long long gi = r.lo; gi < r.hi; ++gi) {
+    base[gi] = run[0];
+    run[0] += cnt[gi];
   }
-  long long run = part[tid] - mine;
-  for (long long gi = lo; gi < hi; ++gi) {
-    base[gi] = run;
-    run += cnt[gi];
-  }
-  if (tid == 1023) *reinterpret_cast<long long*>(A.count) = part[1023];
+  if (threadIdx.x == SCAN_THREADS - 1) *reinterpret_cast<long long*>(A.count) = part[0][SCAN_THREADS - 1];
 }
 __global__ __launch_bounds__(256) void traj_compact_write_kernel(gvec_traj_compact_args A) {
   __shared__ int runs[16];
@@ -195,90 +172,20 @@ __global__ __launch_bounds__(256) void traj_compact_write_kernel(gvec_traj_compa
   for (int k = 0; k < 4; ++k) {
     int before = 0;
     for (int q = 0; q < k * 4 + wave; ++q) before += runs[q];
-    if ((m[k] >> lane()) & 1) idx[base + before + __popcll(m[k] & ((1ull << lane()) - 1))] = blockIdx.x * (long long)COMPACT_BLOCK + k * 256 + tid;
+    if ((m[k] >> lane_id()) & 1) idx[base + before + __popcll(m[k] & ((1ull << lane_id()) - 1))] = blockIdx.x * (long long)COMPACT_BLOCK + k * 256 + tid;
   }
 }
 
-// ---- gather: the row mover ----
-// A row of n floats from s to d, both only dword-aligned (a row is 9 * W * H floats: 8,100 bytes at 15x15) and not alike: the
-// scheme of gvec_pool_collect's copy_row (gvec_collect.hpp), restated here so that no existing kernel's code changes.
-// Sixteen bytes per lane with BOTH sides on 16-byte boundaries: destination quad j (floats [kd + 4j, kd + 4j + 4) of the row)
-// is cut out of the aligned source quads j and j + 1 counted from s + kd - a, a = the floats by which the two sides differ.
-// Only quads that lie inside the row are read; the floats before / after that body go one by one (part 0).
-template <int D>
-__device__ __forceinline__ void move_quads(const float4* __restrict__ sq, float4* __restrict__ dq, int jlo, int jhi, int first, int stride) {
-#pragma unroll 4
-  for (int j = jlo + first; j < jhi; j += stride) {
-    const float4 lo = sq[j];
-    float4 o;
-    if (D == 0) {
-      o = lo;
-    } else {
-      const float4 hi = sq[j + 1];
-      if (D == 1) o = make_float4(lo.y, lo.z, lo.w, hi.x);
-      if (D == 2) o = make_float4(lo.z, lo.w, hi.x, hi.y);
-      if (D == 3) o = make_float4(lo.w, hi.x, hi.y, hi.z);
-    }
-    dq[j] = o;
-  }
-}
-__device__ __forceinline__ void move_row_f32(const float* __restrict__ s, float* __restrict__ d, int n, int part, int shift) {
-  const int kd = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(d) & 15u)) & 15u) >> 2);   // floats before d is 16-byte aligned
-  const int a = uni_i((int)((reinterpret_cast<uintptr_t>(s + kd) >> 2) & 3u));                   // s + kd sits a floats into its quad
-  // source quad j spans floats [kd - a + 4j, + 4) of the row; j and (a != 0) j + 1 must lie in [0, n)
-  const int jlo = a > kd ? 1 : 0;
-  const int room = a ? n - 8 - kd + a : n - 4 - kd;
-  const int jhi = room < 0 ? jlo : (room / 4 + 1 > jlo ? room / 4 + 1 : jlo);                    // exclusive
-  const float4* sq = reinterpret_cast<const float4*>(s + kd - a);
-  float4* dq = reinterpret_cast<float4*>(d + kd);
-  const int first = part * 64 + lane(), stride = 64 << shift;
-  switch (a) {
-    case 0: move_quads<0>(sq, dq, jlo, jhi, first, stride); break;
-    case 1: move_quads<1>(sq, dq, jlo, jhi, first, stride); break;
-    case 2: move_quads<2>(sq, dq, jlo, jhi, first, stride); break;
-    default: move_quads<3>(sq, dq, jlo, jhi, first, stride); break;
-  }
-  if (part == 0) {
-    int head = kd + 4 * jlo, tail = kd + 4 * jhi;       // [0, head) and [tail, n): a few floats each (all of a very short row)
-    if (jhi == jlo) head = tail = 0;
-    for (int k = lane(); k < head && k < n; k += 64) d[k] = s[k];
-    for (int k = tail + lane(); k < n; k += 64) d[k] = s[k];
-  }
-}
-// The same for a row of n BYTES (a mask row is 5 * W * H bytes: 1,125 at 15x15, aligned to nothing): four bytes per lane, the
-// stores on dword boundaries, a destination dword cut out of two aligned source dwords by v_alignbyte.
-__device__ __forceinline__ void move_row_u8(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int n, int part, int shift) {
-  const int kd = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(d) & 3u)) & 3u);
-  const int a = uni_i((int)(reinterpret_cast<uintptr_t>(s + kd) & 3u));
-  const int jlo = a > kd ? 1 : 0;
-  const int room = a ? n - 8 - kd + a : n - 4 - kd;
-  const int jhi = room < 0 ? jlo : (room / 4 + 1 > jlo ? room / 4 + 1 : jlo);
-  const uint32_t* __restrict__ sw = reinterpret_cast<const uint32_t*>(s + kd - a);
-  uint32_t* __restrict__ dw = reinterpret_cast<uint32_t*>(d + kd);
-  const int first = part * 64 + lane(), stride = 64 << shift;
-  if (a == 0) {
-    for (int j = jlo + first; j < jhi; j += stride) dw[j] = sw[j];
-  } else {
-    for (int j = jlo + first; j < jhi; j += stride) dw[j] = __builtin_amdgcn_alignbyte(sw[j + 1], sw[j], (uint32_t)a);
-  }
-  if (part == 0) {
-    int head = kd + 4 * jlo, tail = kd + 4 * jhi;
-    if (jhi == jlo) head = tail = 0;
-    for (int k = lane(); k < head && k < n; k += 64) d[k] = s[k];
-    for (int k = tail + lane(); k < n; k += 64) d[k] = s[k];
-  }
-}
-
-// 1 << shift wavefronts per minibatch row
-__global__ __launch_bounds__(64 * TRAJ_WAVES) void traj_gather_kernel(gvec_traj_gather_args A, int shift) {
-  const long long gw = uni_ll((long long)blockIdx.x * TRAJ_WAVES + (threadIdx.x >> 6));
-  const long long i = gw >> shift;
-  const int part = (int)(gw & ((1 << shift) - 1));
+// ---- gather: 1 << shift wavefronts per minibatch row (a row is 9 * W * H floats and 5 * W * H mask bytes: 8,100 and 1,125
+// bytes at 15x15, aligned to nothing wider than an element - gvec_rows.hpp) ----
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void traj_gather_kernel(gvec_traj_gather_args A, int shift) {
+  const WaveSplit w = wave_split(shift);
+  const long long i = w.item;
   if (i >= A.M) return;
   const long long p = uni_ll(A.pos[i]);
   float* dobs = A.out_obs + (size_t)i * A.obs_floats;
   uint8_t* dmask = A.out_mask + (size_t)i * A.mask_bytes;
-  const int first = part * 64 + lane(), stride = 64 << shift;
+  const int first = w.first, stride = w.stride;
   if (p < 0 || p >= A.T * A.N) {                   // a position the host never saw: a zeroed row that weighs nothing
     for (int k = first; k < A.obs_floats; k += stride) dobs[k] = 0.0f;
     for (int k = first; k < A.mask_bytes; k += stride) dmask[k] = 0;
@@ -289,8 +196,8 @@ __global__ __launch_bounds__(64 * TRAJ_WAVES) void traj_gather_kernel(gvec_traj_
     }
     return;
   }
-  move_row_f32(A.obs + (size_t)p * A.obs_floats, dobs, A.obs_floats, part, shift);
-  if (A.mask_bytes > 0) move_row_u8(A.mask + (size_t)p * A.mask_bytes, dmask, A.mask_bytes, part, shift);
+  copy_row(A.obs + (size_t)p * A.obs_floats, dobs, A.obs_floats, w);
+  if (A.mask_bytes > 0) move_row_u8(A.mask + (size_t)p * A.mask_bytes, dmask, A.mask_bytes, w);
   if (first == 0) {
     A.out_action[i] = A.action[p];
     A.out_logp[i] = A.logp[p];
@@ -317,9 +224,7 @@ size_t traj_scratch_bytes(long long T, long long N) {
   return ((gae > compact ? gae : compact) + 255) / 256 * 256;
 }
 hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s) {
-  const long long N = (long long)a.num_envs * a.num_learners;
-  hipLaunchKernelGGL(traj_record_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_threads(traj_record_kernel, (long long)a.num_envs * a.num_learners, s, a);
 }
 hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s) {
   const long long groups = (a.N + 63) / 64;
@@ -330,16 +235,13 @@ hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s) {
 hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s) {
   const dim3 grid((unsigned)compact_groups(a.T * a.N));
   hipLaunchKernelGGL(traj_compact_count_kernel, grid, dim3(256), 0, s, a);
-  hipLaunchKernelGGL(traj_compact_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(traj_compact_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, a);
   hipLaunchKernelGGL(traj_compact_write_kernel, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s) {
-  int shift = 0;                                   // enough wavefronts to fill 256 CUs when the batch is small
-  while (shift < 3 && (a.M << shift) < 16384) ++shift;
-  const long long waves = a.M << shift;
-  hipLaunchKernelGGL(traj_gather_kernel, dim3((unsigned)((waves + TRAJ_WAVES - 1) / TRAJ_WAVES)), dim3(64 * TRAJ_WAVES), 0, s, a, shift);
-  return hipGetLastError();
+  const int shift = split_shift(a.M);
+  return launch_waves(traj_gather_kernel, a.M << shift, s, a, shift);
 }
 
 }  // namespace gvec

@@ -32,9 +32,15 @@ def test_header_dims_are_unpacked_in_one_place():
 
 
 def test_wave_to_item_index_is_written_once():
-    # the wave-uniform item of a wavefront, blockIdx.x * WAVES_PER_BLOCK + its wave, is wave_item() of gvec_dispatch.hpp
-    assert [n for n, _ in _sites(r"uni\(\s*\(int\)\s*\(?\s*blockIdx\.x\s*\*\s*WAVES_PER_BLOCK")] == ["gvec_dispatch.hpp"]
+    # the wave-uniform item of a wavefront, blockIdx.x * WAVES_PER_BLOCK + its wave, is wave_item() of gvec_waves.hpp
+    assert [n for n, _ in _sites(r"uni\(\s*\(int\)\s*\(?\s*blockIdx\.x\s*\*\s*WAVES_PER_BLOCK")] == ["gvec_waves.hpp"]
     assert [n for n, _ in _sites(r"threadIdx\.x\s*>>\s*6\)\s*,\s*lane")] == []  # the old prologue's first line
+    # ... in 32 and in 64 bits; no unit multiplies blockIdx.x by a waves-per-workgroup constant of its own, and only
+    # obs_memory_kernel and categorical_target_kernel spell the index out (with the shared constant: their comments say
+    # what the shared call cost them)
+    assert ([n for n, _ in _sites(r"blockIdx\.x\s*\*\s*(\(\w+\))?\s*\w*WAVES\w*")]
+            == ["gvec_memory.hip", "gvec_qtarget.hip"] + ["gvec_waves.hpp"] * 2)
+    assert [n for n, _ in _sites(r"constexpr\s+int\s+\w*WAVES\w*\s*=")] == ["gvec_waves.hpp"]
 
 
 def test_gym_stage_size_is_written_once():
