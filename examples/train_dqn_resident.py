@@ -10,11 +10,13 @@ observation, Huber loss, gradient clipping at 1.0, a hard target update, fixed p
 geometrically over the workers); the code is this repo's own.  An example, not part of the measured hot path.
 
     python examples/train_dqn_resident.py --num-envs 4096 --updates 200 [--prioritized] [--n-step 3]
-        [--masked-targets | --double | --categorical --atoms 51 --v-min -110 --v-max 110]
+        [--masked-targets | --double | --categorical --atoms 51 --v-min -110 --v-max 110] [--augment]
 
 --masked-targets bootstraps from the best LEGAL action of the next state (the mask is rebuilt from the sampled next
 observation: the ring stores none), --double picks that action with the online network (Double DQN), --categorical learns a
 distribution over --atoms returns per action (C51) with the same masked Double selection: q_targets.py, one launch per batch.
+--augment gives every sampled row a board symmetry of its own (symmetry.py, one launch per batch) before the targets: the
+network ends in a Linear over the flattened board, so it shares nothing between a position and its mirror image.
 """
 import argparse
 import json
@@ -30,6 +32,7 @@ import torch.nn.functional as F
 from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
 from generalsreinforcementlearning_amd.q_targets import categorical_target, double_q_target
 from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+from generalsreinforcementlearning_amd.symmetry import augment_transition
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
 
 
@@ -91,6 +94,7 @@ def main(argv=None):
     ap.add_argument("--atoms", type=int, default=51)
     ap.add_argument("--v-min", type=float, default=-110.0, help="the support's bounds: the default covers the env's terminal +-100")
     ap.add_argument("--v-max", type=float, default=110.0)
+    ap.add_argument("--augment", action="store_true", help="a random board symmetry per sampled row (mirrors, quarter turns)")
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
@@ -122,6 +126,8 @@ def main(argv=None):
     pool = ParallelVecEnvPool(B, lambda n: GeneralsVecEnv(n, board_width=a.board, board_height=a.board, max_players=2, max_turns=a.max_steps_per_episode,
                                                          seed=a.seed, device_outputs=True),
                               policy, buf, max_steps_per_episode=a.max_steps_per_episode, seed=a.seed, batched_actions=True)
+    sym_gen = torch.Generator(device=dev)
+    sym_gen.manual_seed(a.seed)
     pool.collect(a.warmup_steps)
     losses, t0 = [], time.perf_counter()
     for u in range(a.updates):
@@ -138,6 +144,8 @@ def main(argv=None):
             else:
                 s, act, r, ns, d = buf.sample_arrays(a.batch_size)
             disc = a.gamma
+        if a.augment:                               # s, act and ns under one symmetry per row; the masked targets rebuild the mask from ns
+            s, act, ns, _ = augment_transition(s, act, ns, generator=sym_gen)
         if a.categorical:
             with torch.no_grad():               # the projected distribution of the best legal next action (picked by the online net)
                 m, _ = categorical_target(ns, target(ns), r, disc, d, a.v_min, a.v_max, logits_select=q(ns))
@@ -176,6 +184,8 @@ def main(argv=None):
            "mean_episode_reward": sum(x[0] for x in results) / max(len(results), 1), "ring_fill": len(buf), "n_step": a.n_step}
     if a.categorical or a.masked_targets or a.double:
         out["targets"] = f"categorical{a.atoms}" if a.categorical else "double" if a.double else "masked"
+    if a.augment:
+        out["augment"] = True
     pool._env.close()
     print(json.dumps(out))
     return out

@@ -121,6 +121,22 @@ class CategoricalTargetArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("next_obs", "logits_eval", "logits_select", "reward", "discount", "done", "m", "next_action")])
 
 
+SYM_MAX_PLANE_SETS = 4   # GVEC_SYM_MAX_PLANE_SETS
+
+
+class SymPlaneSet(C.Structure):
+    """gvec_sym_plane_set (include/generals_vec.h): in and out are device memory."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_int32), ("in_row_stride", C.c_int64)]
+
+
+class ObsSymmetryArgs(C.Structure):
+    """gvec_obs_symmetry_args (include/generals_vec.h): every pointer is device memory; all but sym may be None."""
+    _fields_ = ([("rows", C.c_int64)] + [(n, C.c_int32) for n in ("width", "height", "num_sets", "inverse", "reserved")]
+                + [("sets", SymPlaneSet * SYM_MAX_PLANE_SETS)]
+                + [(n, C.c_void_p) for n in ("sym", "mask_in", "mask_out", "values_in", "values_out", "action_in", "action_out",
+                                             "applied")])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -194,6 +210,7 @@ SYMBOLS = {
     "gvec_obs_valid_mask": (_i32, [_i32, _vp, C.POINTER(ObsValidMaskArgs)]),
     "gvec_q_target": (_i32, [_i32, _vp, C.POINTER(QTargetArgs)]),
     "gvec_categorical_target": (_i32, [_i32, _vp, C.POINTER(CategoricalTargetArgs)]),
+    "gvec_obs_symmetry": (_i32, [_i32, _vp, C.POINTER(ObsSymmetryArgs)]),
     "gvec_gym_observe":(_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

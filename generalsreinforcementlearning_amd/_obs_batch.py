@@ -1,5 +1,6 @@
-"""What the fronts of the observation-batch entry points share (features.py, memory.py, q_targets.py, and the slots of
-selfplay_env.py): a batch of nine-plane observations, rows flattened, read in place when the rows have one common stride.
+"""What the fronts of the observation-batch entry points share (features.py, memory.py, q_targets.py, symmetry.py, and the
+slots of selfplay_env.py): a batch of nine-plane observations (symmetry.py: of P planes), rows flattened, read in place when
+the rows have one common stride.
 Small checks that each caller composes in its own order; every one raises before anything touches a device."""
 
 MAX_DIM = 32          # GVEC_MAX_DIM
@@ -89,11 +90,29 @@ def row_stride(obs, tail, row_floats):
 
 def in_place(obs, tail, H, W):
     """(obs to read, its row stride in floats): obs itself where its rows have one common stride, else a contiguous copy"""
-    obs = obs.detach()
-    if obs.is_contiguous():                          # the common case, without walking the strides
-        return obs, 9 * W * H
-    stride = row_stride(obs, tail, 9 * W * H)
-    return (obs, stride) if stride is not None else (obs.contiguous(), 9 * W * H)
+    return in_place_planes(obs, tail, 9, H, W)
+
+
+def in_place_planes(t, tail, P, H, W):
+    """in_place for rows of P planes: [..., P, H, W] (tail 3) or [..., P, H * W] (tail 2)"""
+    t = t.detach()
+    if t.is_contiguous():                            # the common case, without walking the strides
+        return t, P * W * H
+    stride = row_stride(t, tail, P * W * H)
+    return (t, stride) if stride is not None else (t.contiguous(), P * W * H)
+
+
+def read_plane_shape(t, name, max_planes):
+    """(leading shape, rows, P, H, W) of planes [..., P, H, W] with 1 <= P <= max_planes, or ValueError"""
+    if t.dim() < 3 or not 1 <= t.shape[-3] <= max_planes:
+        raise ValueError(f"{name} {tuple(t.shape)} is not [..., P, H, W] with P in [1, {max_planes}]")
+    P, H, W = int(t.shape[-3]), int(t.shape[-2]), int(t.shape[-1])
+    lead = tuple(t.shape[:-3])
+    check_board(W, H)
+    rows = 1
+    for d in lead:
+        rows *= int(d)
+    return lead, rows, P, H, W
 
 
 def check_out(out, name, dtypes, dtype_words, numel, dev):

@@ -1,7 +1,7 @@
 // gvec_api_obs.hip — the entry points that read a batch of nine-plane observations: the strategic feature planes, the
-// fog-of-war memory planes and the masked Q targets.  Handle-free like gvec_api_replay.hip's: they check their arguments,
-// which needs no device, and end in ON_DEVICE.  Host only (gvec_handle.hpp); the kernels are in gvec_features.hip,
-// gvec_memory.hip and gvec_qtarget.hip.
+// fog-of-war memory planes, the masked Q targets and the board symmetries.  Handle-free like gvec_api_replay.hip's: they check
+// their arguments, which needs no device, and end in ON_DEVICE.  Host only (gvec_handle.hpp); the kernels are in
+// gvec_features.hip, gvec_memory.hip, gvec_qtarget.hip and gvec_symmetry.hip.
 #include <cmath>
 
 #include "gvec_handle.hpp"
@@ -120,6 +120,75 @@ int32_t gvec_categorical_target(int32_t device, void* hip_stream, const gvec_cat
   if (!a->next_obs || !a->logits_eval || !a->reward || !a->done || !a->m || !a->next_action) return null_args("gvec_categorical_target");
   if (a->rows == 0) return GVEC_OK;
   ON_DEVICE(device, launch_categorical_target(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+}
+
+// ---- board symmetries ----
+int32_t gvec_obs_symmetry(int32_t device, void* hip_stream, const gvec_obs_symmetry_args* a) {
+  const char* fn = "gvec_obs_symmetry";
+  if (!a) return null_args(fn);
+  RET_IF(check_rows_and_board(fn, a));
+  if (a->num_sets < 0 || a->num_sets > GVEC_SYM_MAX_PLANE_SETS) {
+    set_err("%s: num_sets %d outside [0, %d]", fn, a->num_sets, GVEC_SYM_MAX_PLANE_SETS);
+    return GVEC_E_INVALID;
+  }
+  if (a->inverse != 0 && a->inverse != 1) {
+    set_err("%s: inverse %d is neither 0 nor 1", fn, a->inverse);
+    return GVEC_E_INVALID;
+  }
+  if (a->reserved != 0) {
+    set_err("%s: reserved %d must be 0", fn, a->reserved);
+    return GVEC_E_INVALID;
+  }
+  // what the launch reads and what it writes, as byte ranges (empty when rows == 0)
+  struct Range {
+    uintptr_t lo, hi;
+    const char* name;
+  };
+  Range ins[GVEC_SYM_MAX_PLANE_SETS + 4], outs[GVEC_SYM_MAX_PLANE_SETS + 4];
+  int n_in = 0, n_out = 0;
+  const uintptr_t rows = (uintptr_t)a->rows, HW = (uintptr_t)(a->width * a->height), A = 5u * HW;
+  auto range = [&](const void* p, uintptr_t row_bytes, uintptr_t stride_bytes, const char* name) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return Range{lo, rows ? lo + (rows - 1) * stride_bytes + row_bytes : lo, name};
+  };
+  static const char* const set_in[] = {"sets[0].in", "sets[1].in", "sets[2].in", "sets[3].in"};
+  static const char* const set_out[] = {"sets[0].out", "sets[1].out", "sets[2].out", "sets[3].out"};
+  for (int k = 0; k < a->num_sets; ++k) {
+    const gvec_sym_plane_set& s = a->sets[k];
+    if (s.planes < 1 || s.planes > 64) {
+      set_err("%s: sets[%d].planes %d outside [1, 64]", fn, k, s.planes);
+      return GVEC_E_INVALID;
+    }
+    const uintptr_t row = (uintptr_t)s.planes * HW;
+    if (s.in_row_stride < (int64_t)row) {
+      set_err("%s: sets[%d].in_row_stride %lld < planes * width * height = %lld", fn, k, (long long)s.in_row_stride, (long long)row);
+      return GVEC_E_INVALID;
+    }
+    if (!s.in || !s.out) return null_args(fn);
+    ins[n_in++] = range(s.in, row * sizeof(float), (uintptr_t)s.in_row_stride * sizeof(float), set_in[k]);
+    outs[n_out++] = range(s.out, row * sizeof(float), row * sizeof(float), set_out[k]);
+  }
+  if (!a->sym || !a->mask_in != !a->mask_out || !a->values_in != !a->values_out || !a->action_in != !a->action_out) return null_args(fn);
+  if (a->num_sets == 0 && !a->mask_in && !a->values_in && !a->action_in) {
+    set_err("%s: nothing to transform (no plane set, mask, values or action)", fn);
+    return GVEC_E_INVALID;
+  }
+  ins[n_in++] = range(a->sym, 1, 1, "sym");
+  if (a->mask_in) ins[n_in++] = range(a->mask_in, A, A, "mask_in"), outs[n_out++] = range(a->mask_out, A, A, "mask_out");
+  if (a->values_in) {
+    ins[n_in++] = range(a->values_in, A * sizeof(float), A * sizeof(float), "values_in");
+    outs[n_out++] = range(a->values_out, A * sizeof(float), A * sizeof(float), "values_out");
+  }
+  if (a->action_in) ins[n_in++] = range(a->action_in, 8, 8, "action_in"), outs[n_out++] = range(a->action_out, 8, 8, "action_out");
+  if (a->applied) outs[n_out++] = range(a->applied, 1, 1, "applied");
+  for (int o = 0; o < n_out; ++o)
+    for (int i = 0; i < n_in; ++i)
+      if (outs[o].lo < ins[i].hi && ins[i].lo < outs[o].hi) {
+        set_err("%s: output %s overlaps input %s (the transform is not in place)", fn, outs[o].name, ins[i].name);
+        return GVEC_E_INVALID;
+      }
+  if (a->rows == 0) return GVEC_OK;
+  ON_DEVICE(device, launch_obs_symmetry(*a, reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
 }  // extern "C"

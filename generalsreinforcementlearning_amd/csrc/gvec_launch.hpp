@@ -318,4 +318,7 @@ hipError_t launch_obs_valid_mask(const gvec_obs_valid_mask_args& a, hipStream_t 
 hipError_t launch_q_target(const gvec_q_target_args& a, hipStream_t s);
 hipError_t launch_categorical_target(const gvec_categorical_target_args& a, hipStream_t s);
 
+// board symmetries per row (gvec_symmetry.hip; generals_vec.h "board symmetries")
+hipError_t launch_obs_symmetry(const gvec_obs_symmetry_args& a, hipStream_t s);
+
 }  // namespace gvec

@@ -870,6 +870,58 @@ int32_t gvec_obs_valid_mask(int32_t device, void* hip_stream, const gvec_obs_val
 int32_t gvec_q_target(int32_t device, void* hip_stream, const gvec_q_target_args* args);
 int32_t gvec_categorical_target(int32_t device, void* hip_stream, const gvec_categorical_target_args* args);
 
+/* ---- board symmetries (D4), one per row: observations, masks, action-indexed values and actions -------
+ * The rules of the game do not know left from right, so a stored transition is worth up to eight.  Handle-free like the feature
+ * planes: DEVICE pointers on `device`, enqueued on hip_stream, nothing synchronises.  One launch moves every tensor of a row
+ * with that row's symmetry.  Tile t = y*W + x, A = 5*H*W, action 5*t + d with d = up (0,-1), right (1,0), down (0,1),
+ * left (-1,0), then 4 = the half move.
+ * The group.  sym in [0, 8): fx = sym & 1, fy = sym & 2, tr = sym & 4.  g maps a source tile (x, y): if fx, x = W-1-x; if fy,
+ *   y = H-1-y; then, if tr, x and y are swapped.  tr needs W == H: on another board only sym < 4 exists.  Direction vectors go
+ *   through the same three steps, which permutes d -> d' (4 -> 4 always):
+ *     sym 0 [0,1,2,3]  1 [0,3,2,1]  2 [2,1,0,3]  3 [2,3,0,1]  4 [3,2,1,0]  5 [3,0,1,2]  6 [1,2,3,0]  7 [1,0,3,2]
+ *   Every sym is its own inverse except 5 and 6, which are each other's.
+ * What a row's symmetry g does: a plane, out[g(t)] = in[t]; an action-indexed row (mask, values), out[5*g(t) + d'] =
+ *   in[5*t + d]; an action a in [0, A), 5*g(a / 5) + d'(a % 5).  An action outside [0, A) is copied unchanged (-1 is what
+ *   gvec_q_target returns for a row without a legal action).  Values are moved as bits: NaN payloads and -0.0 survive.
+ * The half move.  Action 5*t + 4 names no direction: GeneralsEnv plays the first of up, right, down, left whose target is on
+ *   the board (left when none is: a 1x1 board), d0(t).  That rule is not symmetric, so a half move from t is EXACT under g iff
+ *   d0(g(t)) == d'(d0(t)): the move played from g(t) is the image of the move played from t.  When action_in is given, a row
+ *   whose action is a half move in [0, A) that is not exact under its sym is transformed with the identity instead, every tensor
+ *   of the row.  Full moves, out-of-range actions and calls without action_in restrict nothing.
+ * sym uint8 [rows], required.  A value >= 8, or >= 4 where W != H, cannot be seen by the host: the row is transformed with the
+ *   identity.  applied uint8 [rows], optional: the symmetry the row was transformed with (0 for a half move that fell back and
+ *   for a sym out of range).
+ * inverse != 0 transforms with the inverse of each row's symmetry.  The half-move rule is evaluated as in the forward call all
+ *   the same - for sym itself, on action_in as given - so a call with inverse = 1, the same sym and the ORIGINAL action undoes
+ *   exactly what the forward call did to the planes, the mask and the values (applied is the same in both).  action_out of
+ *   such a call is the inverse image of the original action, which nobody needs; the forward call's action_out goes back
+ *   through a FORWARD call whose sym is the inverse of its applied (a half move that was exact one way is exact back).
+ * Plane sets: num_sets in [0, GVEC_SYM_MAX_PLANE_SETS]; set k reads in float32 [rows][planes][H*W], consecutive rows
+ *   in_row_stride floats apart, and writes out float32 [rows][planes][H*W], dense.  mask_in -> mask_out uint8 [rows][A];
+ *   values_in -> values_out float32 [rows][A]; action_in -> action_out int64 [rows].  Each pair is optional and goes together.
+ *   EVERY element of every output is written.  No output may overlap any input.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or sym NULL, one half of a pair NULL,
+ *   in or out of a set NULL, nothing to transform, num_sets outside [0, 4], planes outside [1, 64], in_row_stride <
+ *   planes*width*height, rows < 0 or rows >= 2^31, width or height outside [1, GVEC_MAX_DIM], inverse outside {0, 1},
+ *   reserved != 0, an output overlapping an input.  rows == 0 is a no-op that needs no device. */
+#define GVEC_SYM_MAX_PLANE_SETS 4
+typedef struct gvec_sym_plane_set {
+  const float* in; float* out;
+  int32_t planes;                                                                          /* 1 .. 64 */
+  int64_t in_row_stride;                                                                   /* floats, >= planes*width*height */
+} gvec_sym_plane_set;
+typedef struct gvec_obs_symmetry_args {
+  int64_t rows;
+  int32_t width, height, num_sets, inverse, reserved;
+  gvec_sym_plane_set sets[GVEC_SYM_MAX_PLANE_SETS];
+  const uint8_t* sym;
+  const uint8_t* mask_in; uint8_t* mask_out;                                               /* NULL: no mask */
+  const float* values_in; float* values_out;                                               /* NULL: no values */
+  const int64_t* action_in; int64_t* action_out;                                           /* NULL: no action, no half-move rule */
+  uint8_t* applied;                                                                        /* NULL: not wanted */
+} gvec_obs_symmetry_args;
+int32_t gvec_obs_symmetry(int32_t device, void* hip_stream, const gvec_obs_symmetry_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
