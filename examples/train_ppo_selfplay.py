@@ -20,8 +20,16 @@ five are recomputed from them where they are consumed, while acting and on every
 last saw of every tile, which the observation forgets the moment the tile is fogged again.  They are state, not a function of
 one observation, so the rollout buffer stores them per step (SelfPlayRolloutBuffer(memory=)).  With --features as well the
 features are computed from remembered_observation: the distance to the nearest enemy tile seen so far.
+
+--actor-lag K lets a frozen copy of the network act, refreshed from the learner every K iterations: the actor-learner
+pattern, in one process.  --vtrace replaces GAE by V-trace targets (SelfPlayRolloutBuffer.evaluate_rollout re-scores the
+stored rows with the learner in place, finish_vtrace runs gvec_traj_vtrace), recomputed before every epoch, so that neither
+the lag nor the gradient steps already taken on this rollout bias them; --rho-bar / --c-bar are its two truncation levels.
+The surrogate stays PPO's, on the ratio to the stored (behaviour) log-probs, with V-trace's pg as the advantage and vs as
+the value target.
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -72,6 +80,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--features", action="store_true", help="feed the five strategic feature planes next to the observation's nine")
     ap.add_argument("--memory", action="store_true", help="feed the four fog-of-war memory planes (what each tile last showed, and how long ago)")
+    ap.add_argument("--vtrace", action="store_true", help="V-trace targets from the learner's own log-probs and values, before every epoch")
+    ap.add_argument("--rho-bar", type=float, default=1.0, help="V-trace: truncation of the importance weight of the TD error")
+    ap.add_argument("--c-bar", type=float, default=1.0, help="V-trace: truncation of the trace coefficient")
+    ap.add_argument("--actor-lag", type=int, default=0, metavar="K",
+                    help="a frozen copy of the network acts, refreshed every K iterations (0: the learner itself acts)")
     a = ap.parse_args(argv)
 
     torch.manual_seed(a.seed)
@@ -97,18 +110,38 @@ def main(argv=None):
     buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda, memory=memory)
     head = MaskedCategoricalHead(dev)
     current = lambda: inputs(buf.obs.view(B * L, *obs_shape), buf.memory.view(B * L, NUM_MEMORY_PLANES, *obs_shape[1:]) if a.memory else None)
+    actor = copy.deepcopy(net).requires_grad_(False) if a.actor_lag > 0 else net
+    rho_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+
+    def passes(it):
+        """the iteration's minibatches; with --vtrace the targets are rebuilt from the learner as it stands before each epoch"""
+        if not a.vtrace:
+            yield from buf.minibatches(a.batch_size, epochs=a.epochs, seed=a.seed + it)
+            return
+        for epoch in range(a.epochs):
+            logp, value = buf.evaluate_rollout(lambda o, m: net(inputs(o, m)), head, chunk_rows=a.batch_size)
+            with torch.no_grad():
+                last = net(current())[1]
+            buf.finish_vtrace(last, logp, value=value, rho_bar=a.rho_bar, c_bar=a.c_bar)
+            if epoch == 0:
+                rho_stats.copy_(buf.stats)          # how far off-policy the rollout is before the first gradient step
+            yield from buf.minibatches(a.batch_size, epochs=1, seed=(a.seed + it) * a.epochs + epoch)
+
     buf.begin(*env.reset())
     out, draws, t0 = [], 0, time.perf_counter()
     for it in range(a.iterations):
+        if a.actor_lag > 0 and it % a.actor_lag == 0:
+            actor.load_state_dict(net.state_dict())
         with torch.no_grad():
             while not buf.full:
-                logits, value = net(current())
+                logits, value = actor(current())
                 draws += 1                          # one seed per step: a draw is keyed by (seed, row, action index)
                 actions, logp, _ = head.sample(logits.view(B, L, n_actions), buf.valid_actions_mask, seed=(a.seed << 32) + draws)
                 buf.step(actions, logp, value)
-            buf.finish(net(current())[1])
+            if not a.vtrace:
+                buf.finish(net(current())[1])
         sums = torch.zeros(5, device=dev)           # policy loss, value loss, entropy, clipped share, batches
-        for batch in buf.minibatches(a.batch_size, epochs=a.epochs, seed=a.seed + it):
+        for batch in passes(it):
             w = batch["weight"]
             n = w.sum().clamp_min(1.0)
             logits, value = net(inputs(batch["obs"], batch.get("memory")))
@@ -126,11 +159,12 @@ def main(argv=None):
             with torch.no_grad():
                 sums += torch.stack([pg, vl, ent, (((ratio - 1).abs() > a.clip).float() * w).sum() / n, torch.ones((), device=dev)])
         valid = float(buf.stats[0])                 # the iteration's one host read (with the sums below)
+        mean_rho = float(rho_stats[3] / rho_stats[0].clamp_min(1.0)) if a.vtrace else None
         buf.next_rollout()
         s = (sums[:4] / sums[4].clamp_min(1.0)).tolist()
         row = {"iteration": it, "policy_loss": s[0], "value_loss": s[1], "entropy": s[2], "clip_fraction": s[3],
                "valid_rows": valid / (a.horizon * B * L), "env_steps": (it + 1) * a.horizon * B,
-               "seconds": time.perf_counter() - t0}
+               "mean_rho": mean_rho, "seconds": time.perf_counter() - t0}
         print(json.dumps(row))
         out.append(row)
     moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), start))

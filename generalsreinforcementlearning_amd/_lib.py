@@ -61,6 +61,13 @@ class TrajGaeArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("reward", "value", "flags", "adv", "ret", "stats", "scratch")])
 
 
+class TrajVtraceArgs(C.Structure):
+    """gvec_traj_vtrace_args (include/generals_vec.h): every pointer is device memory; rho_out may be None."""
+    _fields_ = ([("T", C.c_int64), ("N", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double), ("rho_bar", C.c_double), ("c_bar", C.c_double)]
+                + [(n, C.c_void_p) for n in ("reward", "value", "flags", "logp_behaviour", "logp_target", "vs", "pg", "rho_out", "stats",
+                                             "scratch")])
+
+
 class TrajCompactArgs(C.Structure):
     _fields_ = [("T", C.c_int64), ("N", C.c_int64)] + [(n, C.c_void_p) for n in ("flags", "idx", "count", "scratch")]
 
@@ -200,6 +207,7 @@ SYMBOLS = {
     "gvec_traj_scratch_bytes": (_u64, [C.c_int64, C.c_int64]),
     "gvec_traj_record": (_i32, [_i32, _vp, C.POINTER(TrajRecordArgs)]),
     "gvec_traj_gae": (_i32, [_i32, _vp, C.POINTER(TrajGaeArgs)]),
+    "gvec_traj_vtrace": (_i32, [_i32, _vp, C.POINTER(TrajVtraceArgs)]),
     "gvec_traj_compact": (_i32, [_i32, _vp, C.POINTER(TrajCompactArgs)]),
     "gvec_traj_gather": (_i32, [_i32, _vp, C.POINTER(TrajGatherArgs)]),
     "gvec_policy_sample": (_i32, [_i32, _vp, C.POINTER(PolicySampleArgs)]),

@@ -209,6 +209,23 @@ int32_t gvec_traj_gae(int32_t device, void* hip_stream, const gvec_traj_gae_args
   ON_DEVICE(device, launch_traj_gae(*a, reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
+int32_t gvec_traj_vtrace(int32_t device, void* hip_stream, const gvec_traj_vtrace_args* a) {
+  if (!a) return null_args("gvec_traj_vtrace");
+  RET_IF(traj_shape("gvec_traj_vtrace", a->T, a->N));
+  if (!(a->gamma >= 0.0 && a->gamma <= 1.0) || !(a->lambda >= 0.0 && a->lambda <= 1.0)) {
+    set_err("gvec_traj_vtrace: gamma %g or lambda %g outside [0, 1]", a->gamma, a->lambda);
+    return GVEC_E_INVALID;
+  }
+  if (!(a->rho_bar > 0.0) || !(a->c_bar > 0.0)) {
+    set_err("gvec_traj_vtrace: rho_bar %g or c_bar %g not > 0 (+inf means no clipping)", a->rho_bar, a->c_bar);
+    return GVEC_E_INVALID;
+  }
+  if (!a->reward || !a->value || !a->flags || !a->logp_behaviour || !a->logp_target || !a->vs || !a->pg || !a->stats || !a->scratch)
+    return null_args("gvec_traj_vtrace");          // rho_out may be NULL
+  RET_IF(check_scratch("gvec_traj_vtrace", a->scratch));
+  ON_DEVICE(device, launch_traj_vtrace(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+}
+
 int32_t gvec_traj_compact(int32_t device, void* hip_stream, const gvec_traj_compact_args* a) {
   if (!a) return null_args("gvec_traj_compact");
   RET_IF(traj_shape("gvec_traj_compact", a->T, a->N));

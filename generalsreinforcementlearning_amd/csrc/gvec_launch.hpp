@@ -299,6 +299,7 @@ hipError_t launch_nstep_gather(const gvec_nstep_gather_args& a, hipStream_t s);
 size_t traj_scratch_bytes(long long T, long long N);
 hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s);
 hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s);
+hipError_t launch_traj_vtrace(const gvec_traj_vtrace_args& a, hipStream_t s);
 hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s);
 hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s);
 

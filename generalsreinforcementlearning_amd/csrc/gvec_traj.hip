@@ -1,5 +1,5 @@
-// gvec_traj.hip — on-policy self-play rollouts in HBM: the per-step record, generalized advantage estimation, the compaction
-// of the valid rows and the minibatch gather (gvec_traj_* in generals_vec.h).
+// gvec_traj.hip — self-play rollouts in HBM: the per-step record, generalized advantage estimation, V-trace targets, the
+// compaction of the valid rows and the minibatch gather (gvec_traj_* in generals_vec.h).
 //
 // A rollout is T rows of N = B * L streams, learner-minor as gvec_gym_step_players emits them; row t, stream n sits at
 // position p = t * N + n of every store.  flags[p] carries the episode protocol (GVEC_TRAJ_VALID / _TERMINAL / _CUT), so the
@@ -12,6 +12,7 @@ namespace gvec {
 namespace {
 
 constexpr int GAE_ROWS = 32;           // rows a lane has in flight: the loads do not depend on the recurrence
+constexpr int VTRACE_ROWS = 8;         // the same for V-trace, whose rows cost eight registers and an exp each: DESIGN.md §4.17
 constexpr int COMPACT_BLOCK = 1024;    // positions per workgroup of the compaction (256 threads, four each)
 
 // ---- record: one thread per stream ----
@@ -94,29 +95,112 @@ __global__ __launch_bounds__(64) void traj_gae_kernel(gvec_traj_gae_args A) {
     part[2] = s2;
   }
 }
-// second stage, one workgroup: thread i adds partials i, i + 256, ... in that order, then a fixed tree over the 256 threads
+// second stage, one workgroup: thread i adds the K partials of groups i, i + 256, ... in that order, then a fixed tree over
+// the 256 threads; the slots of stats[4] past K are zero
+template <int K>
 __global__ __launch_bounds__(256) void traj_stats_kernel(const double* part, long long groups, double* stats) {
-  __shared__ double sh[3][256];
+  __shared__ double sh[K][256];
   const int tid = (int)threadIdx.x;
-  double c = 0.0, s1 = 0.0, s2 = 0.0;
+  double s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = 0.0;
   for (long long gi = tid; gi < groups; gi += 256) {
-    c += part[gi * 3];
-    s1 += part[gi * 3 + 1];
-    s2 += part[gi * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] += part[gi * K + k];
   }
-  sh[0][tid] = c;
-  sh[1][tid] = s1;
-  sh[2][tid] = s2;
+#pragma unroll
+  for (int k = 0; k < K; ++k) sh[k][tid] = s[k];
   __syncthreads();
   for (int off = 128; off >= 1; off >>= 1) {
     if (tid < off) {
-      sh[0][tid] += sh[0][tid + off];
-      sh[1][tid] += sh[1][tid + off];
-      sh[2][tid] += sh[2][tid + off];
+#pragma unroll
+      for (int k = 0; k < K; ++k) sh[k][tid] += sh[k][tid + off];
     }
     __syncthreads();
   }
-  if (tid < 4) stats[tid] = tid < 3 ? sh[tid][0] : 0.0;
+  if (tid < 4) stats[tid] = tid < K ? sh[tid < K ? tid : 0][0] : 0.0;
+}
+
+// ---- V-trace: the same walk with two more loads per row.  exp and the two min depend on no other row: they are formed
+// between the loads and the recurrence, and only delta -> acc -> vs and pg are on the serial chain ----
+__global__ __launch_bounds__(64) void traj_vtrace_kernel(gvec_traj_vtrace_args A) {
+  const long long N = A.N, T = A.T;
+  const long long n0 = (long long)blockIdx.x * 64 + lane_id();
+  const bool act = n0 < N;
+  const long long n = act ? n0 : N - 1;             // the tail lanes of the last wavefront read a real stream and store nothing
+  const double* __restrict__ reward = A.reward;
+  const float* __restrict__ value = A.value;
+  const uint8_t* __restrict__ flags = A.flags;
+  const float* __restrict__ logp_b = A.logp_behaviour;
+  const float* __restrict__ logp_t = A.logp_target;
+  float* __restrict__ vs = A.vs;
+  float* __restrict__ pg = A.pg;
+  float* __restrict__ rho_out = A.rho_out;
+  const double g = A.gamma, gl = A.gamma * A.lambda, rho_bar = A.rho_bar, c_bar = A.c_bar;
+  double acc = 0.0, next_v = (double)value[T * N + n], next_vs = next_v;
+  double cnt = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (long long hi = T; hi > 0; hi -= VTRACE_ROWS) {  // rows hi-1 .. hi-VTRACE_ROWS: loads, then the ratios, then the recurrence
+    double r[VTRACE_ROWS], rho[VTRACE_ROWS], glc[VTRACE_ROWS];
+    float v[VTRACE_ROWS], lt[VTRACE_ROWS], lb[VTRACE_ROWS];
+    uint32_t f[VTRACE_ROWS];
+#pragma unroll
+    for (int i = 0; i < VTRACE_ROWS; ++i) {
+      const long long t = hi - 1 - i, o = (t < 0 ? 0 : t) * N + n;
+      r[i] = reward[o];
+      v[i] = value[o];
+      f[i] = flags[o];
+      lt[i] = logp_t[o];
+      lb[i] = logp_b[o];
+    }
+#pragma unroll
+    for (int i = 0; i < VTRACE_ROWS; ++i) {
+      const double w = exp((double)lt[i] - (double)lb[i]);
+      rho[i] = fmin(rho_bar, w);
+      glc[i] = gl * fmin(c_bar, w);
+    }
+#pragma unroll
+    for (int i = 0; i < VTRACE_ROWS; ++i) {
+      const long long t = hi - 1 - i;
+      if (t < 0) continue;                          // the same in every lane
+      const double vt = (double)v[i];
+      const bool valid = f[i] & GVEC_TRAJ_VALID, term = f[i] & GVEC_TRAJ_TERMINAL, cut = f[i] & GVEC_TRAJ_CUT;
+      double a = 0.0, p = 0.0, ro = 0.0;
+      if (valid) {
+        const double nv = term ? 0.0 : next_v, nvs = term ? 0.0 : (cut ? next_v : next_vs);
+        const double delta = rho[i] * ((r[i] + g * nv) - vt);
+        a = delta + glc[i] * (cut ? 0.0 : acc);
+        p = rho[i] * ((r[i] + g * nvs) - vt);
+        ro = rho[i];
+      }
+      acc = a;                                      // an invalid row clears it
+      next_vs = vt + a;
+      next_v = vt;
+      const float p32 = (float)p, ro32 = (float)ro;
+      if (act) {
+        vs[t * N + n] = (float)next_vs;
+        pg[t * N + n] = p32;
+        if (rho_out) rho_out[t * N + n] = ro32;
+        if (valid) {                                // the statistics describe pg and rho as stored
+          const double x = (double)p32;
+          cnt += 1.0;
+          s1 += x;
+          s2 += x * x;
+          s3 += (double)ro32;
+        }
+      }
+    }
+  }
+  cnt = wave_sum(cnt);                              // fixed butterflies: the same bits on every run
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  s3 = wave_sum(s3);
+  if (lane_id() == 0) {
+    double* part = static_cast<double*>(A.scratch) + (size_t)blockIdx.x * 4;
+    part[0] = cnt;
+    part[1] = s1;
+    part[2] = s2;
+    part[3] = s3;
+  }
 }
 
 // ---- compaction: the ascending positions of the VALID rows ----
@@ -219,7 +303,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void traj_gather_kernel(gvec_
 }  // namespace
 
 size_t traj_scratch_bytes(long long T, long long N) {
-  const size_t gae = (size_t)((N + 63) / 64) * 3 * 8;
+  const size_t gae = (size_t)((N + 63) / 64) * 4 * 8;    // V-trace's four partials per wavefront; GAE uses three
   const size_t compact = (size_t)compact_groups(T * N) * 2 * 8;
   return ((gae > compact ? gae : compact) + 255) / 256 * 256;
 }
@@ -229,7 +313,13 @@ hipError_t launch_traj_record(const gvec_traj_record_args& a, hipStream_t s) {
 hipError_t launch_traj_gae(const gvec_traj_gae_args& a, hipStream_t s) {
   const long long groups = (a.N + 63) / 64;
   hipLaunchKernelGGL(traj_gae_kernel, dim3((unsigned)groups), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(traj_stats_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(a.scratch), groups, a.stats);
+  hipLaunchKernelGGL(traj_stats_kernel<3>, dim3(1), dim3(256), 0, s, static_cast<const double*>(a.scratch), groups, a.stats);
+  return hipGetLastError();
+}
+hipError_t launch_traj_vtrace(const gvec_traj_vtrace_args& a, hipStream_t s) {
+  const long long groups = (a.N + 63) / 64;
+  hipLaunchKernelGGL(traj_vtrace_kernel, dim3((unsigned)groups), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(traj_stats_kernel<4>, dim3(1), dim3(256), 0, s, static_cast<const double*>(a.scratch), groups, a.stats);
   return hipGetLastError();
 }
 hipError_t launch_traj_compact(const gvec_traj_compact_args& a, hipStream_t s) {

@@ -4,7 +4,8 @@ A rollout is `horizon` = T steps of N = num_envs * num_learners streams ([B][L],
 buffer owns every store in HBM: observations and masks of T + 1 slots (the env's step launch writes slot t + 1 directly: no
 second copy of the 8 to 14 KB rows), action / log-prob / value / reward / flags per row, and after `finish` advantages and
 returns.  Four HIP entry points do the work (include/generals_vec.h): gvec_traj_record (one launch
-per step), gvec_traj_gae, gvec_traj_compact, gvec_traj_gather.
+per step), gvec_traj_gae, gvec_traj_compact, gvec_traj_gather.  A fifth, gvec_traj_vtrace, replaces
+gvec_traj_gae where the network that learns is no longer the one that acted: `finish_vtrace`, fed by `evaluate_rollout`.
 
 The episode protocol, which the flags of a row encode (TRAJ_VALID / TRAJ_TERMINAL / TRAJ_CUT):
   - a step that re-dealt its env (info["reset"]) is no transition: the action was ignored - its rows are invalid;
@@ -24,6 +25,15 @@ Precondition: every board holds max_players players (GeneralsSelfPlayVecEnv alwa
             ...                      # batch["weight"] is 0 for the invalid rows
         buf.next_rollout()
 
+Off-policy (a lagging actor, or every epoch after the first gradient step): V-trace targets instead of GAE's, from the
+learner's own log-probs and values of the stored rows, re-evaluated in place:
+
+        for epoch in range(4):
+            logp, value = buf.evaluate_rollout(lambda obs, memory: net(obs), head)      # net: obs -> (logits, value)
+            buf.finish_vtrace(net(buf.obs.flatten(0, 1))[1], logp, value=value)
+            for batch in buf.minibatches(4096):
+                ...                  # batch["rho"] is the clipped importance weight of the row
+
 Nothing here synchronises with the host, except minibatches(compact=True): one 8-byte read per rollout.
 
 memory=ObservationMemory((num_envs, num_learners), H, W) carries the fog-of-war memory planes (memory.py, DESIGN.md section
@@ -32,7 +42,7 @@ current slot's view and every batch has a "memory" entry.  Without it nothing is
 """
 import ctypes as C
 
-from ._lib import TRAJ_VALID, TrajCompactArgs, TrajGaeArgs, TrajGatherArgs, TrajRecordArgs, check, load
+from ._lib import TRAJ_VALID, TrajCompactArgs, TrajGaeArgs, TrajGatherArgs, TrajRecordArgs, TrajVtraceArgs, check, load
 
 
 class SelfPlayRolloutBuffer:
@@ -77,6 +87,8 @@ class SelfPlayRolloutBuffer:
         self._rec_ref = C.byref(self._rec)
         self._memory = memory
         self.mem_store = None if memory is None else z((T + 1, N, 4, nb), t.float32)
+        self._rho = self._vt_value = None                               # V-trace's stores: allocated by the first finish_vtrace
+        self._vtrace = False
 
     # ---- collection ---------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -113,7 +125,7 @@ class SelfPlayRolloutBuffer:
         self._restart()
 
     def _restart(self):
-        self._step, self._finished, self._valid_count = 0, False, None
+        self._step, self._finished, self._valid_count, self._vtrace = 0, False, None, False
 
     def _as(self, x, dtype):
         t = self._t
@@ -154,7 +166,74 @@ class SelfPlayRolloutBuffer:
                         flags=self.flags.data_ptr(), adv=self._adv.data_ptr(), ret=self._ret.data_ptr(), stats=self.stats.data_ptr(),
                         scratch=self._scratch.data_ptr())
         check(self._L.gvec_traj_gae(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_gae")
-        self._finished = True
+        self._finished, self._vtrace = True, False
+
+    def finish_vtrace(self, last_value, target_logp, value=None, rho_bar=1.0, c_bar=1.0):
+        """V-trace targets (gvec_traj_vtrace) in place of GAE's, for a rollout whose actor is not the network being trained.
+        target_logp float32 [T, B, L] (or [T, N]): the learner's log-prob of every stored action, as `evaluate_rollout`
+        returns it; the stored `logp` is the behaviour's.  value [T, B, L], optional: the learner's fresh values of slots
+        0 .. T-1, which with last_value go into a store of the buffer's own - the recorded `self.value` stays as it is and
+        batch["value"] still returns it.  Without it the recorded values are used, as finish() uses them.
+        Afterwards advantages is pg, returns is vs, stats is {valid rows, sum pg, sum pg^2, sum rho}, `rho` [T, B, L] holds
+        min(rho_bar, pi / mu) (0 on invalid rows) and every batch has a "rho" entry.  It may be called again on the same
+        rollout (re-targeting between epochs), and finish() after it restores the GAE outputs.  No host sync."""
+        if not self.full:
+            raise RuntimeError(f"finish_vtrace() after {self._step} of {self.horizon} steps")
+        t, T, N = self._t, self.horizon, self.num_streams
+        if not (float(rho_bar) > 0.0 and float(c_bar) > 0.0):
+            raise ValueError(f"rho_bar and c_bar must be > 0: {rho_bar}, {c_bar}")
+
+        def rows(x, name):
+            if not isinstance(x, t.Tensor) or x.numel() != T * N:
+                raise ValueError(f"{name} must be a tensor of {T} x {self.num_envs} x {self.num_learners} elements")
+            if not (x.is_cuda and x.dtype == t.float32 and x.is_contiguous()):
+                x = x.to(device=self._dev, dtype=t.float32).contiguous()
+            return x.view(T, N)
+
+        target_logp = rows(target_logp, "target_logp")
+        last_value = self._as(last_value, t.float32).view(-1)
+        if value is None:
+            values = self.value
+        else:
+            if self._vt_value is None:
+                self._vt_value = t.zeros((T + 1, N), dtype=t.float32, device=self._dev)
+            values = self._vt_value
+            values[:T].copy_(rows(value, "value"))
+        values[T].copy_(last_value)
+        if self._rho is None:
+            self._rho = t.zeros((T, N), dtype=t.float32, device=self._dev)
+        a = TrajVtraceArgs(T=T, N=N, gamma=self.gamma, lam=self.gae_lambda, rho_bar=float(rho_bar), c_bar=float(c_bar),
+                           reward=self.reward.data_ptr(), value=values.data_ptr(), flags=self.flags.data_ptr(),
+                           logp_behaviour=self.logp.data_ptr(), logp_target=target_logp.data_ptr(), vs=self._ret.data_ptr(),
+                           pg=self._adv.data_ptr(), rho_out=self._rho.data_ptr(), stats=self.stats.data_ptr(),
+                           scratch=self._scratch.data_ptr())
+        check(self._L.gvec_traj_vtrace(self._dev.index, self._stream(), C.byref(a)), "gvec_traj_vtrace")
+        self._finished = self._vtrace = True
+
+    def evaluate_rollout(self, fn, head, chunk_rows=None):
+        """The learner's view of the stored rollout, without gathering it: fn(obs [M, 9, H, W], memory [M, 4, H, W] or None)
+        -> (logits [M, A], value [M]) is called on contiguous chunks of rows 0 .. T * N of the stores (views: no gather, no
+        copy; chunk_rows=None takes them all at once), under torch.no_grad(), and head.evaluate scores the stored actions
+        under the stored masks.  Returns (logp [T, B, L], value [T, B, L]), what finish_vtrace takes."""
+        t, env = self._t, self.env
+        total = self.horizon * self.num_streams
+        chunk = total if chunk_rows is None else int(chunk_rows)
+        if chunk < 1:
+            raise ValueError(f"chunk_rows must be >= 1: {chunk_rows}")
+        obs = self.obs_store.view(-1, 9, env.board_height, env.board_width)
+        mask = self.mask_store.view(-1, self.mask_bytes).view(t.bool)
+        mem = None if self.mem_store is None else self.mem_store.view(-1, 4, env.board_height, env.board_width)
+        action = self.action.view(-1)
+        logp, value = t.empty(total, dtype=t.float32, device=self._dev), t.empty(total, dtype=t.float32, device=self._dev)
+        with t.no_grad():
+            for lo in range(0, total, chunk):
+                hi = min(lo + chunk, total)
+                logits, v = fn(obs[lo:hi], None if mem is None else mem[lo:hi])
+                lp, _ = head.evaluate(logits, mask[lo:hi], action[lo:hi])
+                logp[lo:hi].copy_(lp.view(-1))
+                value[lo:hi].copy_(v.reshape(-1))
+        shape = (self.horizon, self.num_envs, self.num_learners)
+        return logp.view(shape), value.view(shape)
 
     def _done(self):
         if not self._finished:
@@ -168,6 +247,13 @@ class SelfPlayRolloutBuffer:
     @property
     def returns(self):
         return self._ret.view(self._done())
+
+    @property
+    def rho(self):
+        """[T, B, L]: the clipped importance weights of the last finish_vtrace (0 on invalid rows)."""
+        if not self._vtrace:
+            raise RuntimeError("rho exists after finish_vtrace()")
+        return self._rho.view(self._done())
 
     @property
     def valid(self):
@@ -191,7 +277,8 @@ class SelfPlayRolloutBuffer:
         valid_actions_mask bool [M, 5 * H * W], action, logp, value, returns, advantages (normalised over the rollout's valid
         rows when `normalize`) and weight (1 for a valid row, 0 otherwise) [M].  The tensors are reused by the next gather of
         the same M.  With memory=: also memory [M, 4, H, W], the planes stored at the same positions (a position outside the
-        rollout, which `rejected` counts and whose weight is 0, gets those of the nearest row)."""
+        rollout, which `rejected` counts and whose weight is 0, gets those of the nearest row).  After finish_vtrace: also rho [M],
+        fetched the same way."""
         self._done()
         m = int(pos.numel())
         o = self._outputs(m)
@@ -209,6 +296,11 @@ class SelfPlayRolloutBuffer:
             rows = self.mem_store.view(-1, self.mem_floats)[:self.horizon * self.num_streams]
             self._t.index_select(rows, 0, pos.clamp(0, rows.shape[0] - 1), out=o["memory"].view(m, self.mem_floats))
             batch["memory"] = o["memory"]
+        if self._vtrace:
+            if "rho" not in o:
+                o["rho"] = self._t.empty(m, dtype=self._t.float32, device=self._dev)
+            self._t.index_select(self._rho.view(-1), 0, pos.clamp(0, self._rho.numel() - 1), out=o["rho"])
+            batch["rho"] = o["rho"]
         return batch
 
     def valid_positions(self):

@@ -642,6 +642,29 @@ int32_t gvec_nstep_gather(int32_t device, void* hip_stream, const gvec_nstep_gat
  *   on the final observation the truncating step returned - the bootstrap wanted.  adv / ret float32[T][N], rounded once.
  *   stats double[4] = {valid rows, sum of adv, sum of adv^2, 0} over the valid rows, of adv AS STORED (float32), by a
  *   fixed-order two-stage reduction without atomics: the same input gives the same bits.  Two launches.
+ * gvec_traj_vtrace: V-trace targets (Espeholt et al., IMPALA, 2018) for a rollout whose acting policy mu is not the policy
+ *   pi that is trained: the same backward recurrence over the same flags, with one more input per row, the learner's
+ *   log-prob of the stored action.  Per stream, backwards over t = T-1 .. 0, in float64; V[t] = (double)value[t] and
+ *   value[T] is the caller's bootstrap:
+ *     w   = exp((double)logp_target[t] - (double)logp_behaviour[t])           the two float32 log-probs
+ *     rho = min(rho_bar, w);   c = min(c_bar, w);   gl = gamma * lambda, formed once
+ *     valid row    nv    = TERMINAL ? 0 : V[t+1]
+ *                  nvs   = TERMINAL ? 0 : (CUT ? V[t+1] : vs_next)       vs_next: the UNROUNDED vs of row t+1; V[T] for t = T-1
+ *                  delta = rho * ((reward + gamma * nv) - V[t])
+ *                  acc   = delta + (gl * c) * (CUT ? 0 : acc_next)
+ *                  vs[t] = V[t] + acc
+ *                  pg[t] = rho * ((reward + gamma * nvs) - V[t])
+ *                  rho_out[t] = rho
+ *     invalid row  acc = 0, vs[t] = V[t], pg[t] = 0, rho_out[t] = 0
+ *     then acc_next = acc, vs_next = vs[t]
+ *   A CUT row bootstraps pg from V[t+1], as delta does: vs of row t+1 carries the corrections of the rows after the cut,
+ *   which are no part of this episode (after a truncation row t+1 is the re-deal row and the two agree; flags from
+ *   elsewhere may put a valid row there).  With logp_target bitwise
+ *   equal to logp_behaviour and both bars >= 1, vs is gvec_traj_gae's ret exactly (before the rounding), and with lambda = 1
+ *   as well pg is its adv up to rounding.  vs / pg / rho_out float32[T][N], each rounded once; rho_out may be NULL.
+ *   stats double[4] = {valid rows, sum of pg, sum of pg^2, sum of rho_out} over the valid rows of the values AS STORED, by
+ *   the same fixed-order two-stage reduction: slots 0-2 mean what gvec_traj_gather reads, which normalises pg unchanged.
+ *   rho_bar / c_bar = +inf: no clipping.  Two launches.
  * gvec_traj_compact: idx int64[T*N] takes the ascending positions p = t*N + n of the VALID rows, *count their number
  *   (entries of idx beyond it are left alone).  Three launches.
  * gvec_traj_gather: the minibatch of M positions pos[i] in [0, T*N): out_obs[i] = the obs_floats floats of row pos[i] of
@@ -651,10 +674,10 @@ int32_t gvec_nstep_gather(int32_t device, void* hip_stream, const gvec_nstep_gat
  *   (both 0 when stats[0] == 0); out_weight float32 = VALID ? 1 : 0.  A position outside the range gives a zeroed row with
  *   weight 0 and adds one to *rejected (checked on the device).  Rows need only 4-byte (masks: 1-byte) alignment.  One launch,
  *   one to eight wavefronts per row.
- * scratch (gae, compact): gvec_traj_scratch_bytes(T, N) bytes, 16-byte aligned, contents of no interest to the caller.
+ * scratch (gae, vtrace, compact): gvec_traj_scratch_bytes(T, N) bytes, 16-byte aligned, contents of no interest to the caller.
  * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL,
  *   T < 1, N < 1 (num_envs < 1, num_learners < 1), t outside [0, T), M < 0, gamma or lambda outside [0, 1] (NaN included),
- *   obs_floats < 1, mask_bytes < 0.  M == 0 is a no-op that needs no device. */
+ *   rho_bar or c_bar not > 0 (NaN included), obs_floats < 1, mask_bytes < 0.  M == 0 is a no-op that needs no device. */
 #define GVEC_TRAJ_VALID    1
 #define GVEC_TRAJ_TERMINAL 2
 #define GVEC_TRAJ_CUT      4
@@ -675,6 +698,16 @@ typedef struct gvec_traj_gae_args {
   double* stats;
   void* scratch;
 } gvec_traj_gae_args;
+typedef struct gvec_traj_vtrace_args {
+  int64_t T, N;
+  double gamma, lambda, rho_bar, c_bar;
+  const double* reward; const float* value; const uint8_t* flags;
+  const float* logp_behaviour; const float* logp_target;                                   /* [T][N] */
+  float* vs; float* pg;
+  float* rho_out;                                                                          /* NULL: not stored */
+  double* stats;
+  void* scratch;
+} gvec_traj_vtrace_args;
 typedef struct gvec_traj_compact_args {
   int64_t T, N;
   const uint8_t* flags;
@@ -695,6 +728,7 @@ typedef struct gvec_traj_gather_args {
 uint64_t gvec_traj_scratch_bytes(int64_t T, int64_t N);
 int32_t gvec_traj_record(int32_t device, void* hip_stream, const gvec_traj_record_args* args);
 int32_t gvec_traj_gae(int32_t device, void* hip_stream, const gvec_traj_gae_args* args);
+int32_t gvec_traj_vtrace(int32_t device, void* hip_stream, const gvec_traj_vtrace_args* args);
 int32_t gvec_traj_compact(int32_t device, void* hip_stream, const gvec_traj_compact_args* args);
 int32_t gvec_traj_gather(int32_t device, void* hip_stream, const gvec_traj_gather_args* args);
 
