@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Which checkpoint plays better: entrants seated at on-device self-play boards, finished games tallied by one HIP launch
+per step (gvec_arena_update), and ratings on the Elo scale fitted to who outlasted whom.
+
+    python examples/train_ppo_selfplay.py --iterations 50 --save a.pt
+    python examples/train_ppo_selfplay.py --iterations 200 --save b.pt
+    python examples/evaluate_arena.py a.pt b.pt --random --episodes 4
+
+Each positional argument is a checkpoint written by train_ppo_selfplay.py --save; every --random adds an entrant that plays
+uniformly over its legal moves.  Entrants are seated so that each sits in every column (player seat) equally often
+(arena.balanced_seating), every env contributes exactly --episodes finished games, and nothing synchronises with the host
+between polls.  A multi-player game's pairwise results are treated as independent games by the fit: the ratings rank, their
+error bars are not calibrated.  An example, not part of the measured hot path.
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from generalsreinforcementlearning_amd.arena import Arena, random_policy, torch_policy
+from generalsreinforcementlearning_amd.features import strategic_features
+from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
+
+
+def _trainer():
+    """examples/train_ppo_selfplay.py as a module: the checkpoints' network class lives there"""
+    spec = importlib.util.spec_from_file_location("train_ppo_selfplay", os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_ppo_selfplay.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+class _WithFeatures(torch.nn.Module):
+    """a --features checkpoint's input: the observation's nine planes and the five strategic planes computed from them"""
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+
+    def forward(self, obs):
+        return self.net(torch.cat([obs, strategic_features(obs)], dim=1))
+
+
+def load_entrant(path, board, dev, greedy, seed):
+    ck = torch.load(path, map_location=dev)
+    if ck["board"] != board:
+        raise SystemExit(f"{path} was trained on a {ck['board']}x{ck['board']} board, the arena plays {board}x{board}")
+    if ck["memory"]:
+        raise SystemExit(f"{path} was trained with --memory: its input carries state from step to step, which an arena entrant "
+                         "(a function of the observation) cannot hold")
+    net = _trainer().ActorCritic((ck["channels"], board, board), board * board * 5).to(dev)
+    net.load_state_dict(ck["model"])
+    net.eval()
+    return torch_policy(_WithFeatures(net) if ck["features"] else net, greedy=greedy, seed=seed)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("checkpoints", nargs="*", help="files written by train_ppo_selfplay.py --save")
+    ap.add_argument("--random", action="count", default=0, help="add an entrant that plays uniformly over its legal moves (repeatable)")
+    ap.add_argument("--num-envs", type=int, default=1024)
+    ap.add_argument("--board", type=int, default=15)
+    ap.add_argument("--players", type=int, default=2)
+    ap.add_argument("--max-turns", type=int, default=500)
+    ap.add_argument("--episodes", type=int, default=2, help="finished games every env contributes")
+    ap.add_argument("--poll-every", type=int, default=32)
+    ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--greedy", action="store_true", help="checkpoints play their legal argmax instead of sampling")
+    ap.add_argument("--seed", type=int, default=42)
+    a = ap.parse_args(argv)
+
+    dev = torch.device("cuda", 0)
+    names = [os.path.basename(p) for p in a.checkpoints] + [f"random-{k}" for k in range(a.random)]
+    if not names:
+        raise SystemExit("nothing to evaluate: give checkpoints and / or --random")
+    entrants = [load_entrant(p, a.board, dev, a.greedy, a.seed + k) for k, p in enumerate(a.checkpoints)]
+    entrants += [random_policy(seed=a.seed + 1000 + k) for k in range(a.random)]
+    env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
+                                 seed=a.seed, device_outputs=True)
+    arena = Arena(env, entrants, names=names)
+    steps = arena.run(episodes_per_env=a.episodes, poll_every=a.poll_every, max_steps=a.max_steps)
+    res = arena.results()
+    ratings = res.ratings()
+    print(res.table())
+    out = {"names": names, "steps": steps, "games": res.totals["games"], "ratings": ratings.tolist(), "score": res.score.tolist(),
+           "pair_games": res.games.tolist(), "win_rate": res.entrants["win_rate"].tolist(),
+           "elimination_rate": res.entrants["elimination_rate"].tolist(), "mean_length": res.entrants["mean_length"].tolist(),
+           "mean_return": res.entrants["mean_return"].tolist(), "games_per_env": res.totals["per_env"]["games"].tolist()}
+    print(json.dumps({k: out[k] for k in ("names", "steps", "games", "ratings")}))
+    env.close()
+    return out
+
+
+if __name__ == "__main__":
+    main()

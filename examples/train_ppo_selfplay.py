@@ -27,6 +27,12 @@ stored rows with the learner in place, finish_vtrace runs gvec_traj_vtrace), rec
 the lag nor the gradient steps already taken on this rollout bias them; --rho-bar / --c-bar are its two truncation levels.
 The surrogate stays PPO's, on the ratio to the stored (behaviour) log-probs, with V-trace's pg as the advantage and vs as
 the value target.
+
+--arena-every K --arena-episodes k rates the learner as it goes: every K iterations the current network plays the frozen
+snapshots taken K, 2K, ... iterations ago (at most four are kept) in a match arena (arena.Arena: its own small batch of
+boards, k finished games per board, every entrant in every seat equally often), the row of that iteration gains its rating
+with the oldest snapshot anchored at 1500, and the current network joins the snapshots.  --save PATH writes the final network
+where examples/evaluate_arena.py reads it.
 """
 import argparse
 import copy
@@ -39,6 +45,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 
+from generalsreinforcementlearning_amd.arena import Arena, torch_policy
 from generalsreinforcementlearning_amd.features import NUM_STRATEGIC_FEATURES, strategic_features
 from generalsreinforcementlearning_amd.memory import NUM_MEMORY_PLANES, ObservationMemory, remembered_observation
 from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead
@@ -85,7 +92,14 @@ def main(argv=None):
     ap.add_argument("--c-bar", type=float, default=1.0, help="V-trace: truncation of the trace coefficient")
     ap.add_argument("--actor-lag", type=int, default=0, metavar="K",
                     help="a frozen copy of the network acts, refreshed every K iterations (0: the learner itself acts)")
+    ap.add_argument("--arena-every", type=int, default=0, metavar="K",
+                    help="every K iterations, rate the network against frozen snapshots of itself (0: never)")
+    ap.add_argument("--arena-episodes", type=int, default=2, metavar="k", help="finished games per arena board")
+    ap.add_argument("--arena-envs", type=int, default=256, help="boards of the arena's own env")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write the final network (examples/evaluate_arena.py loads it)")
     a = ap.parse_args(argv)
+    if a.arena_every > 0 and a.memory:
+        ap.error("--arena-every cannot rate a --memory network: an arena entrant is a function of the observation alone")
 
     torch.manual_seed(a.seed)
     dev = torch.device("cuda", 0)
@@ -127,6 +141,32 @@ def main(argv=None):
                 rho_stats.copy_(buf.stats)          # how far off-policy the rollout is before the first gradient step
             yield from buf.minibatches(a.batch_size, epochs=1, seed=(a.seed + it) * a.epochs + epoch)
 
+    snapshots, arena_env = [], None
+
+    def rate(it):
+        """the current network against the snapshots in an arena of its own -> the row's "arena" entry (None before the
+        first snapshot exists); then the current network becomes the newest snapshot, and the oldest of five leaves"""
+        nonlocal arena_env
+        entry = None
+        if snapshots:
+            if arena_env is None:
+                arena_env = GeneralsSelfPlayVecEnv(a.arena_envs, board_width=a.board, board_height=a.board, max_players=a.players,
+                                                   max_turns=a.max_turns, seed=a.seed + 1, device_outputs=True)
+            play = lambda n, k: torch_policy(lambda o: n(inputs(o, None)), head, seed=a.seed + 7919 * it + k)
+            arena = Arena(arena_env, [play(n, k) for k, n in enumerate(snapshots)] + [play(net, len(snapshots))],
+                          names=[f"iteration {i}" for i in snapshot_its] + ["current"])
+            arena.reset(seed=a.seed + 1 + it)
+            arena.run(episodes_per_env=a.arena_episodes)
+            res = arena.results()
+            ratings = res.ratings(anchor=0)
+            entry = {"rating": float(ratings[-1]), "snapshot_ratings": ratings[:-1].tolist(), "snapshot_iterations": list(snapshot_its),
+                     "win_rate": float(res.entrants["win_rate"][-1]), "games": int(res.totals["games"])}
+        snapshots.append(copy.deepcopy(net).requires_grad_(False))
+        snapshot_its.append(it)
+        del snapshots[:-4], snapshot_its[:-4]
+        return entry
+
+    snapshot_its = []
     buf.begin(*env.reset())
     out, draws, t0 = [], 0, time.perf_counter()
     for it in range(a.iterations):
@@ -165,10 +205,17 @@ def main(argv=None):
         row = {"iteration": it, "policy_loss": s[0], "value_loss": s[1], "entropy": s[2], "clip_fraction": s[3],
                "valid_rows": valid / (a.horizon * B * L), "env_steps": (it + 1) * a.horizon * B,
                "mean_rho": mean_rho, "seconds": time.perf_counter() - t0}
+        if a.arena_every > 0 and (it + 1) % a.arena_every == 0:
+            row["arena"] = rate(it)
         print(json.dumps(row))
         out.append(row)
     moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), start))
     result = {"iterations": out, "bad_actions": head.bad_actions, "rejected": int(buf.rejected.item()), "parameter_change": moved}
+    if a.save:
+        torch.save({"model": net.state_dict(), "board": a.board, "players": a.players, "channels": channels, "features": a.features,
+                    "memory": a.memory}, a.save)
+    if arena_env is not None:
+        arena_env.close()
     env.close()
     return result
 

@@ -16,9 +16,12 @@ from .features import NUM_STRATEGIC_FEATURES, STRATEGIC_FEATURE_NAMES, strategic
 from .memory import MEMORY_PLANE_NAMES, NUM_MEMORY_PLANES, ObservationMemory, remembered_observation  # noqa: F401
 from .q_targets import categorical_target, double_q_target, valid_actions_mask_from_observation  # noqa: F401
 from .symmetry import apply_symmetry, augment_transition, inverse_symmetry, num_symmetries, random_symmetries  # noqa: F401
+from .arena import (Arena, ArenaResult, EpisodeTally, balanced_seating, expected_score, fit_elo, random_policy,  # noqa: F401
+                    torch_policy)
 
 __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState",
            "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "strategic_features",
            "NUM_STRATEGIC_FEATURES", "STRATEGIC_FEATURE_NAMES", "ObservationMemory", "remembered_observation", "NUM_MEMORY_PLANES",
            "MEMORY_PLANE_NAMES", "valid_actions_mask_from_observation", "double_q_target", "categorical_target",
-           "apply_symmetry", "augment_transition", "inverse_symmetry", "num_symmetries", "random_symmetries"]
+           "apply_symmetry", "augment_transition", "inverse_symmetry", "num_symmetries", "random_symmetries",
+           "Arena", "ArenaResult", "EpisodeTally", "balanced_seating", "expected_score", "fit_elo", "random_policy", "torch_policy"]

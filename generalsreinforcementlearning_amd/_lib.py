@@ -144,6 +144,15 @@ class ObsSymmetryArgs(C.Structure):
                                              "applied")])
 
 
+class ArenaArgs(C.Structure):
+    """gvec_arena_args (include/generals_vec.h): every pointer is device memory; alive, reset and obs may be None."""
+    _fields_ = ([("rows", C.c_int64)] + [(n, C.c_int32) for n in ("width", "height", "num_learners", "games_cap")]
+                + [("obs_row_stride", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("alive", "terminated", "truncated", "reset", "winner", "reward", "player_ids", "obs",
+                                             "death", "ep_len", "ep_return", "games", "wins", "eliminated", "len_sum", "ret_sum",
+                                             "pair2")])
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -219,6 +228,7 @@ SYMBOLS = {
     "gvec_q_target": (_i32, [_i32, _vp, C.POINTER(QTargetArgs)]),
     "gvec_categorical_target": (_i32, [_i32, _vp, C.POINTER(CategoricalTargetArgs)]),
     "gvec_obs_symmetry": (_i32, [_i32, _vp, C.POINTER(ObsSymmetryArgs)]),
+    "gvec_arena_update": (_i32, [_i32, _vp, C.POINTER(ArenaArgs)]),
     "gvec_gym_observe":(_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_finish_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvec_gym_actions": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
 // gvec_api_obs.hip — the entry points that read a batch of nine-plane observations: the strategic feature planes, the
-// fog-of-war memory planes, the masked Q targets and the board symmetries.  Handle-free like gvec_api_replay.hip's: they check
-// their arguments, which needs no device, and end in ON_DEVICE.  Host only (gvec_handle.hpp); the kernels are in
-// gvec_features.hip, gvec_memory.hip, gvec_qtarget.hip and gvec_symmetry.hip.
+// fog-of-war memory planes, the masked Q targets, the board symmetries and the match arena's tally (which reads one when it
+// is given one).  Handle-free like gvec_api_replay.hip's: they check their arguments, which needs no device, and end in
+// ON_DEVICE.  Host only (gvec_handle.hpp); the kernels are in gvec_features.hip, gvec_memory.hip, gvec_qtarget.hip,
+// gvec_symmetry.hip and gvec_arena.hip.
 #include <cmath>
 
 #include "gvec_handle.hpp"
@@ -10,11 +11,17 @@ namespace {
 
 // what every argument struct here starts with; each entry point calls these in its own order
 template <typename A>
-int32_t check_rows_and_board(const char* fn, const A* a) {
+int32_t check_rows(const char* fn, const A* a) {
   if (a->rows < 0 || a->rows > 0x7FFFFFFFll) {
     set_err("%s: rows %lld outside [0, 2^31)", fn, (long long)a->rows);
     return GVEC_E_INVALID;
   }
+  return GVEC_OK;
+}
+
+template <typename A>
+int32_t check_rows_and_board(const char* fn, const A* a) {
+  RET_IF(check_rows(fn, a));
   if (a->width < 1 || a->width > GVEC_MAX_DIM || a->height < 1 || a->height > GVEC_MAX_DIM) {
     set_err("%s: width %d or height %d outside [1, %d]", fn, a->width, a->height, GVEC_MAX_DIM);
     return GVEC_E_INVALID;
@@ -189,6 +196,31 @@ int32_t gvec_obs_symmetry(int32_t device, void* hip_stream, const gvec_obs_symme
       }
   if (a->rows == 0) return GVEC_OK;
   ON_DEVICE(device, launch_obs_symmetry(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+}
+
+// ---- match arena ----
+int32_t gvec_arena_update(int32_t device, void* hip_stream, const gvec_arena_args* a) {
+  const char* fn = "gvec_arena_update";
+  if (!a) return null_args(fn);
+  if (a->obs) {   // the board is read with an observation only
+    RET_IF(check_rows_and_board(fn, a));
+    RET_IF(check_row_stride(fn, a));
+  } else {
+    RET_IF(check_rows(fn, a));
+  }
+  if (a->num_learners < 1 || a->num_learners > GVEC_MAX_PLAYERS) {
+    set_err("%s: num_learners %d outside [1, %d]", fn, a->num_learners, GVEC_MAX_PLAYERS);
+    return GVEC_E_INVALID;
+  }
+  if (a->games_cap < 0) {
+    set_err("%s: games_cap %d is negative (0 means no cap)", fn, a->games_cap);
+    return GVEC_E_INVALID;
+  }
+  if (!a->terminated || !a->truncated || !a->winner || !a->reward || !a->player_ids) return null_args(fn);
+  if (!a->death || !a->ep_len || !a->ep_return || !a->games || !a->wins || !a->eliminated || !a->len_sum || !a->ret_sum || !a->pair2)
+    return null_args(fn);
+  if (a->rows == 0) return GVEC_OK;
+  ON_DEVICE(device, launch_arena_update(*a, reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
 }  // extern "C"

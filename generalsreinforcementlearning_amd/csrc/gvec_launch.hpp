@@ -322,4 +322,7 @@ hipError_t launch_categorical_target(const gvec_categorical_target_args& a, hipS
 // board symmetries per row (gvec_symmetry.hip; generals_vec.h "board symmetries")
 hipError_t launch_obs_symmetry(const gvec_obs_symmetry_args& a, hipStream_t s);
 
+// match arena: episode tally per env (gvec_arena.hip; generals_vec.h "match arena")
+hipError_t launch_arena_update(const gvec_arena_args& a, hipStream_t s);
+
 }  // namespace gvec

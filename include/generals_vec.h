@@ -956,6 +956,45 @@ typedef struct gvec_obs_symmetry_args {
 } gvec_obs_symmetry_args;
 int32_t gvec_obs_symmetry(int32_t device, void* hip_stream, const gvec_obs_symmetry_args* args);
 
+/* ---- match arena: per-env episode tally and pairwise placements -------------------------------------------
+ * Counts finished games where a self-play step's outputs already lie: one launch per env step, handle-free like the feature
+ * planes (DEVICE pointers on `device`, enqueued on hip_stream, nothing synchronises).  All state is per env and owned by the
+ * caller, so no atomic is needed and every number is the same from run to run.  rows = B envs, L = num_learners columns.
+ * Inputs of the step: alive uint8 [B][L] (NULL: nobody is ever recorded as eliminated), terminated, truncated uint8 [B], reset
+ *   uint8 [B] (this step re-dealt the env and played no turn; NULL: none did), winner int8 [B] (a player id or -1), reward
+ *   float64 [B][L], player_ids int32 [L] (column -> player id), obs float32 [B][L][9][H*W] or NULL, consecutive observations
+ *   obs_row_stride floats apart (only plane 1 is read, and only where an env is truncated).
+ * Running state: death int32 [B][L] (0 alive, else the 1-based episode step at which the column was first seen not alive),
+ *   ep_len int32 [B], ep_return float64 [B][L].  Totals: games int32 [B], wins, eliminated int32 [B][L], len_sum int64 [B],
+ *   ret_sum float64 [B][L], pair2 int32 [B][L][L] (twice the score of column i against column j; the diagonal stays 0).
+ * Per env b, in this order:
+ *   1. reset[b] != 0: the running state is cleared (zeros) and nothing else happens.
+ *   2. ep_len += 1; per column ep_return += reward, and death = ep_len where death == 0 and alive == 0.
+ *   3. terminated[b] | truncated[b] != 0, the episode ends.  With games_cap > 0 and games[b] == games_cap nothing is counted.
+ *      Otherwise a column's key is death when death != 0 (later is better) and 2^20 + land when it survived, land = the number
+ *      of tiles with obs plane 1 == 0.5 (its own) when obs is given and the env was truncated without terminating, else 0; an
+ *      episode is assumed shorter than 2^20 steps.  For i != j: pair2[i][j] += 2 where key_i > key_j, 1 where they are equal.
+ *      games += 1, len_sum += ep_len, wins += (winner[b] == player_ids[column]), eliminated += (death != 0), ret_sum +=
+ *      ep_return.  Counted or not, the running state is cleared.
+ * Integer adds and plain float64 adds in this order: the result is defined to the bit.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a required pointer NULL (all but
+ *   alive, reset and obs), rows < 0 or rows >= 2^31, num_learners outside [1, GVEC_MAX_PLAYERS], games_cap < 0, and with obs:
+ *   width or height outside [1, GVEC_MAX_DIM], obs_row_stride < 9*width*height.  rows == 0 is a no-op that needs no device. */
+typedef struct gvec_arena_args {
+  int64_t rows;
+  int32_t width, height;                                                                   /* read with obs only */
+  int32_t num_learners, games_cap;                                                         /* games_cap 0: no cap */
+  int64_t obs_row_stride;                                                                  /* floats, >= 9*width*height */
+  const uint8_t* alive;                                                                    /* NULL: everybody, always */
+  const uint8_t* terminated; const uint8_t* truncated;
+  const uint8_t* reset;                                                                    /* NULL: no env was re-dealt */
+  const int8_t* winner; const double* reward; const int32_t* player_ids;
+  const float* obs;                                                                        /* NULL: survivors tie */
+  int32_t* death; int32_t* ep_len; double* ep_return;
+  int32_t* games; int32_t* wins; int32_t* eliminated; int64_t* len_sum; double* ret_sum; int32_t* pair2;
+} gvec_arena_args;
+int32_t gvec_arena_update(int32_t device, void* hip_stream, const gvec_arena_args* args);
+
 /* ---- experience gather support ---------------------------------------
  * Writes the compact state records of envs [env_begin, env_begin+n) into a device
  * buffer (e.g. a torch tensor handed to RCCL) as a slab [n] headers | [n] plane blocks |
