@@ -1,10 +1,12 @@
 """The host side of the match arena (generalsreinforcementlearning_amd/arena.py): seating, the rating fit, and the argument
-checks of EpisodeTally.update and gvec_arena_update, which run before anything touches a device and are pinned here without one."""
+checks of EpisodeTally.update and gvec_arena_update.  The file runs with and without a device and the entry point's pointers
+are placeholders, so every call of it goes through tests/_api_calls.py, which launches nothing on them."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from _api_calls import passes_checks, rejected
 from generalsreinforcementlearning_amd import _lib as lib
 from generalsreinforcementlearning_amd.csrc import build as B
 
@@ -129,7 +131,8 @@ def test_struct_layout_matches_the_header():
             f.alive.offset, f.obs.offset, f.death.offset, f.pair2.offset) == (0, 8, 12, 16, 20, 24, 32, 88, 96, 160)
 
 
-P = 1 << 20   # stands for a device pointer: no check dereferences it
+FN = "gvec_arena_update"
+P = 1 << 20   # stands for a device pointer: no check dereferences it, a launch would (passes_checks keeps it from one)
 STATE = ("death", "ep_len", "ep_return", "games", "wins", "eliminated", "len_sum", "ret_sum", "pair2")
 
 
@@ -141,8 +144,7 @@ def _args(**over):
 
 
 def _rejected(L, a, text):
-    assert L.gvec_arena_update(0, None, C.byref(a) if a is not None else None) == -1
-    assert text in L.gvec_last_error().decode(), L.gvec_last_error()
+    rejected(L, FN, a, text)
 
 
 def test_entry_point_refuses_bad_arguments_without_a_gpu(L):
@@ -161,16 +163,14 @@ def test_entry_point_refuses_bad_arguments_without_a_gpu(L):
 
 
 def test_zero_rows_is_a_no_op_without_a_device(L):
-    assert L.gvec_arena_update(0, None, C.byref(_args(rows=0))) == 0
-    assert L.gvec_arena_update(0, None, C.byref(_args(rows=0, num_learners=8, games_cap=5, alive=None, reset=None))) == 0
+    passes_checks(L, FN, _args(rows=0))
+    passes_checks(L, FN, _args(rows=0, num_learners=8, games_cap=5, alive=None, reset=None))
     # without an observation the board is not read: its fields may hold anything
-    assert L.gvec_arena_update(0, None, C.byref(_args(rows=0, obs=None, width=0, height=99, obs_row_stride=0, num_learners=1))) == 0
+    passes_checks(L, FN, _args(rows=0, obs=None, width=0, height=99, obs_row_stride=0, num_learners=1))
 
 
 def test_passing_arguments_reach_the_device_check(L):
     """what refuses a call that passes every check on a box without a GPU is the device, with another code (with one, the
-    stand-in pointers must not be launched on: nothing to pin there)"""
-    import torch
-    if not torch.cuda.is_available():
-        assert L.gvec_arena_update(0, None, C.byref(_args())) == -2      # GVEC_E_NO_DEVICE
-        assert L.gvec_arena_update(0, None, C.byref(_args(alive=None, reset=None, obs=None, width=0, height=0))) == -2
+    stand-in pointers must not be launched on: passes_checks makes no call there)"""
+    passes_checks(L, FN, _args())                                        # GVEC_E_NO_DEVICE
+    passes_checks(L, FN, _args(alive=None, reset=None, obs=None, width=0, height=0))

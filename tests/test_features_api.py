@@ -1,10 +1,12 @@
-"""The argument checks of gvec_obs_features and of its Python front (features.strategic_features, the envs' option).  They run
-before anything touches a device, so they are pinned here without one.  The checks it shares with the other observation-batch
-entry points (null arguments, rows, board, row stride) are in test_qtarget_api.py's table."""
+"""The argument checks of gvec_obs_features and of its Python front (features.strategic_features, the envs' option).  The
+file runs with and without a device and its pointers are placeholders, so every call of the entry point goes through
+tests/_api_calls.py, which launches nothing on them.  The checks it shares with the other observation-batch entry points (null
+arguments, rows, board, row stride) are in test_qtarget_api.py's table."""
 import ctypes as C
 
 import pytest
 
+from _api_calls import passes_checks, rejected
 from generalsreinforcementlearning_amd import _lib as lib
 from generalsreinforcementlearning_amd.csrc import build as B
 
@@ -15,7 +17,8 @@ def L():
     return lib.load()
 
 
-P = 4096   # stands for a device pointer: no check dereferences it
+FN = "gvec_obs_features"
+P = 4096   # stands for a device pointer: no check dereferences it, a launch would (passes_checks keeps it from one)
 
 
 def _args(**over):
@@ -25,8 +28,7 @@ def _args(**over):
 
 
 def _rejected(L, a, text):
-    assert L.gvec_obs_features(0, None, C.byref(a) if a is not None else None) == -1
-    assert text in L.gvec_last_error().decode(), L.gvec_last_error()
+    rejected(L, FN, a, text)
 
 
 def test_struct_layout_matches_the_header():
@@ -46,15 +48,15 @@ def test_reserved_must_be_zero(L):
 
 
 def test_zero_rows_is_a_no_op_without_a_device(L):
-    assert L.gvec_obs_features(0, None, C.byref(_args(rows=0))) == 0
-    assert L.gvec_obs_features(0, None, C.byref(_args(rows=0, obs_row_stride=9 * 225 + 7, cap=1024))) == 0
+    passes_checks(L, FN, _args(rows=0))
+    passes_checks(L, FN, _args(rows=0, obs_row_stride=9 * 225 + 7, cap=1024))
     _rejected(L, _args(rows=0, cap=48), "cap 48")                       # the checks come first all the same
 
 
 def test_every_bound_is_accepted(L):
     """the extremes of every range pass the checks: rows == 0 keeps the call off the device"""
     for w, h, cap in ((1, 1, 2), (32, 32, 1024), (32, 1, 2), (1, 32, 1024)):
-        assert L.gvec_obs_features(0, None, C.byref(_args(rows=0, width=w, height=h, cap=cap, obs_row_stride=9 * w * h))) == 0
+        passes_checks(L, FN, _args(rows=0, width=w, height=h, cap=cap, obs_row_stride=9 * w * h))
 
 
 def test_strategic_features_rejects_bad_input_before_any_launch():

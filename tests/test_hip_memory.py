@@ -499,3 +499,29 @@ def test_rollout_buffer_without_memory_is_what_it_was():
         assert buf.mem_store is None and buf.memory is None
     finally:
         env.close()
+
+
+# ---- prev flush against out ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("order", [("out", "prev"), ("prev", "out")], ids=["prev_behind_out", "prev_before_out"])
+@pytest.mark.parametrize("W,H,rows", [(15, 15, 67), (5, 6, 3)], ids=["15x15", "5x6"])          # 5x6: a row is no multiple of a wave or of 16 bytes
+def test_prev_flush_against_out(W, H, rows, order):
+    """prev = out + STATE bytes and prev = out - STATE pass the argument checks (test_memory_api.py): there a store one
+    element past out's end, or one before its start, lands in the previous state.  obs, reset, prev and out are carved out of
+    one device allocation (tests/_slab.py); one update from a random previous state with some rows reset: out is the
+    reference's bit for bit, prev, obs and reset are what was uploaded, guard bands and gaps untouched."""
+    from _slab import Slab
+    rpf, cap = 1, 64
+    obs, reset = _sequence(W, H, rows, rpf)
+    ref = _reference(W, H, rows, rpf, cap)
+    s = next(s for s in range(1, STEPS) if 0 < int(reset[s].sum()) < rows)                     # some rows reset, not all
+    STATE = rows * 4 * H * W * 4
+    slab = Slab({"obs": rows * 9 * H * W * 4, "reset": rows // rpf, "prev": STATE, "out": STATE}, (order, ("obs",), ("reset",)))
+    assert slab.offsets[order[1]] - slab.offsets[order[0]] == STATE
+    slab.put("obs", obs[s])
+    slab.put("reset", reset[s])
+    slab.put("prev", ref[s - 1])
+    slab.upload(_torch(), _dev())
+    hip_update(slab.at("obs"), slab.at("prev"), slab.at("reset"), slab.at("out"), W, H, cap, rows, rpf)   # raises unless 0
+    assert not np.array_equal(ref[s].view(np.uint32), ref[s - 1].view(np.uint32))
+    slab.check({"out": ref[s]}, f"{W}x{H}, {order}")

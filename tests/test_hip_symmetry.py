@@ -381,3 +381,115 @@ def test_guard_bands_and_a_second_call(W, H, rows):
         check_all(res, shift)
     for before, after in zip(snapshot, [x[1] for x in first[0]] + [first[1][1], first[2][1]]):
         assert t.equal(before, after)
+
+
+# ---- buffers that exactly touch ---------------------------------------------------------------------------------------------
+# The entry point accepts an output whose first byte is the first byte behind an input, and one whose last byte is the last
+# before it.  There a store one element past an end - a mask head or tail at the wrong alignment, the last slot of a strided
+# row - lands in live input data, not in a guard band or the allocator's slack.  Every buffer of these launches is carved out
+# of one device allocation (tests/_slab.py), so the distances are exact; after the launch every output is the reference's bit
+# for bit, every input what was uploaded, and the guard bands and gaps untouched.
+TOUCH_W = TOUCH_H = 15
+TOUCH_BUFFERS = ("sym", "in", "out", "mask_in", "mask_out", "values_in", "values_out", "action_in", "action_out", "applied")
+
+
+@functools.lru_cache(maxsize=None)
+def _touching_batch(rows, planes):
+    """(inputs, the reference's outputs) of a 15x15 launch of one plane set with mask, values, action and applied - drawn
+    once, left unchanged.  From nine rows on every symmetry and the out-of-range 8 occur in turn (three rows: 4, 5, 6); a few
+    rows play a half move from the middle of the board, which sym 1 keeps and sym 2 turns into the identity."""
+    W, H = TOUCH_W, TOUCH_H
+    A = 5 * H * W
+    rng = np.random.default_rng(77000 + 10 * rows + planes)
+    sym = ((np.arange(rows) + (4 if rows < 8 else 0)) % 9).astype(np.uint8)
+    p = _float_bits(rng, (rows, planes, H, W))
+    mask = rng.integers(0, 256, size=(rows, A), dtype=np.uint8)              # any byte: they are moved, not normalised
+    values = _float_bits(rng, (rows, A))
+    action = (5 * rng.integers(0, H * W, size=rows) + rng.integers(0, 4, size=rows)).astype(np.int64)
+    action[np.isin(np.arange(rows) % 64, (1, 2, 5))] = 5 * (7 * W + 7) + 4
+    if rows > 16:
+        action[9], action[10] = -1, A
+    want_p, want_m, want_v, want_a, applied = SR.apply(sym, H, W, [p], mask, values, action)
+    if rows >= 9:
+        assert set(sym[:9]) == set(range(9)) and applied[8] == 0
+        assert applied[1] == 1 and sym[2] == 2 and applied[2] == 0           # applied differs from sym, and not in every half move
+    ins = dict(sym=sym, planes=p, mask_in=mask, values_in=values, action_in=action)
+    outs = dict(out=want_p[0], mask_out=want_m, values_out=want_v, action_out=want_a, applied=applied)
+    for x in list(ins.values()) + list(outs.values()):
+        x.setflags(write=False)
+    return ins, outs
+
+
+def _launch_touching(rows, groups, distances, planes=9, stride=None, shift=None, mask_out_alignment=None):
+    """one launch of _touching_batch(rows, planes): the buffers of each group flush against each other in the order given, the
+    others apart.  distances: (a, b, bytes) with b's first byte that many behind a's, as the entry point's range check counts."""
+    from _slab import FILL, Slab
+    W, H = TOUCH_W, TOUCH_H
+    HW, A = H * W, 5 * H * W
+    row = planes * HW
+    stride = row if stride is None else stride
+    in_floats = (rows - 1) * stride + row                                     # as far as a strided input reaches
+    ins, outs = _touching_batch(rows, planes)
+    sizes = {"sym": rows, "applied": rows, "in": in_floats * 4, "out": rows * row * 4, "mask_in": rows * A, "mask_out": rows * A,
+             "values_in": rows * A * 4, "values_out": rows * A * 4, "action_in": rows * 8, "action_out": rows * 8}
+    flush = {name for g in groups for name in g}
+    slab = Slab(sizes, tuple(groups) + tuple((name,) for name in TOUCH_BUFFERS if name not in flush), shift)
+    for a, b, nbytes in distances:
+        assert slab.offsets[b] - slab.offsets[a] == nbytes, (a, b)
+    spread = np.full(in_floats, FILL * 0x01010101, np.uint32)                 # the rows of the input, stride apart
+    for r in range(rows):
+        spread[r * stride:r * stride + row] = ins["planes"][r].view(np.uint32).reshape(-1)
+    slab.put("in", spread)
+    for name in ("sym", "mask_in", "values_in", "action_in"):
+        slab.put(name, ins[name])
+    slab.upload(_torch(), _dev())
+    at = slab.at
+    if mask_out_alignment is not None:
+        assert at("mask_out").data_ptr() % 4 == mask_out_alignment
+    _raw(at("sym"), W, H, [(at("in"), at("out"), planes, stride)], mask=(at("mask_in"), at("mask_out")),
+         values=(at("values_in"), at("values_out")), action=(at("action_in"), at("action_out")), applied=at("applied"))   # raises unless 0
+    slab.check(outs, f"{rows} rows, {groups}")
+
+
+def _seams(rows, planes=9):
+    """name -> arguments of _launch_touching: which buffers touch, and the byte distance that says so"""
+    HW, A = TOUCH_H * TOUCH_W, 5 * TOUCH_H * TOUCH_W
+    state = rows * planes * HW * 4
+    strided = ((rows - 1) * 2 * planes * HW + planes * HW) * 4                # the first byte behind the last row's payload
+    seams = {"out_behind_in": dict(groups=[("in", "out")], distances=[("in", "out", state)]),
+             "out_before_in": dict(groups=[("out", "in")], distances=[("out", "in", state)]),
+             "out_behind_strided_in": dict(groups=[("in", "out")], distances=[("in", "out", strided)], stride=2 * planes * HW),
+             "applied_behind_sym": dict(groups=[("sym", "applied")], distances=[("sym", "applied", rows)]),
+             "applied_before_sym": dict(groups=[("applied", "sym")], distances=[("applied", "sym", rows)]),
+             "values_out_behind_values_in": dict(groups=[("values_in", "values_out")], distances=[("values_in", "values_out", rows * A * 4)]),
+             "mask_in_behind_mask_out": dict(groups=[("mask_out", "mask_in")], distances=[("mask_out", "mask_in", rows * A)],
+                                             shift={"mask_out": 3}, mask_out_alignment=3)}
+    for k in range(4):                                                        # the seam at each byte alignment: head and tail stores
+        seams[f"mask_out_behind_mask_in_at_{k}"] = dict(groups=[("mask_in", "mask_out")], distances=[("mask_in", "mask_out", rows * A)],
+                                                        shift={"mask_in": (k - rows * A) % 4}, mask_out_alignment=k)
+    return seams
+
+
+@pytest.mark.parametrize("seam", sorted(_seams(9)))
+def test_an_output_flush_against_an_input(seam):
+    _launch_touching(9, **_seams(9)[seam])
+
+
+# the argument sets that test_symmetry_api.py pins as accepted (3 rows: out = in + 24,300 bytes, in - 24,300, a strided in's
+# end, applied = sym + 3) are launched there only where no device is; here they return 0 on real memory and compute the reference
+@pytest.mark.parametrize("seam", ["out_behind_in", "out_before_in", "out_behind_strided_in", "applied_behind_sym"])
+def test_the_accepted_touching_arguments_of_the_api_test(seam):
+    case = _seams(3)[seam]
+    assert case["distances"][0][2] == {"out_behind_in": 24300, "out_before_in": 24300, "out_behind_strided_in": (2 * 4050 + 2025) * 4,
+                                       "applied_behind_sym": 3}[seam]
+    _launch_touching(3, **case)
+
+
+def test_a_staged_launch_with_outputs_flush_against_inputs():
+    """4,096 rows of 15x15, the smallest launch whose transposed rows go through LDS, with four planes (a full pass of three and
+    a partial one): out directly behind in, mask_out directly behind mask_in"""
+    rows, planes = 4096, 4
+    ins, _ = _touching_batch(rows, planes)
+    assert (ins["sym"] & 4).any() and rows >= 4096 and TOUCH_W >= 13
+    _launch_touching(rows, [("in", "out"), ("mask_in", "mask_out")], planes=planes,
+                     distances=[("in", "out", rows * planes * 225 * 4), ("mask_in", "mask_out", rows * 1125)])

@@ -1,10 +1,13 @@
-"""The argument checks of gvec_obs_memory_update and of its Python front (memory.ObservationMemory).  They run before
-anything touches a device, so they are pinned here without one.  The checks it shares with the other observation-batch entry
-points (null arguments, rows, board, row stride) are in test_qtarget_api.py's table."""
+"""The argument checks of gvec_obs_memory_update and of its Python front (memory.ObservationMemory).  The file runs with and
+without a device and its pointers are placeholders, so every call of the entry point goes through tests/_api_calls.py: one
+that passes the checks with rows > 0 is made only where no device can launch it (test_hip_memory.py runs such arguments on
+real memory).  The checks it shares with the other observation-batch entry points (null arguments, rows, board, row stride)
+are in test_qtarget_api.py's table."""
 import ctypes as C
 
 import pytest
 
+from _api_calls import passes_checks, rejected
 from generalsreinforcementlearning_amd import _lib as lib
 from generalsreinforcementlearning_amd.csrc import build as B
 
@@ -15,7 +18,8 @@ def L():
     return lib.load()
 
 
-P = 1 << 20   # stands for a device pointer: no check dereferences it
+FN = "gvec_obs_memory_update"
+P = 1 << 20   # stands for a device pointer: no check dereferences it, a launch would (passes_checks keeps it from one)
 STATE = 3 * 4 * 225 * 4   # bytes of the default arguments' state
 
 
@@ -26,8 +30,7 @@ def _args(**over):
 
 
 def _rejected(L, a, text):
-    assert L.gvec_obs_memory_update(0, None, C.byref(a) if a is not None else None) == -1
-    assert text in L.gvec_last_error().decode(), L.gvec_last_error()
+    rejected(L, FN, a, text)
 
 
 def test_struct_layout_matches_the_header():
@@ -53,9 +56,8 @@ def test_prev_overlapping_out_without_being_it(L, delta):
 
 
 def test_zero_rows_is_a_no_op_without_a_device(L):
-    assert L.gvec_obs_memory_update(0, None, C.byref(_args(rows=0))) == 0
-    assert L.gvec_obs_memory_update(0, None, C.byref(_args(rows=0, rows_per_flag=7, obs_row_stride=9 * 225 + 7, cap=1024,
-                                                            prev=2 * P, reset=3 * P))) == 0
+    passes_checks(L, FN, _args(rows=0))
+    passes_checks(L, FN, _args(rows=0, rows_per_flag=7, obs_row_stride=9 * 225 + 7, cap=1024, prev=2 * P, reset=3 * P))
     _rejected(L, _args(rows=0, cap=48), "cap 48")                       # the checks come first all the same
     _rejected(L, _args(rows=0, out=None), "NULL")
 
@@ -63,7 +65,7 @@ def test_zero_rows_is_a_no_op_without_a_device(L):
 def test_every_bound_is_accepted(L):
     """the extremes of every range pass the checks: rows == 0 keeps the call off the device"""
     for w, h, cap in ((1, 1, 2), (32, 32, 1024), (32, 1, 2), (1, 32, 1024)):
-        assert L.gvec_obs_memory_update(0, None, C.byref(_args(rows=0, width=w, height=h, cap=cap, obs_row_stride=9 * w * h))) == 0
+        passes_checks(L, FN, _args(rows=0, width=w, height=h, cap=cap, obs_row_stride=9 * w * h))
 
 
 def test_passing_arguments_reach_the_device_check(L):
@@ -73,7 +75,7 @@ def test_passing_arguments_reach_the_device_check(L):
     if torch.cuda.is_available():
         pytest.skip("GPU present")
     for prev in (2 * P, 2 * P + STATE, 2 * P - STATE):
-        assert L.gvec_obs_memory_update(0, None, C.byref(_args(prev=prev))) == -2   # GVEC_E_NO_DEVICE
+        passes_checks(L, FN, _args(prev=prev))                                      # GVEC_E_NO_DEVICE
 
 
 def test_python_front_rejects_bad_input_before_any_launch():

@@ -1,5 +1,6 @@
 """The argument checks of gvec_obs_valid_mask, gvec_q_target and gvec_categorical_target and of their Python front
-(q_targets.py).  They run before anything touches a device, so they are pinned here without one.
+(q_targets.py).  The file runs with and without a device and its pointers are placeholders, so every call of an entry point
+goes through tests/_api_calls.py, which launches nothing on them.
 
 The checks that all five observation-batch entry points of gvec_api_obs.hip share (null arguments, rows, board, row stride,
 zero rows, the bounds, valid arguments reaching the device) are one table here, ENTRY / REQUIRED / OPTIONAL, which also
@@ -9,6 +10,7 @@ import ctypes as C
 
 import pytest
 
+from _api_calls import passes_checks, rejected
 from generalsreinforcementlearning_amd import _lib as lib
 from generalsreinforcementlearning_amd.csrc import build as B
 
@@ -19,7 +21,7 @@ def L():
     return lib.load()
 
 
-P = 1 << 20   # stands for a device pointer: no check dereferences it
+P = 1 << 20   # stands for a device pointer: no check dereferences it, a launch would (passes_checks keeps it from one)
 
 
 def _mask_args(**over):
@@ -66,9 +68,7 @@ OPTIONAL = {"gvec_obs_valid_mask": (), "gvec_q_target": ("q_select", "discount",
 
 
 def _rejected(L, fn, a, text):
-    assert getattr(L, fn)(0, None, C.byref(a) if a is not None else None) == -1
-    msg = L.gvec_last_error().decode()
-    assert text in msg and msg.startswith(fn + ":"), msg
+    rejected(L, fn, a, text)
 
 
 def test_struct_layouts_match_the_header():
@@ -129,7 +129,7 @@ def test_support_bounds(L, lo, hi):
 
 @pytest.mark.parametrize("fn", ENTRY)
 def test_zero_rows_is_a_no_op_without_a_device(L, fn):
-    assert getattr(L, fn)(0, None, C.byref(ENTRY[fn](rows=0))) == 0
+    passes_checks(L, fn, ENTRY[fn](rows=0))
     _rejected(L, fn, ENTRY[fn](rows=0, width=33), "outside [1, 32]")                 # the checks come first all the same
     _rejected(L, fn, ENTRY[fn](rows=0, **{REQUIRED[fn][0]: None}), "NULL")
 
@@ -138,9 +138,9 @@ def test_every_bound_is_accepted(L):
     """the extremes of every range pass the checks: rows == 0 keeps the call off the device"""
     for w, h in ((1, 1), (32, 32), (32, 1), (1, 32)):
         for fn in ENTRY:
-            assert getattr(L, fn)(0, None, C.byref(ENTRY[fn](rows=0, width=w, height=h, obs_row_stride=9 * w * h))) == 0
+            passes_checks(L, fn, ENTRY[fn](rows=0, width=w, height=h, obs_row_stride=9 * w * h))
     for n in (2, 64):
-        assert L.gvec_categorical_target(0, None, C.byref(_c_args(rows=0, num_atoms=n, v_min=-1e30, v_max=1e30))) == 0
+        passes_checks(L, "gvec_categorical_target", _c_args(rows=0, num_atoms=n, v_min=-1e30, v_max=1e30))
 
 
 @pytest.mark.parametrize("fn", ENTRY)
@@ -150,8 +150,8 @@ def test_passing_arguments_reach_the_device_check(L, fn):
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present")
-    assert getattr(L, fn)(0, None, C.byref(ENTRY[fn]())) == -2                        # GVEC_E_NO_DEVICE
-    assert getattr(L, fn)(0, None, C.byref(ENTRY[fn](obs_row_stride=9 * 225 + 7, **{k: 7 * P for k in OPTIONAL[fn]}))) == -2
+    passes_checks(L, fn, ENTRY[fn]())                                                 # GVEC_E_NO_DEVICE
+    passes_checks(L, fn, ENTRY[fn](obs_row_stride=9 * 225 + 7, **{k: 7 * P for k in OPTIONAL[fn]}))
 
 
 def test_python_front_rejects_bad_input_before_any_launch():
