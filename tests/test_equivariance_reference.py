@@ -1,0 +1,501 @@
+"""The board's eight symmetries, on the CPU: the transforms of tests/_equivariance.py checked against themselves, and the
+oracle held to step(g.s, g.a) = g.step(s, a) on the very inputs tests/test_hip_equivariance.py gives the device - with the
+coverage of those inputs asserted here, counted on the oracle, so that the device test cannot pass on an easy run.
+
+The cases and the lock-step driver (step_case, Orbit, drive) live here and are imported by the device test: both run the
+same boards, the same moves and the same comparisons; only the engine under test differs."""
+import numpy as np
+import pytest
+
+import _equivariance as Q
+import _gym_reference as G
+import _harness as H
+import _oracle as O
+import _symmetry_reference as S
+
+ABORT_CODES = (1, 2, 3, 4, 6, 7, 8)                     # a move the turn refuses: the turn is aborted (5 is ErrGameOver)
+THREE_SEATS = ((0, 0), (3, 0), (2, 2))                  # the generals of the hand-made 4x3 board for three players
+AGENT_MIX = (0, 6000)                                   # no idle seats and few half moves: armies travel, games end
+FLOORS = ("aborted", "eliminated", "finished", "growth", "shared_tile", "transposed_nonsquare")
+# and, where the handle has room for a third seat, "turnover": a player eliminated in a game that goes on
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------------------
+def step_case(mw, mh, maxp, fog=True, turns=50, seed=None, mix=AGENT_MIX):
+    """The padded, ragged batch of one compiled variant (handle limits mw x mh, maxp players): two 4x3 and a 4x4 two-player
+    board, whose games end within tens of turns (with room for a third seat the second one is THREE_SEATS: a player is
+    eliminated and its tiles turn over while the game goes on), and a non-square board near the limit, each with all 8
+    images, and one board that fills (mw, mh) with its 4 non-transposing images - 36 envs in one launch.  Seed, armies,
+    agent mix and turn count are tuned on the oracle until every case meets the coverage floors asserted below."""
+    m = min(mw, mh)
+    fit = lambda w, h: min(maxp, max(2, w * h // 30))
+    near = (m, max(3, m - 3))
+    sizes = [(4, 3, 2), (4, 3, 2 if maxp == 2 else 3), (4, 4, 2), near + (fit(*near),), (mw, mh, fit(mw, mh))]
+    syms = [Q.ALL_SYMS] * 4 + [Q.FLIP_SYMS]
+    return {"mw": mw, "mh": mh, "maxp": maxp, "fog": fog, "turns": turns, "sizes": sizes, "syms": syms,
+            "seed": 71 if seed is None else seed, "permille": 40, "mix": mix, "id": f"{mw}x{mh}_p{maxp}_{'fog' if fog else 'nofog'}"}
+
+
+STEP_CASES = [step_case(*H.VARIANT_DIMS[v], maxp) for v in sorted(H.VARIANT_DIMS) for maxp in (2, 4, 8)]
+FOG_OFF_CASE = step_case(*H.VARIANT_DIMS[(2, "odd")], 4, fog=False)
+
+
+class Orbit:
+    """The image envs of a case: boards, and for image i its base row and symmetry."""
+
+    def __init__(self, case):
+        c = case
+        planes = H.gen_boards(c["seed"], [(4, 3, 2) if size == (4, 3, 3) else size for size in c["sizes"]], c["mw"], c["mh"])
+        for e, (w, h, p) in enumerate(c["sizes"]):
+            if (w, h, p) == (4, 3, 3):                   # the generator does not seat three on a board this small
+                army, owner, typ = O.planes_from_tiles(4, 3, [dict(x=x, y=y, owner=q, type=1) for q, (x, y) in enumerate(THREE_SEATS)],
+                                                       c["mw"] * c["mh"])
+                planes[0][e], planes[1][e], planes[2][e], planes[5][e] = army, owner, typ, 3
+        for e in range(len(c["sizes"])):                 # armies on the generals: the first fights come within a few turns
+            planes[0][e][planes[2][e] == 1] = 30 - 3 * e
+        (self.army, self.owner, self.typ, self.w, self.h, self.p, self.base, self.sym) = Q.orbit_boards(*planes, c["syms"])
+        self.B = len(self.w)
+        self.bases = np.flatnonzero(self.sym == 0)
+        for i in range(self.B):
+            assert self.w[i] <= c["mw"] and self.h[i] <= c["mh"]
+
+    def reset(self, target):
+        target.reset(self.army, self.owner, self.typ, self.w, self.h, self.p)
+
+    def dims(self, i):
+        """(w, h) of image i's base board"""
+        b = self.base[i]
+        return int(self.w[b]), int(self.h[b])
+
+    def image_actions(self, acts):
+        """every image env's slots from its base env's moves"""
+        out = acts.copy()
+        for i in range(self.B):
+            out[i] = Q.image_actions(acts[self.base[i]], *self.dims(i), int(self.sym[i]))
+        return out
+
+
+class OracleAsEngine:
+    """An OracleBatch under VecEngine's method names, for the driver."""
+
+    def __init__(self, ora):
+        self.ora, self.B, self.max_p, self.stride = ora, ora.B, ora.max_p, ora.stride
+
+    def step(self, acts, want_mask=False):
+        return self.ora.step(acts, want_mask=want_mask)
+
+    def game_state(self, env_begin=0, n=None, fields=None):
+        return self.ora.read_state(env_begin, n, fields)
+
+    def write_state(self, arrays, env_begin=0):
+        self.ora.write_state(arrays, env_begin)
+
+    def observe(self, player=-1):
+        assert player == -1
+        return np.stack([self.ora.observe(p) for p in range(self.max_p)], axis=1)
+
+    def serializer_mask_bits(self):
+        return self.ora.serializer_mask()
+
+    def experience_begin(self):
+        self.ora.experience_begin()
+
+    def experience_rewards(self):
+        r, d = self.ora.rewards()
+        return r, d.astype(bool)
+
+    def compute_player_visibility(self, player):
+        vis, fog = np.zeros((self.B, self.stride), bool), np.zeros((self.B, self.stride), bool)
+        for e in range(self.B):
+            eng = self.ora.engine(e)
+            if player < eng.p:
+                v, f = eng.player_visibility(player)
+                vis[e, : len(v)], fog[e, : len(f)] = v, f
+        return vis, fog
+
+
+# ---- the driver -------------------------------------------------------------------------------------------------------------
+def compare_states(orb, st, ctx):
+    for i in range(orb.B):
+        want = Q.image_state(st, int(orb.base[i]), int(orb.sym[i]))
+        Q.assert_env_states_equal(Q.env_state(st, i), want, f"{ctx}: env {i} (sym {orb.sym[i]} of env {orb.base[i]})")
+
+
+def compare_rows(orb, rows, image, what, ctx):
+    """rows [B, ...]: image(rows[base], w, h, sym) must be rows[i], bit for bit"""
+    for i in range(orb.B):
+        want = image(rows[orb.base[i]], *orb.dims(i), int(orb.sym[i]))
+        got = rows[i]
+        if want.dtype.kind == "f":
+            want, got = want.view(np.uint32), np.ascontiguousarray(got).view(np.uint32)
+        if not np.array_equal(got, want):
+            bad = np.argwhere(got != want)
+            raise AssertionError(f"{ctx}: {what} of env {i} (sym {orb.sym[i]} of env {orb.base[i]}, base board {orb.dims(i)}) is not the "
+                                 f"image of the base env's at {len(bad)} place(s), first {tuple(bad[0])}")
+
+
+def compare_outputs(orb, target, rewards, ctx):
+    """the per-player outputs of every image env against the transformed base env"""
+    compare_rows(orb, target.observe(-1), Q.image_observation, "observe(-1)", ctx)
+    compare_rows(orb, target.serializer_mask_bits(), lambda b, w, h, s: Q.image_packed_mask(b, w, h, s, Q.SERIALIZER_VECTORS),
+                 "the serializer mask", ctx)
+    for p in range(target.max_p):
+        vis, fog = target.compute_player_visibility(p)
+        live = (orb.p > p)[:, None]                      # a seat the env does not have: nothing is promised about its planes
+        compare_rows(orb, np.asarray(vis) & live, Q.image_tiles, f"player {p}'s visibility", ctx)
+        compare_rows(orb, np.asarray(fog) & live, Q.image_tiles, f"player {p}'s fog plane", ctx)
+        if hasattr(target, "stream_deltas"):
+            kind, count, upd = target.stream_deltas(p)
+            pk, poff, pupd = target.stream_deltas_packed(p)
+            for i in np.flatnonzero(orb.p > p):
+                b, s = int(orb.base[i]), int(orb.sym[i])
+                assert kind[i] == kind[b] and count[i] == count[b] and pk[i] == pk[b], f"{ctx}: stream delta kind / count of env {i}, viewer {p}"
+                want = Q.image_deltas(upd[b], count[b], *orb.dims(i), s)
+                assert np.array_equal(np.sort(upd[i, : count[i]]), want), f"{ctx}: stream deltas of env {i} (sym {s} of env {b}), viewer {p}"
+                assert np.array_equal(np.sort(Q.packed_deltas(poff, pupd, i)[0]), Q.image_deltas(*Q.packed_deltas(poff, pupd, b), *orb.dims(i), s)), \
+                    f"{ctx}: packed stream deltas of env {i} (sym {s} of env {b}), viewer {p}"
+    r, d = rewards
+    assert np.array_equal(r.view(np.uint32), r[orb.base].view(np.uint32)), f"{ctx}: rewards differ from the base env's in envs " \
+        f"{np.unique(np.argwhere(r.view(np.uint32) != r[orb.base].view(np.uint32))[:, 0])[:8]}"
+    assert np.array_equal(d, d[orb.base]), f"{ctx}: the rewards' done flags differ from the base env's"
+    return int(np.count_nonzero(r[orb.bases]))
+
+
+def drive(case, orb, target, ora, turns, outputs_every=5, seed_offset=0, on_state=None):
+    """`turns` lock-step turns: the oracle's agent moves the base envs, every image env plays the image of its base env's
+    moves, and after every turn each image env of `target` must be the image of its base env - err, full state, packed legal
+    masks; every `outputs_every`-th turn also every player's observation, serializer mask, visibility, rewards and (on the
+    device) stream deltas.  `ora` supplies the moves (and, when `target` wraps it, is the engine under test).  Returns the
+    coverage counted on the base envs of the oracle."""
+    own = isinstance(target, OracleAsEngine) and target.ora is ora
+    cov = dict.fromkeys(FLOORS, 0)
+    cov["rewards"] = cov["turnover"] = 0
+    cov["transposed_nonsquare"] = int(sum(1 for i in range(orb.B) if orb.sym[i] & 4 and orb.w[i] != orb.h[i]))
+    alive = ora.read_state(fields=("alive",))["alive"].copy()
+    for k in range(turns):
+        ctx = f"{case['id']} turn {k}"
+        acts = orb.image_actions(ora.agent_actions(case["seed"] + seed_offset, case["permille"]))
+        outputs = (k + 1) % outputs_every == 0
+        if outputs:
+            target.experience_begin()
+        err, bits = target.step(acts, want_mask=True)
+        oerr = err if own else ora.step(acts)
+        assert np.array_equal(err, err[orb.base]), f"{ctx}: err differs from the base env's in envs {np.flatnonzero(err != err[orb.base])[:8]}: " \
+            f"{err[err != err[orb.base]][:8]} vs {err[orb.base][err != err[orb.base]][:8]}"
+        st = target.game_state()
+        compare_states(orb, st, ctx)
+        compare_rows(orb, bits, lambda b, w, h, s: Q.image_packed_mask(b, w, h, s, Q.ENGINE_VECTORS), "the post-step legal mask", ctx)
+        if outputs:
+            cov["rewards"] += compare_outputs(orb, target, target.experience_rewards(), ctx)
+        if on_state is not None:
+            on_state(st)
+        # coverage, on the oracle's base envs
+        ost = st if own else ora.read_state(fields=("alive", "done", "turn"))
+        for b in orb.bases:
+            played = oerr[b] != 5
+            cov["aborted"] += int(oerr[b] in ABORT_CODES)
+            cov["eliminated"] += int((alive[b] != 0).sum() - (ost["alive"][b] != 0).sum())
+            cov["finished"] += int(played and ost["done"][b])
+            cov["turnover"] += int((alive[b] != 0).sum() > (ost["alive"][b] != 0).sum() and not ost["done"][b])
+            cov["growth"] += int(played and oerr[b] == 0 and ost["turn"][b] % 25 == 0)
+            cov["shared_tile"] += int(played and Q.moves_share_a_tile(acts[b], int(orb.p[b])))
+        alive = ost["alive"].copy()
+    return cov
+
+
+def assert_floors(cov, case):
+    short = [f for f in FLOORS + (("turnover",) if case["maxp"] > 2 else ()) if cov[f] < 1]
+    assert not short, f"{case['id']}: the run holds no {', '.join(short)}: {cov}"
+
+
+def oracle_run(case):
+    orb = Orbit(case)
+    ora = O.OracleBatch(orb.B, case["mw"], case["mh"], case["maxp"], fog=case["fog"])
+    orb.reset(ora)
+    ora.set_agent_mix(*case["mix"])
+    return orb, ora, OracleAsEngine(ora)
+
+
+# ---- helper self-checks -----------------------------------------------------------------------------------------------------
+BOARDS = [(7, 5), (5, 5), (3, 8), (12, 9)]
+
+
+@pytest.mark.parametrize("w,h", BOARDS, ids=[f"{w}x{h}" for w, h in BOARDS])
+def test_a_symmetry_and_its_inverse_compose_to_the_identity(w, h):
+    rng = np.random.default_rng(w * 100 + h)
+    stride, n, P = w * h + 11, w * h, 3
+    state = {f: np.full((2, stride), Q.PAD[f], dt) for f, dt in (("army", np.int32), ("owner", np.int8), ("type", np.uint8), ("visible", np.uint8),
+                                                               ("listed", np.int8), ("changed", np.uint8), ("vis_changed", np.uint8))}
+    for f in state:
+        state[f][:, :n] = rng.integers(0, 4, (2, n))
+    state.update(width=np.array([w, w], np.int32), height=np.array([h, h], np.int32), turn=np.array([3, 4], np.int32),
+                 general_idx=np.array([[0, n - 1, -1], [w - 1, n - w, 5]], np.int32), alive=np.ones((2, P), np.uint8))
+    acts = np.zeros((2, P), O.ACTION_DTYPE)
+    acts["from_x"], acts["from_y"] = rng.integers(0, w, (2, P)), rng.integers(0, h, (2, P))
+    acts["to_x"], acts["to_y"] = acts["from_x"] + rng.integers(-1, 2, (2, P)), acts["from_y"] + rng.integers(-1, 2, (2, P))   # off the board too
+    acts["flags"] = rng.integers(0, 4, (2, P))
+    mb = 4 * ((stride + 63) // 64) * 8
+    u = np.zeros((P, 4, mb // 4 * 8), np.uint8)
+    u[..., :n] = rng.integers(0, 2, (P, 4, n))
+    bits = np.packbits(u, axis=-1, bitorder="little").reshape(P, mb)
+    row = np.zeros((P, 9 * stride), np.float32)
+    row[:, : 9 * n] = rng.random((P, 9 * n), np.float32)
+    gym = rng.random((2, 9, h, w), np.float32)
+    upd = (rng.permutation(n)[: n // 2].astype(np.uint64) | (rng.integers(0, 2 ** 31, n // 2).astype(np.uint64) << np.uint64(16)))
+    for s in Q.ALL_SYMS:
+        inv = S.INVERSE[s]
+        iw, ih = Q.image_dims(w, h, s)
+        assert (iw, ih) == ((h, w) if s & 4 else (w, h)), "a transposing symmetry swaps the dims, the others keep them"
+        assert sorted(Q.tile_perm(w, h, s)) == list(range(n))
+        assert np.array_equal(Q.tile_perm(iw, ih, inv)[Q.tile_perm(w, h, s)], np.arange(n))
+        img = Q.image_state(state, 1, s)
+        assert (img["width"], img["height"]) == (iw, ih) and img["turn"] == 4
+        back = Q.image_state({f: np.asarray(v)[None] for f, v in img.items()}, 0, inv)
+        for f in state:
+            assert np.array_equal(back[f], state[f][1]), (s, f)
+        assert np.array_equal(Q.image_actions(Q.image_actions(acts, w, h, s), iw, ih, inv), acts)
+        for vec in (Q.ENGINE_VECTORS, Q.SERIALIZER_VECTORS):
+            assert np.array_equal(Q.image_packed_mask(Q.image_packed_mask(bits, w, h, s, vec), iw, ih, inv, vec), bits)
+        assert np.array_equal(Q.image_observation(Q.image_observation(row, w, h, s), iw, ih, inv), row)
+        assert np.array_equal(Q.image_observation(Q.image_observation(gym, w, h, s), iw, ih, inv), gym)
+        assert np.array_equal(Q.image_deltas(Q.image_deltas(upd, len(upd), w, h, s), len(upd), iw, ih, inv), np.sort(upd))
+        if s:
+            assert not np.array_equal(Q.image_tiles(np.arange(stride), w, h, s), Q.image_tiles(np.arange(stride), w, h, 0))
+
+
+def test_transforms_agree_with_the_plane_transforms():
+    """the permutation against _symmetry_reference.transform_planes, and a move against where its two tiles go"""
+    w, h = 6, 4
+    plane = np.arange(w * h)
+    for s in Q.ALL_SYMS:
+        iw, ih = Q.image_dims(w, h, s)
+        assert np.array_equal(Q.image_tiles(plane, w, h, s).reshape(ih, iw), S.transform_planes(plane.reshape(h, w), s))
+        a = np.zeros(1, O.ACTION_DTYPE)
+        a[0] = (2, 1, 3, 1, 1, (0, 0, 0))
+        b = Q.image_actions(a, w, h, s)[0]
+        perm = Q.tile_perm(w, h, s)
+        assert b["from_y"] * iw + b["from_x"] == perm[1 * w + 2] and b["to_y"] * iw + b["to_x"] == perm[1 * w + 3]
+        assert (b["to_x"] - b["from_x"], b["to_y"] - b["from_y"]) == S.map_vector(s, 1, 0)
+        idle = np.zeros(2, O.ACTION_DTYPE)
+        assert np.array_equal(Q.image_actions(idle, w, h, s), idle)
+
+
+def _probe_direction_order(packed_mask_of):
+    """A 3x3 board, player 0's general with an army in the middle: block one neighbour with a mountain and see which bit-plane
+    loses the middle tile's bit."""
+    order = [None] * 4
+    for dx, dy in Q.ENGINE_VECTORS:
+        masks = []
+        for blocked in (False, True):
+            tiles = [dict(x=1, y=1, owner=0, army=9, type=1), dict(x=0, y=0, owner=1, army=1, type=1)]
+            if blocked:
+                tiles.append(dict(x=1 + dx, y=1 + dy, type=3))
+            army, owner, typ = O.planes_from_tiles(3, 3, tiles)
+            ora = O.OracleBatch(1, 3, 3, 2)
+            ora.reset(army[None], owner[None], typ[None], [3], [3], [2])
+            bits = packed_mask_of(ora)[0, 0]
+            masks.append(np.unpackbits(bits.reshape(4, -1), axis=-1, bitorder="little")[:, 4])
+        assert masks[0].all(), "the middle tile may move in all four directions"
+        dropped = np.flatnonzero(masks[0] != masks[1])
+        assert len(dropped) == 1
+        order[int(dropped[0])] = (dx, dy)
+    return tuple(order)
+
+
+def test_direction_orders_of_the_two_masks():
+    assert _probe_direction_order(lambda ora: ora.legal_mask()) == Q.ENGINE_VECTORS == ((0, -1), (1, 0), (0, 1), (-1, 0))
+    assert _probe_direction_order(lambda ora: ora.serializer_mask()) == Q.SERIALIZER_VECTORS == ((0, -1), (0, 1), (-1, 0), (1, 0))
+
+
+def test_orbit_boards_pads_and_swaps():
+    case = step_case(9, 10, 4)
+    orb = Orbit(case)
+    assert orb.B == 36 and list(orb.bases) == [0, 8, 16, 24, 32]
+    for i in range(orb.B):
+        n = int(orb.w[i]) * int(orb.h[i])
+        assert (orb.owner[i, n:] == -1).all() and not orb.army[i, n:].any() and not orb.typ[i, n:].any()
+        w, h = orb.dims(i)
+        assert (int(orb.w[i]), int(orb.h[i])) == ((h, w) if orb.sym[i] & 4 else (w, h))
+        assert sorted(orb.army[i]) == sorted(orb.army[orb.base[i]])
+    assert any(orb.sym[i] & 4 and orb.w[i] != orb.h[i] for i in range(orb.B))
+
+
+# ---- the oracle obeys the property, on the device test's inputs -------------------------------------------------------------
+@pytest.mark.parametrize("case", STEP_CASES + [FOG_OFF_CASE], ids=lambda c: c["id"])
+def test_oracle_is_equivariant_on_the_step_cases(case):
+    orb, ora, target = oracle_run(case)
+    cov = drive(case, orb, target, ora, case["turns"])
+    assert_floors(cov, case)
+    assert cov["rewards"] > 0
+
+
+# ---- the aged forms (test_hip_equivariance.py (b)) --------------------------------------------------------------------------
+AGED_MIX = (0, 30000)                                   # many half moves: a general above 65,535 comes back below it
+AGED_CASES = [step_case(*H.VARIANT_DIMS[(s, "odd")], maxp, turns=40, mix=AGED_MIX) for s, maxp in ((1, 2), (2, 4), (4, 8), (7, 2), (10, 4), (16, 8))]
+WARM_TURNS = 8
+
+
+def plant_aged_forms(orb, target, seed):
+    """The values of tests/_state_forms.age_batch on the base envs (a different kind on each: period 5), one owned tile
+    taken off its owner's list, and the same state, transformed, on every image env."""
+    import _state_forms as F
+    F.age_batch(target, seed, period=5)
+    st = target.game_state()
+    army, listed, turn = st["army"].copy(), st["listed"].copy(), st["turn"].copy()
+    for b in orb.bases:
+        n = int(orb.w[b]) * int(orb.h[b])
+        owned = np.flatnonzero((st["owner"][b, :n] >= 0) & (st["type"][b, :n] == 0) & (listed[b, :n] == st["owner"][b, :n]))
+        if len(owned):
+            listed[b, owned[len(owned) // 2]] = -1
+        turn[b] = 21 + (b // 8) % 3                      # the growth turn comes within the first few turns, not on all envs at once
+    for i in range(orb.B):
+        b, s = int(orb.base[i]), int(orb.sym[i])
+        army[i] = Q.image_tiles(army[b], *orb.dims(i), s, 0)
+        listed[i] = Q.image_tiles(listed[b], *orb.dims(i), s, -1)
+        turn[i] = turn[b]
+    target.write_state({"army": army, "listed": listed, "turn": turn})
+
+
+def drive_aged(case, orb, target, ora, after_planting=None):
+    """warm-up turns with many invalid moves, the planting, then the comparison of drive; returns (coverage, forms tally)"""
+    import _state_forms as F
+    warm = dict(case, permille=80)
+    drive(warm, orb, target, ora, WARM_TURNS, outputs_every=4)
+    plant_aged_forms(orb, target, case["seed"])
+    if not (isinstance(target, OracleAsEngine) and target.ora is ora):
+        plant_aged_forms(orb, OracleAsEngine(ora), case["seed"])
+    if after_planting is not None:
+        after_planting()
+    tally = F.FormsTally()
+    tally.add(target.game_state())
+    cov = drive(case, orb, target, ora, case["turns"], seed_offset=1, on_state=tally.add)
+    return cov, tally
+
+
+@pytest.mark.parametrize("case", AGED_CASES, ids=lambda c: c["id"])
+def test_oracle_is_equivariant_on_the_aged_cases(case):
+    orb, ora, target = oracle_run(case)
+    cov, tally = drive_aged(case, orb, target, ora)
+    tally.assert_all_seen(case["id"])                   # wide and list-differs envs, and envs crossing in both directions
+    assert cov["growth"] > 0 and cov["aborted"] > 0, cov
+
+
+# ---- the gym cases (test_hip_equivariance.py (c)) ---------------------------------------------------------------------------
+# The gym layout has one row pitch per batch: a square board takes the 7 symmetries that move it, a non-square one the 3
+# that keep its dims.  The reference env's half move goes in the first direction of (up, right, down, left) that stays on
+# the board (generals_env.py:419-425), which no tile keeps under every symmetry at once (under a transpose no tile keeps it
+# at all), so the envs come in PAIRS: per board and symmetry a copy of the board and its image, and the copy draws half
+# moves only from the tiles _symmetry_reference.exact_tiles names for that symmetry.
+GYM_CASES = {"8x8": dict(w=8, h=8, syms=(1, 2, 3, 4, 5, 6, 7)), "9x6": dict(w=9, h=6, syms=(1, 2, 3))}
+GYM_STEPS = GYM_MAX_TURNS = 40                         # the envs still in their first episode are truncated at the last step
+GYM_BOARDS = 3                                         # per case; the last one is set up for a capture of the general
+
+
+class GymOrbit:
+    """The pairs of a gym case: env 2j is a copy of a board, env 2j + 1 its image under sym[j]."""
+
+    def __init__(self, name):
+        c = GYM_CASES[name]
+        self.W, self.H, K = c["w"], c["h"], GYM_BOARDS
+        w, h = self.W, self.H
+        army, owner, typ, ws, hs, ps = H.gen_boards(23, [(w, h, 2)] * K, w, h)
+        army[typ == 1] = 9                               # a general that may move from the first step on
+        # the last board: player 0 stands next to player 1's general with an army that takes it
+        g1 = int(np.flatnonzero((typ[K - 1] == 1) & (owner[K - 1] == 1))[0])
+        attack = None
+        for d, (dx, dy) in enumerate(Q.ENGINE_VECTORS):  # the gym's move types 0..3 are up, right, down, left too (generals_env.py:369)
+            fx, fy = g1 % w - dx, g1 // w - dy
+            if 0 <= fx < w and 0 <= fy < h and typ[K - 1, fy * w + fx] == 0 and owner[K - 1, fy * w + fx] < 0:
+                army[K - 1, fy * w + fx], owner[K - 1, fy * w + fx] = 60, 0
+                attack = 5 * (fy * w + fx) + d
+                break
+        assert attack is not None
+        rep = [k for k in range(K) for _ in c["syms"]]
+        self.sym = [s for _ in range(K) for s in c["syms"]]
+        self.attack = [attack if k == K - 1 else None for k in rep]
+        self.boards = Q.orbit_boards(army[rep], owner[rep], typ[rep], ws[rep], hs[rep], ps[rep], [(0, s) for s in self.sym])[:6]
+        self.pairs = len(rep)
+        self.B = 2 * self.pairs
+        self.exact = {s: S.exact_tiles(s, h, w) for s in c["syms"]}
+
+
+def drive_gym(orb, step, obs, mask, learners, attack_at=4):
+    """GYM_STEPS steps of a gym env dealt orb.boards.  step(actions [B, L]) -> (obs, reward, terminated, truncated, mask, turn);
+    observation, mask and reward come per learner ([B, L, ...]).  The copy's learners draw from their masks (half moves from
+    the exact tiles only), the image plays the image action; after every step the image env's outputs must be the images of
+    the copy's.  A pair is compared until it has been re-dealt.  Returns the counts the callers assert on."""
+    W, Hh, L = orb.W, orb.H, learners
+    rng = np.random.default_rng(5)
+    live = np.ones(orb.pairs, bool)
+    seen = {"half_moves": 0, "truncated": 0, "terminal_100": 0, "compared": 0, "pairs": orb.pairs}
+    for k in range(GYM_STEPS):
+        actions = np.zeros((orb.B, L), np.int64)
+        for j in range(orb.pairs):
+            s = orb.sym[j]
+            for l in range(L):
+                m = mask[2 * j, l]
+                cand = np.flatnonzero(m)
+                cand = cand[(cand % 5 < 4) | orb.exact[s][cand // 5]]
+                if l == 0 and orb.attack[j] is not None and k >= attack_at and m[orb.attack[j]]:
+                    a = orb.attack[j]
+                else:
+                    a = int(rng.choice(cand)) if len(cand) else 0        # an empty mask: action 0, refused on both boards
+                actions[2 * j, l] = a
+                actions[2 * j + 1, l] = S.transform_actions(a, s, Hh, W)
+                seen["half_moves"] += int(live[j] and a % 5 == 4 and m[a])
+        obs, reward, terminated, truncated, mask, turn = step(actions)
+        last = live.copy()
+        for j in np.flatnonzero(live):
+            b, i, s = 2 * j, 2 * j + 1, orb.sym[j]
+            ctx = f"step {k}, pair {j} (sym {s})"
+            assert np.array_equal(obs[i].view(np.uint32), S.transform_planes(obs[b], s).view(np.uint32)), f"{ctx}: observation"
+            assert np.array_equal(mask[i], S.transform_action_rows(mask[b], s, Hh, W)), f"{ctx}: valid_actions_mask"
+            assert np.array_equal(np.ascontiguousarray(reward[i]).view(np.uint64), np.ascontiguousarray(reward[b]).view(np.uint64)), \
+                f"{ctx}: reward {reward[i]} vs {reward[b]}"
+            assert terminated[i] == terminated[b] and truncated[i] == truncated[b] and turn[i] == turn[b], f"{ctx}: terminated / truncated / turn"
+            seen["truncated"] += int(truncated[b])
+            seen["terminal_100"] += int(terminated[b] and (np.abs(reward[b]) == 100.0).all())
+            if terminated[b] or truncated[b]:
+                live[j] = False                          # re-dealt in the next step, by a hash of the env id
+    seen["compared"] = int(last.sum())
+    return seen
+
+
+def assert_gym_floors(seen, ctx):
+    assert seen["half_moves"] > 0 and seen["truncated"] > 0 and seen["terminal_100"] > 0 and 2 * seen["compared"] >= seen["pairs"], f"{ctx}: {seen}"
+
+
+@pytest.mark.parametrize("name", list(GYM_CASES))
+def test_half_moves_that_a_symmetry_keeps(name):
+    """Where exact_tiles names tiles, decode_actions commutes with the symmetry on them; every board has such tiles under
+    the flips, and under the plain transpose none."""
+    c = GYM_CASES[name]
+    w, h = c["w"], c["h"]
+    for s in c["syms"]:
+        ok = np.flatnonzero(S.exact_tiles(s, h, w))
+        assert len(ok) >= (0 if s == 4 else 2), (s, len(ok))
+        a = 5 * ok + 4
+        fx, fy, tx, ty, half, _ = G.decode_actions(a, w, h)
+        gx, gy, ux, uy, half2, _ = G.decode_actions(S.transform_actions(a, s, h, w), w, h)
+        assert half.all() and half2.all()
+        assert np.array_equal(np.stack(S.map_xy(s, fx, fy, w, h)), np.stack([gx, gy])) and np.array_equal(np.stack(S.map_xy(s, tx, ty, w, h)), np.stack([ux, uy]))
+
+
+@pytest.mark.parametrize("name", list(GYM_CASES))
+def test_reference_gym_env_is_equivariant_on_the_gym_cases(name):
+    """The numpy restatement of GeneralsEnv over the oracle, the other seat idle, on the device test's boards and draws: it
+    obeys the property, and the run holds half moves, a truncation, a terminal reward and enough pairs compared to the end."""
+    from test_vector_env import OracleBackedEngine
+    orb = GymOrbit(name)
+    env = G.NumpyReferenceVecEnv(OracleBackedEngine(orb.B, orb.W, orb.H, 2), orb.B, orb.W, orb.H, max_players=2, max_turns=GYM_MAX_TURNS, seed=3,
+                                 board_pool=16)
+    env.reset()
+    obs, info = env.install_boards(*orb.boards)
+    idle = np.zeros((orb.B, 2), O.ACTION_DTYPE)
+
+    def step(actions):
+        obs, reward, terminated, truncated, info = env.step(actions[:, 0], other_actions=idle)
+        return obs[:, None], reward[:, None], terminated, truncated, info["valid_actions_mask"][:, None], info["turn"]
+
+    seen = drive_gym(orb, step, obs[:, None], info["valid_actions_mask"][:, None], 1)
+    assert_gym_floors(seen, name)
