@@ -175,6 +175,13 @@ int32_t gvec_expand_experience_records(int32_t device, void* hip_stream, const i
     set_err("gvec_expand_experience_records: layout {%d, %d, %d, %d, ., %d} is not one gvec_experience_record_layout produces", rd, mp, fd, ns, stride);
     return GVEC_E_INVALID;
   }
+  // expand_records_kernel reads a record as dwords and writes a tile's four mask bytes (and an absent slot's zeros) as one
+  // dword; every slot of action_mask is 4 * stride bytes, so the array's own alignment decides
+  if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(action_mask)) & 3u) {
+    set_err("gvec_expand_experience_records: records and action_mask must be 4-byte aligned (%s is not)",
+            (reinterpret_cast<uintptr_t>(records) & 3u) ? "records" : "action_mask");
+    return GVEC_E_INVALID;
+  }
   if (n == 0) return GVEC_OK;
   ON_DEVICE(device, launch_expand_records(records, n, layout8, state, next_state, action_mask, meta, reinterpret_cast<hipStream_t>(hip_stream)));
 }
@@ -200,6 +207,10 @@ int32_t gvec_observe(gvec_handle* h, int32_t player, float* out, int32_t mem) {
 
 int32_t gvec_serializer_mask(gvec_handle* h, uint8_t* bits, int32_t mem) {
   if (!h || !bits) return GVEC_E_INVALID;
+  if (mem == GVEC_MEM_DEVICE && (reinterpret_cast<uintptr_t>(bits) & 3u)) {   // the kernel stores the planes as dwords
+    set_err("gvec_serializer_mask: a device bits array must be 4-byte aligned");
+    return GVEC_E_INVALID;
+  }
   if (h->sharded()) {
     const size_t mb = (size_t)h->maxp * h->mask_bytes;
     return sharded::fan_host(h, mem, "gvec_serializer_mask", [=](gvec_handle* c, int begin, int) { return gvec_serializer_mask(c, bits + begin * mb, GVEC_MEM_HOST); });

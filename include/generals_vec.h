@@ -244,7 +244,10 @@ int32_t gvec_build_board_pool(gvec_handle* h, int32_t pool_size, uint64_t seed,
  * d = 0 up, 1 right, 2 down, 3 left (rules/legal_moves.go:13-18,66): bit t (LSB
  * first) of plane d = Engine.GetLegalActionMask(p)[t*4 + d], t = y*W + x.  (Go's
  * []bool index order is a transpose of this: see INTEGRATION.md for the 3-line
- * unpack.)  ABI version 2: version 1 packed bit i = mask[i]. */
+ * unpack.)  ABI version 2: version 1 packed bit i = mask[i].
+ * Alignment with GVEC_MEM_DEVICE: none beyond the types'.  The kernel writes the masks into the handle's own resident
+ * buffer (16-byte aligned; gvec_device_buffer) and legal_bits receives a device-to-device copy of it, so a byte array
+ * may sit at any address; the same holds for gvec_legal_mask. */
 int32_t gvec_step(gvec_handle* h, const gvec_action* actions, int32_t* err,
                   uint8_t* legal_bits, int32_t mem);
 
@@ -336,7 +339,11 @@ int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_
  * gvec_serializer_mask    = Serializer.GenerateActionMask (serializer.go:112-176):
  *                           same packing as gvec_legal_mask but the serializer's
  *                           semantics (board owner, army >= 2, no Alive check) and
- *                           direction order 0 up, 1 down, 2 left, 3 right. */
+ *                           direction order 0 up, 1 down, 2 left, 3 right.
+ * Alignment with GVEC_MEM_DEVICE: gvec_observe writes `out` in place and needs only the 4 bytes of a float (it picks
+ * aligned 256-byte store windows, or per-slot stores, per env from the address and the env's own W*H).
+ * gvec_serializer_mask writes `bits` in place as dwords: the array must be 4-BYTE aligned although it is declared as
+ * bytes, and one that is not is refused with GVEC_E_INVALID and a gvec_last_error message before any launch. */
 int32_t gvec_experience_begin(gvec_handle* h);
 /* The same snapshot for envs [env_begin, env_begin+n) only (a consumer that samples a slice of the batch). */
 int32_t gvec_experience_begin_range(gvec_handle* h, int32_t env_begin, int32_t n);
@@ -378,7 +385,11 @@ int32_t gvec_experience_records(gvec_handle* h, const gvec_action* actions, int3
  *   meta               int32   [n][MP][8]: present (1: the record is valid and player p acted - only then the slot
  *                      holds an experience, else it is zeroed), env id, player id, currState.Turn, action index, reward
  *                      (float32 bits), done, W | H << 8.
- * Enqueued on hip_stream (may be NULL) of `device`; device pointers only.  experience.py: expand_records_device. */
+ * Enqueued on hip_stream (may be NULL) of `device`; device pointers only.  experience.py: expand_records_device.
+ * Alignment: state / next_state / meta need what their types say (4 bytes; wider stores are chosen per slot from the
+ * address).  `records` and `action_mask` must be 4-BYTE aligned although they are declared as bytes: a record is read as
+ * dwords, and a tile's four mask bytes - as an absent slot's zeros - leave as one dword.  A pointer that is not is refused
+ * with GVEC_E_INVALID and a gvec_last_error message before anything touches a device. */
 int32_t gvec_expand_experience_records(int32_t device, void* hip_stream, const int32_t* layout8, const void* records, int32_t n,
                                        float* state, float* next_state, uint8_t* action_mask, int32_t* meta);
 /* on != 0: per-turn rollouts (gvec_rollout fused = 0) store the agent's moves in the handle's action buffer and the
@@ -427,7 +438,11 @@ int32_t gvec_stream_deltas_packed(gvec_handle* h, int32_t player, int32_t full_t
  *   gym_actions[B] (indices into Discrete(board_size*5)) against `mask` (the last gvec_gym_observe's), writes
  *   the player's move into actions[B][max_players] (the other players' slots are kept: fill them first, e.g.
  *   with gvec_agent_actions), marks an env whose action is refused GVEC_ACT_SKIP_ENV and a `resetting` env
- *   GVEC_ACT_RESET_ENV; played / invalid / error [B] 0/1 outputs (any may be NULL). */
+ *   GVEC_ACT_RESET_ENV; played / invalid / error [B] 0/1 outputs (any may be NULL).
+ * Alignment (every gvec_gym_* call that writes obs / mask, the *_players ones included): obs needs the 4 bytes of a
+ *   float, mask may sit at ANY byte address - slots of a larger buffer at element offsets are fine.  The kernels pick
+ *   their store code per slot from the address and tile_stride (aligned 256-byte windows, 16-byte quads or one store per
+ *   tile for obs; 16-byte, 4-byte or byte stores for mask); every choice writes the same bytes. */
 int32_t gvec_gym_observe(gvec_handle* h, int32_t player, const int64_t* turn_count, int32_t max_turns,
                          float* obs, uint8_t* mask, double* reward, uint8_t* done, int8_t* winner);
 /* gvec_gym_observe plus the bookkeeping GeneralsEnv.step wraps around it (generals_env.py:226-259), in the same

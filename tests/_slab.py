@@ -11,13 +11,15 @@ GUARD = 256          # bytes before the first and behind the last buffer
 GAP = 64             # bytes, at the least, between two groups
 
 
-def place(sizes, groups, shift=None):
+def place(sizes, groups, shift=None, align=16):
     """Byte offsets {name: offset} and the slab's size.  sizes {name: bytes}; groups is a sequence of tuples of names: the
     buffers of a group lie flush against each other in the order given, groups lie GAP bytes or more apart.  A group starts
-    on a 16-byte boundary plus shift[its first name] bytes."""
+    on an `align`-byte boundary (16; a multiple of it for a test that places buffers inside a 256-byte line) plus
+    shift[its first name] bytes."""
+    assert align % 16 == 0 and GUARD % 16 == 0
     offsets, cursor = {}, GUARD
     for group in groups:
-        cursor = -(-cursor // 16) * 16 + (shift or {}).get(group[0], 0)
+        cursor = -(-cursor // align) * align + (shift or {}).get(group[0], 0)
         for name in group:
             offsets[name] = cursor
             cursor += sizes[name]
@@ -27,9 +29,9 @@ def place(sizes, groups, shift=None):
 
 
 class Slab:
-    def __init__(self, sizes, groups, shift=None):
-        self.sizes = dict(sizes)
-        self.offsets, self.nbytes = place(sizes, groups, shift)
+    def __init__(self, sizes, groups, shift=None, align=16):
+        self.sizes, self.align = dict(sizes), align
+        self.offsets, self.nbytes = place(sizes, groups, shift, align)
         self.image = np.full(self.nbytes, FILL, np.uint8)        # what the device holds before the launch
         self.dev = None
 
@@ -41,8 +43,13 @@ class Slab:
         image[self.offsets[name]:self.offsets[name] + raw.size] = raw
 
     def upload(self, torch, device):
-        self.dev = torch.from_numpy(self.image.copy()).to(device)
-        assert self.dev.data_ptr() % 16 == 0
+        """One allocation with `align` spare bytes, sliced to a start on an `align`-byte boundary: a buffer's address is
+        that boundary plus its offset, whatever the allocator returned."""
+        raw = torch.empty(self.nbytes + self.align, dtype=torch.uint8, device=device)
+        start = -raw.data_ptr() % self.align
+        self.dev = raw[start:start + self.nbytes]
+        self.dev.copy_(torch.from_numpy(self.image))
+        assert self.dev.data_ptr() % self.align == 0
         return self
 
     def at(self, name):

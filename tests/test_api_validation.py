@@ -73,6 +73,16 @@ def test_expand_experience_records(L):
     _rejected(L, L.gvec_expand_experience_records(0, None, bad[0], p, 0, p, p, p, p), "layout {")   # the layout before n == 0
     assert L.gvec_expand_experience_records(0, None, ok, p, 0, p, p, p, p) == OK
     assert L.gvec_expand_experience_records(0, None, _layout(rd_extra=3), p, 0, p, p, p, p) == OK
+    # the kernel moves a record's dwords and a tile's four mask bytes as one dword: 4-byte alignment, which the types do not give
+    for off in (1, 2, 3):
+        q = C.c_void_p(P + off)
+        _rejected(L, L.gvec_expand_experience_records(0, None, ok, p, 4, p, p, q, p), "must be 4-byte aligned (action_mask is not)")
+        _rejected(L, L.gvec_expand_experience_records(0, None, ok, q, 4, p, p, p, p), "must be 4-byte aligned (records is not)")
+        _rejected(L, L.gvec_expand_experience_records(0, None, ok, p, 0, p, p, q, p), "action_mask is not")   # before n == 0
+    assert L.gvec_expand_experience_records(0, None, ok, p, 0, p, p, C.c_void_p(P + 4), p) == OK               # any dword will do
+    # order: NULL, layout, alignment
+    _rejected_silently(L, lambda: L.gvec_expand_experience_records(0, None, ok, p, 4, None, p, C.c_void_p(P + 1), p))
+    _rejected(L, L.gvec_expand_experience_records(0, None, bad[0], p, 4, p, p, C.c_void_p(P + 1), p), "layout {")
 
 
 # ---- gvec_pool_collect -----------------------------------------------------------------------------------------------
