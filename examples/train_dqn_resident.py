@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from generalsreinforcementlearning_amd.env_pool import ParallelVecEnvPool
 from generalsreinforcementlearning_amd.q_targets import categorical_target, double_q_target
+from generalsreinforcementlearning_amd.reward import RewardConfig
 from generalsreinforcementlearning_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from generalsreinforcementlearning_amd.symmetry import augment_transition
 from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
@@ -92,10 +93,22 @@ def main(argv=None):
     ap.add_argument("--double", action="store_true", help="Double DQN: the online network picks the next action among the legal ones")
     ap.add_argument("--categorical", action="store_true", help="C51: a distribution over --atoms returns per action, masked Double targets")
     ap.add_argument("--atoms", type=int, default=51)
-    ap.add_argument("--v-min", type=float, default=-110.0, help="the support's bounds: the default covers the env's terminal +-100")
-    ap.add_argument("--v-max", type=float, default=110.0)
+    ap.add_argument("--v-min", type=float, default=None,
+                    help="the support's bounds; default: -110 / 110 for --reward gym (the env's terminal +-100), else the config's "
+                         "lose_game / win_game widened by a tenth and by invalid_action")
+    ap.add_argument("--v-max", type=float, default=None)
+    ap.add_argument("--reward", choices=("gym", "go", "sparse"), default="gym",
+                    help="gym: GeneralsEnv's own reward; go: the reference's DefaultRewardConfig, clipped, -0.1 for a refused action; "
+                         "sparse: +-1 on the last step of a game and nothing else (RewardConfig)")
     ap.add_argument("--augment", action="store_true", help="a random board symmetry per sampled row (mirrors, quarter turns)")
     a = ap.parse_args(argv)
+    reward_config = {"gym": None, "go": RewardConfig.clipped(), "sparse": RewardConfig.sparse()}[a.reward]
+    if reward_config is None:
+        lo, hi = -110.0, 110.0
+    else:      # an episode's return is dominated by its last step: the outcome, a margin for the shaped steps before it
+        lo = 1.1 * min(reward_config.lose_game, -reward_config.win_game) - abs(reward_config.invalid_action)
+        hi = 1.1 * max(reward_config.win_game, -reward_config.lose_game) + abs(reward_config.invalid_action)
+    a.v_min, a.v_max = (lo if a.v_min is None else a.v_min), (hi if a.v_max is None else a.v_max)
 
     torch.manual_seed(a.seed)
     dev = torch.device("cuda", 0)
@@ -124,7 +137,7 @@ def main(argv=None):
     else:
         buf = DeviceReplayBuffer(a.buffer_size, n_step=a.n_step, gamma=a.gamma)
     pool = ParallelVecEnvPool(B, lambda n: GeneralsVecEnv(n, board_width=a.board, board_height=a.board, max_players=2, max_turns=a.max_steps_per_episode,
-                                                         seed=a.seed, device_outputs=True),
+                                                         seed=a.seed, device_outputs=True, reward_config=reward_config),
                               policy, buf, max_steps_per_episode=a.max_steps_per_episode, seed=a.seed, batched_actions=True)
     sym_gen = torch.Generator(device=dev)
     sym_gen.manual_seed(a.seed)
@@ -186,6 +199,8 @@ def main(argv=None):
         out["targets"] = f"categorical{a.atoms}" if a.categorical else "double" if a.double else "masked"
     if a.augment:
         out["augment"] = True
+    if reward_config is not None:
+        out["reward"], out["v_min"], out["v_max"] = a.reward, a.v_min, a.v_max
     pool._env.close()
     print(json.dumps(out))
     return out

@@ -49,6 +49,7 @@ from generalsreinforcementlearning_amd.arena import Arena, torch_policy
 from generalsreinforcementlearning_amd.features import NUM_STRATEGIC_FEATURES, strategic_features
 from generalsreinforcementlearning_amd.memory import NUM_MEMORY_PLANES, ObservationMemory, remembered_observation
 from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead
+from generalsreinforcementlearning_amd.reward import RewardConfig
 from generalsreinforcementlearning_amd.rollout import SelfPlayRolloutBuffer
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
 
@@ -97,6 +98,9 @@ def main(argv=None):
     ap.add_argument("--arena-episodes", type=int, default=2, metavar="k", help="finished games per arena board")
     ap.add_argument("--arena-envs", type=int, default=256, help="boards of the arena's own env")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the final network (examples/evaluate_arena.py loads it)")
+    ap.add_argument("--reward", choices=("gym", "go", "sparse"), default="gym",
+                    help="gym: GeneralsEnv's own reward; go: the reference's DefaultRewardConfig, clipped, -0.1 for a refused action; "
+                         "sparse: +-1 on the last step of a game and nothing else (RewardConfig)")
     a = ap.parse_args(argv)
     if a.arena_every > 0 and a.memory:
         ap.error("--arena-every cannot rate a --memory network: an arena entrant is a function of the observation alone")
@@ -117,8 +121,9 @@ def main(argv=None):
 
     opt = torch.optim.Adam(net.parameters(), lr=a.lr)
     start = [p.detach().clone() for p in net.parameters()]
+    reward_config = {"gym": None, "go": RewardConfig.clipped(), "sparse": RewardConfig.sparse()}[a.reward]
     env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
-                                 seed=a.seed, device_outputs=True)
+                                 seed=a.seed, device_outputs=True, reward_config=reward_config)
     B, L = env.num_envs, env.num_learners
     memory = ObservationMemory((B, L), a.board, a.board, device=dev) if a.memory else None
     buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda, memory=memory)
@@ -211,6 +216,8 @@ def main(argv=None):
         out.append(row)
     moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), start))
     result = {"iterations": out, "bad_actions": head.bad_actions, "rejected": int(buf.rejected.item()), "parameter_change": moved}
+    if reward_config is not None:
+        result["reward"] = a.reward
     if a.save:
         torch.save({"model": net.state_dict(), "board": a.board, "players": a.players, "channels": channels, "features": a.features,
                     "memory": a.memory}, a.save)

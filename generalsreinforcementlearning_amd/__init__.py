@@ -9,6 +9,7 @@ from ._lib import GvecError, lib, lib_path, load  # noqa: F401
 from .vec_engine import (ACTION_DTYPE, ACT_HALF, ACT_VALID, ERR_NAMES, TILE_CITY, TILE_GENERAL, TILE_MOUNTAIN,  # noqa: F401
                          TILE_NORMAL, VecEngine, make_actions, unpack_legal_bits)
 from .env_state import VecEnvState  # noqa: F401
+from .reward import REWARD_TERMS, RewardConfig  # noqa: F401
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
 from .rollout import SelfPlayRolloutBuffer  # noqa: F401
 from .policy_head import MaskedCategoricalHead  # noqa: F401
@@ -19,7 +20,7 @@ from .symmetry import apply_symmetry, augment_transition, inverse_symmetry, num_
 from .arena import (Arena, ArenaResult, EpisodeTally, balanced_seating, expected_score, fit_elo, random_policy,  # noqa: F401
                     torch_policy)
 
-__all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState",
+__all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState", "RewardConfig", "REWARD_TERMS",
            "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "strategic_features",
            "NUM_STRATEGIC_FEATURES", "STRATEGIC_FEATURE_NAMES", "ObservationMemory", "remembered_observation", "NUM_MEMORY_PLANES",
            "MEMORY_PLANE_NAMES", "valid_actions_mask_from_observation", "double_q_target", "categorical_target",

@@ -33,9 +33,11 @@ class GymVecEnvBase:
         self._t = torch
 
     def __init__(self, learner_shape, feat_cap, num_envs, board_width, board_height, max_players, fog_of_war, max_turns, seed, device,
-                 board_pool, device_outputs):
-        """After _require_gpu().  feat_cap: what _feature_option returned (a subclass calls it before any other check)."""
+                 board_pool, device_outputs, reward_c=None):
+        """After _require_gpu().  feat_cap: what _feature_option returned (a subclass calls it before any other check);
+        reward_c: what _reward_option returned."""
         torch = self._t
+        self._reward_c, self._reward_bits = reward_c, None
         self._feat_cap, self._feat_bufs, self._feat_flip = feat_cap, None, 0
         self.num_envs = num_envs
         self.board_width, self.board_height = board_width, board_height
@@ -67,6 +69,9 @@ class GymVecEnvBase:
         self._d_step = [{"reward": z(per, torch.float64), **{f: z(per, torch.bool) for f in self._STEP_FLAGS},
                          "winner": z(B, torch.int8), "turn": z(B, torch.int64), "terminated": z(B, torch.bool),
                          "truncated": z(B, torch.bool), "needs_reset": z(B, torch.bool)} for _ in range(3)]
+        if reward_c is not None:           # reward_config: the launch's float32 rewards and the terms they are made of, per buffer set
+            for b in self._d_step:
+                b["reward_f32"], b["reward_terms"] = z(per, torch.float32), z(per + (8,), torch.int32)
         self._step_no = 0
         self._arg_cache = {}
         self.last_actions = None
@@ -160,6 +165,38 @@ class GymVecEnvBase:
             self._feat_bufs = [self._t.empty(shape, dtype=self._t.float32, device=self._dev) for _ in range(2)]
         self._feat_flip ^= 1
         info["strategic_features"] = strategic_features(obs, cap=self._feat_cap, out=self._feat_bufs[self._feat_flip])
+        return info
+
+    # ---- reward_config (reward.py) ---------------------------------------------------------------------------
+    @staticmethod
+    def _reward_option(reward_config):
+        """The gvec_reward_config of the option, or None when it is off.  Checked before anything touches a device."""
+        if reward_config is None:
+            return None
+        from .reward import RewardConfig
+        if not isinstance(reward_config, RewardConfig):
+            raise ValueError(f"reward_config must be a RewardConfig or None, not {type(reward_config).__name__}")
+        return reward_config.to_c()
+
+    def _reward_begin(self):
+        """Before a step's launch(es): the reward-only snapshot of the state the step starts from.  Off: nothing."""
+        if self._reward_c is None:
+            return
+        if self._reward_bits is None:
+            self._reward_bits = sum(1 << int(p) for p in self._learner_ids())
+        self.engine.experience_begin(rewards_only=True)
+
+    def _reward_finish(self, out, info):
+        """After a step's launch(es), on the same stream: CalculateRewardWithConfig of every learner against the snapshot, with
+        the step's own `invalid` flags; the step's float64 reward buffer is overwritten with the float32 values and
+        info["reward_terms"] (device mode) is the int32 [..., 8] they are made of.  Off: nothing is launched."""
+        if self._reward_c is None:
+            return info
+        self.engine.experience_rewards_device(self._reward_c, self._reward_bits, out["invalid"].data_ptr(), out["reward_f32"].data_ptr(),
+                                              out["reward_terms"].data_ptr())
+        out["reward"].copy_(out["reward_f32"])
+        if self.device_outputs:
+            info["reward_terms"] = out["reward_terms"]
         return info
 
     # ---- gym API ------------------------------------------------------------------------------------

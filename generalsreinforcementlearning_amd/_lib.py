@@ -128,6 +128,15 @@ class CategoricalTargetArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("next_obs", "logits_eval", "logits_select", "reward", "discount", "done", "m", "next_action")])
 
 
+class RewardConfigC(C.Structure):
+    """gvec_reward_config (include/generals_vec.h); reward.RewardConfig is the Python form."""
+    _fields_ = ([(n, C.c_float) for n in ("win_game", "lose_game", "capture_city", "lose_city", "capture_general", "lose_general",
+                                          "territory", "army", "army_advantage", "invalid_action")]
+                + [("flags", C.c_uint32), ("reserved", C.c_uint32)])
+
+
+REWARD_CLIP = 1          # GVEC_REWARD_CLIP
+
 SYM_MAX_PLANE_SETS = 4   # GVEC_SYM_MAX_PLANE_SETS
 
 
@@ -198,6 +207,9 @@ SYMBOLS = {
     "gvec_experience_begin": (_i32, [_vp]),
     "gvec_experience_begin_range": (_i32, [_vp, _i32, _i32]),
     "gvec_experience_rewards": (_i32, [_vp, _vp, _vp, _i32]),
+    "gvec_reward_config_default": (_i32, [C.POINTER(RewardConfigC)]),
+    "gvec_experience_begin_rewards": (_i32, [_vp]),
+    "gvec_experience_rewards_config": (_i32, [_vp, C.POINTER(RewardConfigC), C.c_uint32, _vp, _vp, _vp, _vp, _i32]),
     "gvec_experience_record_layout": (_i32, [_vp, C.POINTER(C.c_int32)]),
     "gvec_experience_record_bytes": (_i32, [_vp]),
     "gvec_experience_records": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

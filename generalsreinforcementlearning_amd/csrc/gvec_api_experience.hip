@@ -1,6 +1,8 @@
 // gvec_api_experience.hip — what a learner reads off a handle: experience snapshots, rewards and records (and their
 // expansion), observations, the serializer's mask and the experience stream's deltas.  Host only (gvec_handle.hpp); the
 // kernels are in gvec_experience.hip and gvec_stream.hip.
+#include <cmath>
+
 #include "gvec_handle.hpp"
 
 static ExperienceArgs exp_args(gvec_handle* h) {
@@ -103,6 +105,110 @@ int32_t gvec_experience_rewards(gvec_handle* h, float* rewards, uint8_t* done, i
   RET_IF(stage_out(bd, done, B, mem, &a.done));
   HIPCHK(launch_rewards(h->var, a, h->stream));
   RET_IF(copy_out(h, br, rewards, B * h->maxp, mem));
+  RET_IF(copy_out(h, bd, done, B, mem));
+  if (mem == GVEC_MEM_HOST) HIPCHK(hipStreamSynchronize(h->stream));
+  return GVEC_OK;
+}
+
+int32_t gvec_reward_config_default(gvec_reward_config* cfg) {
+  if (!cfg) return null_args("gvec_reward_config_default");
+  *cfg = gvec_reward_config{};
+  cfg->win_game = 1.0f;           // DefaultRewardConfig, rewards.go:23-37
+  cfg->lose_game = -1.0f;
+  cfg->capture_city = 0.1f;
+  cfg->lose_city = -0.1f;
+  cfg->capture_general = 0.5f;
+  cfg->lose_general = -0.5f;
+  cfg->territory = 0.01f;         // TerritoryGained (TerritoryLost is never read)
+  cfg->army = 0.001f;             // ArmyGained (ArmyLost is never read)
+  cfg->army_advantage = 0.05f;
+  return GVEC_OK;
+}
+
+int32_t gvec_experience_begin_rewards(gvec_handle* h) {
+  if (!h) return null_args("gvec_experience_begin_rewards");
+  if (h->sharded()) return sharded::fan(h, [](gvec_handle* c, int, int) { return gvec_experience_begin_rewards(c); });
+  if (h->cfg.num_envs == 0) return GVEC_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RET_IF(ensure_snapshots(h));
+  ExperienceArgs a = exp_args(h);
+  a.env_begin = 0;
+  HIPCHK(launch_snapshot_rewards(h->var, a, h->stream));
+  return GVEC_OK;
+}
+
+int32_t gvec_experience_rewards_config(gvec_handle* h, const gvec_reward_config* cfg, uint32_t players, const uint8_t* invalid, float* rewards,
+                                       int32_t* terms, uint8_t* done, int32_t mem) {
+  static const char* fn = "gvec_experience_rewards_config";
+  // everything that can be said of the arguments alone comes first: it holds without a handle and without a device
+  if (!cfg) {
+    set_err("%s: cfg is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  const float w[10] = {cfg->win_game, cfg->lose_game, cfg->capture_city, cfg->lose_city, cfg->capture_general, cfg->lose_general,
+                       cfg->territory, cfg->army, cfg->army_advantage, cfg->invalid_action};
+  static const char* names[10] = {"win_game", "lose_game", "capture_city", "lose_city", "capture_general", "lose_general",
+                                  "territory", "army", "army_advantage", "invalid_action"};
+  for (int k = 0; k < 10; ++k)
+    if (!std::isfinite(w[k])) {
+      set_err("%s: %s is not finite", fn, names[k]);
+      return GVEC_E_INVALID;
+    }
+  if (cfg->reserved != 0u) {
+    set_err("%s: reserved must be 0", fn);
+    return GVEC_E_INVALID;
+  }
+  if (cfg->flags & ~GVEC_REWARD_CLIP) {
+    set_err("%s: unknown flag bits 0x%x", fn, cfg->flags & ~GVEC_REWARD_CLIP);
+    return GVEC_E_INVALID;
+  }
+  if (!rewards && !terms && !done) {
+    set_err("%s: rewards, terms and done are all NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  if (players >> GVEC_MAX_PLAYERS) {
+    set_err("%s: players 0x%x names a seat at or above GVEC_MAX_PLAYERS", fn, players);
+    return GVEC_E_INVALID;
+  }
+  if (!h) {
+    set_err("%s: the handle is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  if (players >> h->maxp) {
+    set_err("%s: players 0x%x names a seat at or above max_players = %d", fn, players, h->maxp);
+    return GVEC_E_INVALID;
+  }
+  const uint32_t bits = players ? players : ((1u << h->maxp) - 1u);
+  const size_t K = (size_t)__builtin_popcount(bits);
+  if (h->sharded())
+    return sharded::fan_host(h, mem, fn, [=](gvec_handle* c, int begin, int) {
+      return gvec_experience_rewards_config(c, cfg, players, invalid ? invalid + begin * K : nullptr, rewards ? rewards + begin * K : nullptr,
+                                            terms ? terms + begin * K * 8 : nullptr, done ? done + begin : nullptr, GVEC_MEM_HOST);
+    });
+  if (!h->d_snap) {
+    set_err("%s without a preceding gvec_experience_begin or gvec_experience_begin_rewards", fn);
+    return GVEC_E_INVALID;
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t B = (size_t)h->cfg.num_envs;
+  Stage st(h);
+  DevBuf &bi = st.next(), &br = st.next(), &bt = st.next(), &bd = st.next();
+  RewardArgs a = state_args<RewardArgs>(h);
+  a.snap = h->d_snap;
+  a.cfg = *cfg;
+  a.players = bits;
+  a.nk = (int32_t)K;
+  a.num_envs = h->cfg.num_envs;
+  a.fd = h->fd;
+  a.row_dw = h->row_dw;
+  a.snap_dw = h->snap_dw;
+  RET_IF(stage_in(h, bi, invalid, B * K, mem, &a.invalid));
+  RET_IF(stage_out(br, rewards, B * K, mem, &a.rewards));
+  RET_IF(stage_out(bt, terms, B * K * 8, mem, &a.terms));
+  RET_IF(stage_out(bd, done, B, mem, &a.done));
+  HIPCHK(launch_rewards_config(h->var, a, h->stream));
+  RET_IF(copy_out(h, br, rewards, B * K, mem));
+  RET_IF(copy_out(h, bt, terms, B * K * 8, mem));
   RET_IF(copy_out(h, bd, done, B, mem));
   if (mem == GVEC_MEM_HOST) HIPCHK(hipStreamSynchronize(h->stream));
   return GVEC_OK;

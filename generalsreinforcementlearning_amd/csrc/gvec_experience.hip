@@ -138,6 +138,121 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rewards_kernel(Experienc
   if (A.done && lane == 0) A.done[i] = (uint8_t)(over ? 1 : 0);
 }
 
+// The snapshot of a consumer that wants REWARDS only (gvec_experience_begin_rewards): the own() planes and the tail of
+// SnapLayout, in the same buffer - MAXP * fd + 2 * MAXP + 2 dwords per env (248 bytes at 20x20 4P) instead of the whole
+// layout (3.7 KB).  The vis / mask / army sections keep whatever an earlier full snapshot left there: experience records
+// need snapshot_kernel.
+template <int MAXP, int NSLOT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void snapshot_rewards_kernel(ExperienceArgs A) {
+  using B = Board<MAXP, NSLOT>;
+  const int lane = lane_id();
+  const int i = wave_item();
+  if (i >= A.num_envs) return;
+  const int env = A.env_begin + i;
+  B b;
+  load_board(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd);
+  const SnapLayout<MAXP, NSLOT> L{A.fd};
+  uint32_t* sn = A.snap + (size_t)env * A.snap_dw;
+  uint32_t tail = 0u;  // as snapshot_kernel: lane p territory, MAXP+p armies, 2*MAXP turn, +1 W|H<<8
+#pragma unroll
+  for (int p = 0; p < MAXP; ++p) {
+    if (lane < A.fd) sn[L.own() + p * A.fd + lane] = b.own[p];
+    const int32_t terr = b.count(b.own[p]), arm = b.army_sum(b.own[p]);
+    tail = (lane == p) ? (uint32_t)terr : tail;
+    tail = (lane == MAXP + p) ? (uint32_t)arm : tail;
+  }
+  tail = (lane == 2 * MAXP) ? (uint32_t)b.turn : tail;
+  tail = (lane == 2 * MAXP + 1) ? ((uint32_t)b.W | ((uint32_t)b.H << 8)) : tail;
+  if (lane < 2 * MAXP + 2) sn[L.tail() + lane] = tail;
+}
+
+// CalculateRewardWithConfig (rewards.go:45-85) with the caller's weights (RewardArgs::cfg: kernel arguments, wave-uniform
+// scalar loads), for the players of A.players; player p's column is its rank among them.  The same float32 sequence as
+// compute_rewards above - with gvec_reward_config_default the two agree bit for bit - then NormalizeReward (:215-223) when
+// asked for, the "no predecessor" zero, and invalid_action on top.  Lane k ends with column k's reward, lane 8k + j with term j
+// of column k (K <= 8: one dword per lane), so rewards and terms leave as one coalesced store each.
+template <int MAXP, int NSLOT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rewards_config_kernel(RewardArgs A) {
+  using B = Board<MAXP, NSLOT>;
+  const int lane = lane_id();
+  const int i = wave_item();
+  if (i >= A.num_envs) return;
+  B b;
+  load_board(b, A.hdr + (size_t)i * HDR_DW, A.rows + (size_t)i * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, i), A.fd);
+  const int fd = A.fd;
+  const SnapLayout<MAXP, NSLOT> L{fd};
+  const uint32_t* sn = A.snap + (size_t)i * A.snap_dw;
+  const uint32_t tail = (lane < 2 * MAXP + 2) ? sn[L.tail() + lane] : 0u;
+  const int prev_turn = (int)rdlane(tail, 2 * MAXP);
+  const uint32_t prev_dims = rdlane(tail, 2 * MAXP + 1);
+  const bool comparable = prev_dims == ((uint32_t)b.W | ((uint32_t)b.H << 8)) && b.turn > prev_turn;   // compute_rewards' rule
+  const int na = __builtin_popcount(b.alive);
+  const bool over = na <= 1;                                               // GameState.IsGameOver (state.go:73-82)
+  const int winner = (na == 1) ? (31 - __builtin_clz(b.alive)) : -1;       // GameState.GetWinner (state.go:85-100)
+  uint32_t prev_own[MAXP], prev_any = 0u;
+  int32_t cur_arm[MAXP], total = 0;
+#pragma unroll
+  for (int p = 0; p < MAXP; ++p) {
+    prev_own[p] = (lane < fd) ? sn[L.own() + p * fd + lane] : 0u;
+    prev_any |= prev_own[p];
+    cur_arm[p] = b.army_sum(b.own[p]);
+    total += cur_arm[p];
+  }
+  const gvec_reward_config& c = A.cfg;
+  const bool clip = (c.flags & GVEC_REWARD_CLIP) != 0u;
+  const int j = lane & 7;
+  float rv = 0.0f;
+  int32_t tv = 0;
+#pragma unroll
+  for (int p = 0; p < MAXP; ++p) {
+    if (((A.players >> p) & 1u) == 0u) continue;                            // wave-uniform
+    const int col = __builtin_popcount(A.players & ((1u << p) - 1u));
+    const int d_terr = b.count(b.own[p]) - (int)rdlane(tail, p);            // :59-62
+    const int d_arm = cur_arm[p] - (int)rdlane(tail, MAXP + p);             // :65-68
+    const int c_gain = b.count(b.city & b.own[p] & ~prev_own[p]);           // countCityChanges :110-129
+    const int c_lost = b.count(b.city & prev_own[p] & ~b.own[p]);
+    const int g_gain = b.count(b.gen & b.own[p] & ~prev_own[p] & prev_any); // countGeneralChanges :132-151
+    const int g_lost = b.count(b.gen & prev_own[p] & ~b.own[p]);
+    const int pa = cur_arm[p], ea = total - cur_arm[p];                     // calculateArmyAdvantage :153-175
+    const float adv = (total == 0) ? 0.0f : ((float)(pa - ea) / (float)total);
+    float r = 0.0f;
+    r += (float)d_terr * c.territory;
+    r += (float)d_arm * c.army;
+    r += (float)c_gain * c.capture_city;
+    r += (float)c_lost * c.lose_city;
+    r += (float)g_gain * c.capture_general;
+    r += (float)g_lost * c.lose_general;
+    r += adv * c.army_advantage;
+    int outcome = 0;
+    if (over && winner == p) {                                              // :49-56
+      r = c.win_game;
+      outcome = 1;
+    } else if (over && winner != -1) {
+      r = c.lose_game;
+      outcome = -1;
+    }
+    if (clip) r = (r > 1.0f) ? 1.0f : ((r < -1.0f) ? -1.0f : r);            // NormalizeReward :215-223
+    const bool live = comparable && p < b.P;
+    rv = (lane == col) ? (live ? r : 0.0f) : rv;
+    int32_t t = d_terr;
+    t = (j == 1) ? d_arm : t;
+    t = (j == 2) ? c_gain : t;
+    t = (j == 3) ? c_lost : t;
+    t = (j == 4) ? g_gain : t;
+    t = (j == 5) ? g_lost : t;
+    t = (j == 6) ? outcome : t;
+    t = (j == 7) ? (int32_t)__float_as_uint(adv) : t;
+    tv = ((lane >> 3) == col) ? (live ? t : 0) : tv;
+  }
+  if (lane < A.nk) {
+    const size_t at = (size_t)i * A.nk + lane;
+    if (A.invalid && A.invalid[at] != 0) rv = rv + c.invalid_action;
+    if (A.rewards) A.rewards[at] = rv;
+  }
+  if (A.terms && lane < 8 * A.nk) A.terms[(size_t)i * 8 * A.nk + lane] = tv;
+  if (A.done && lane == 0) A.done[i] = (uint8_t)(over ? 1 : 0);
+}
+
 // One EXPERIENCE RECORD per env transition: everything SimpleCollector.OnStateTransition (internal/experience/
 // collector.go:30-98) puts into the experiencepb.Experience of every player that acted, in compact form -
 // bit-planes and u16 armies instead of 2 x P x [9][H][W] float tensors (3.7 KB instead of 115 KB at 20x20 4P): what a
@@ -512,6 +627,12 @@ hipError_t launch_snapshot(const Variant& v, const ExperienceArgs& a, hipStream_
 }
 hipError_t launch_rewards(const Variant& v, const ExperienceArgs& a, hipStream_t s) {
   return dispatch(v, [&](auto P, auto S) { return launch_waves(rewards_kernel<P, S>, a.num_envs, s, a); });
+}
+hipError_t launch_snapshot_rewards(const Variant& v, const ExperienceArgs& a, hipStream_t s) {
+  return dispatch(v, [&](auto P, auto S) { return launch_waves(snapshot_rewards_kernel<P, S>, a.num_envs, s, a); });
+}
+hipError_t launch_rewards_config(const Variant& v, const RewardArgs& a, hipStream_t s) {
+  return dispatch(v, [&](auto P, auto S) { return launch_waves(rewards_config_kernel<P, S>, a.num_envs, s, a); });
 }
 hipError_t launch_experience_records(const Variant& v, const ExperienceArgs& a, hipStream_t s) {
   return dispatch(v, [&](auto P, auto S) { return launch_waves(experience_record_kernel<P, S>, a.num_envs, s, a); });

@@ -158,6 +158,23 @@ struct ExperienceArgs {
   int32_t num_envs, fd, row_dw, snap_dw, record_dw, pstride, stride, player, env_id_base;
 };
 hipError_t launch_experience_records(const Variant& v, const ExperienceArgs& a, hipStream_t s);
+// gvec_experience_rewards_config: CalculateRewardWithConfig for the K players of `players` (ascending id -> column)
+struct RewardArgs {
+  const uint32_t* hdr;
+  const uint32_t* rows;
+  const uint32_t* army16;
+  const int32_t* army32;
+  const uint32_t* snap;    // [B][snap_dw], as ExperienceArgs
+  const uint8_t* invalid;  // [B][K] or null
+  float* rewards;          // [B][K] or null
+  int32_t* terms;          // [B][K][8] or null
+  uint8_t* done;           // [B] or null
+  gvec_reward_config cfg;
+  uint32_t players;        // never 0 here: the entry point expands "all"
+  int32_t nk, num_envs, fd, row_dw, snap_dw;
+};
+hipError_t launch_snapshot_rewards(const Variant& v, const ExperienceArgs& a, hipStream_t s);
+hipError_t launch_rewards_config(const Variant& v, const RewardArgs& a, hipStream_t s);
 // dwords of one env's snapshot / experience record for this variant
 void experience_layout(const Variant& v, int fd, int* snap_dw, int* record_dw);
 // python/generals_gym on the device

@@ -32,7 +32,8 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
     _INFO_FLAGS = (("invalid", "invalid"), ("error", "error"), ("alive", "alive"))
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, learners=None, fog_of_war=True, max_turns=500,
-                 seed=0, device=0, board_pool=1024, device_outputs=False, strategic_features=False, feature_cap=64):
+                 seed=0, device=0, board_pool=1024, device_outputs=False, strategic_features=False, feature_cap=64,
+                 reward_config=None):
         """learners: the player ids that are learners (None: every player); the others are the on-device random agent.
         device_outputs=True  observation / mask / reward / flags are torch tensors on the GPU; `step` takes a CUDA int64
                              tensor [B, L] of actions.  Every tensor a step returns lives in a buffer that the step AFTER
@@ -43,8 +44,14 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
         strategic_features=True  (needs device_outputs=True) reset / step / copy_envs / restore_state add
                              info["strategic_features"], float32 [B, L, 5, H, W]: features.strategic_features of the observation
                              they return (a step's obs_out slot included), distances capped at feature_cap.  One extra
-                             launch per call."""
+                             launch per call.
+        reward_config=RewardConfig  `step`'s rewards are the reference's CalculateRewardWithConfig with these weights
+                             (reward.py) for every learner, config.invalid_action on top for a refused action, instead of
+                             GeneralsEnv._calculate_reward: two extra launches per step (a reward-only snapshot before it, the
+                             rewards after it) on the same stream.  info["reward_terms"] (device mode): int32 [B, L, 8].
+                             Everything else a step returns is unchanged.  None: today's reward, no extra launch."""
         feat_cap = self._feature_option(strategic_features, feature_cap, device_outputs)
+        reward_c = self._reward_option(reward_config)
         self._require_gpu()
         ids = list(range(max_players)) if learners is None else sorted({int(p) for p in learners})
         if not ids or ids[0] < 0 or ids[-1] >= max_players:
@@ -53,7 +60,7 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
         self.num_learners = len(ids)
         self._bits = sum(1 << p for p in ids)
         super().__init__((len(ids),), feat_cap, num_envs, board_width, board_height, max_players, fog_of_war, max_turns, seed, device,
-                         board_pool, device_outputs)
+                         board_pool, device_outputs, reward_c)
 
     # ---- the device path ---------------------------------------------------------------------------------
     def _learner_ids(self):
@@ -95,6 +102,7 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
             ptrs, obs, out, info = self._slot_args(k, obs_out, mask_out)
         self.last_actions = actions        # the tensor the launch reads (kept alive until the next step)
         self._step_no += 1
+        self._reward_begin()
         # ONE launch: every learner's action decoded against its own view of the resident state, the other players' moves
         # from the on-device agent, the turn (or the re-deal of a `resetting` env), then every learner's observation / mask /
         # reward and the env's flags
@@ -102,7 +110,7 @@ class GeneralsSelfPlayVecEnv(GymVecEnvBase):
               "gvec_gym_step_players")
         self._episode += 1
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
+        return obs, out["reward"], out["terminated"], out["truncated"], self._reward_finish(out, self._add_features(obs, dict(info)))
 
     # ---- gym API ------------------------------------------------------------------------------------
     def step(self, actions, obs_out=None, mask_out=None):

@@ -353,9 +353,14 @@ class VecEngine:
         check(self.L.gvec_rollout_range(self.h, env_begin, n, turns, seed, invalid_permille), "gvec_rollout_range")
 
     # ---- internal/experience side channel (serializer.go, rewards.go) --------------------------------
-    def experience_begin(self):
-        """TurnProcessor.captureStateForExperience (turn_processor.go:116-121): snapshot before the step."""
-        check(self.L.gvec_experience_begin(self.h), "gvec_experience_begin")
+    def experience_begin(self, rewards_only=False):
+        """TurnProcessor.captureStateForExperience (turn_processor.go:116-121): snapshot before the step.
+        rewards_only=True: only what experience_rewards reads of it (gvec_experience_begin_rewards: the ownership planes and
+        the per-player totals, a fifteenth of the bytes at 20x20 4P); experience RECORDS need the full snapshot."""
+        if rewards_only:
+            check(self.L.gvec_experience_begin_rewards(self.h), "gvec_experience_begin_rewards")
+        else:
+            check(self.L.gvec_experience_begin(self.h), "gvec_experience_begin")
 
     def experience_begin_range(self, env_begin, n):
         check(self.L.gvec_experience_begin_range(self.h, env_begin, n), "gvec_experience_begin_range")
@@ -380,8 +385,37 @@ class VecEngine:
     def record_agent_actions(self, on=True):
         check(self.L.gvec_record_agent_actions(self.h, int(bool(on))), "gvec_record_agent_actions")
 
-    def experience_rewards(self):
-        """CalculateReward(prev snapshot, current, player) -> (rewards[B][P] float32, done[B] bool)."""
+    def experience_rewards(self, config=None, players=None, invalid=None, terms=False):
+        """CalculateReward(prev snapshot, current, player) -> (rewards[B][P] float32, done[B] bool).
+        config (reward.RewardConfig): CalculateRewardWithConfig with its weights instead (gvec_experience_rewards_config);
+        players: seat ids or a bit mask -> rewards[B][K], columns in ascending seat id (None: all P); invalid: [B][K] bytes,
+        nonzero = that learner's action was refused -> config.invalid_action on top; terms=True: also the int32 [B][K][8]
+        the value is made of (reward.REWARD_TERMS) -> (rewards, done, terms).  Without any of them the call is
+        gvec_experience_rewards, as before."""
+        if config is None and players is None and invalid is None and not terms:
+            return self._experience_rewards_default()
+        from .reward import RewardConfig
+        cfg = (RewardConfig.go_default() if config is None else config).to_c()
+        mask = 0 if players is None else self._players_mask(players)
+        K = bin(mask).count("1") if mask else self.max_p
+        r = np.zeros((self.B, K), np.float32)
+        d = np.zeros(self.B, np.uint8)
+        t = np.zeros((self.B, K, 8), np.int32) if terms else None
+        inv = None
+        if invalid is not None:
+            inv = np.ascontiguousarray(np.asarray(invalid) != 0, np.uint8)
+            if inv.size != self.B * K:
+                raise ValueError(f"invalid must be [{self.B}, {K}], not {list(inv.shape)}")
+        check(self.L.gvec_experience_rewards_config(self.h, C.byref(cfg), mask, _ptr(inv), _ptr(r), _ptr(t), _ptr(d), MEM_HOST),
+              "gvec_experience_rewards_config")
+        return (r, d.astype(bool), t) if terms else (r, d.astype(bool))
+
+    def experience_rewards_device(self, config_c, players_mask, invalid_ptr, rewards_ptr, terms_ptr=None, done_ptr=None):
+        """gvec_experience_rewards_config on device memory (config_c: RewardConfig.to_c()): enqueued on the engine's stream."""
+        check(self.L.gvec_experience_rewards_config(self.h, C.byref(config_c), int(players_mask), invalid_ptr, rewards_ptr, terms_ptr, done_ptr,
+                                                    MEM_DEVICE), "gvec_experience_rewards_config")
+
+    def _experience_rewards_default(self):
         r = np.zeros((self.B, self.max_p), np.float32)
         d = np.zeros(self.B, np.uint8)
         check(self.L.gvec_experience_rewards(self.h, _ptr(r), _ptr(d), MEM_HOST), "gvec_experience_rewards")

@@ -43,7 +43,7 @@ class GeneralsVecEnv(GymVecEnvBase):
 
     def __init__(self, num_envs, board_width=15, board_height=15, max_players=2, fog_of_war=True, max_turns=500,
                  seed=0, device=0, board_pool=1024, device_outputs=False, opponent="random", opponent_random_permille=0,
-                 strategic_features=False, feature_cap=64):
+                 strategic_features=False, feature_cap=64, reward_config=None):
         """device_outputs=True  observation / mask / reward / flags are torch tensors on the GPU; `step` takes a CUDA int64
                              tensor of actions: no board state crosses PCIe, a step is one kernel launch.  Every tensor a
                              step returns lives in a buffer that the step AFTER NEXT reuses.
@@ -56,15 +56,21 @@ class GeneralsVecEnv(GymVecEnvBase):
         step(actions, other_actions=...) overrides either choice for that step.
         strategic_features=True  (needs device_outputs=True) reset / step / copy_envs / restore_state add
                              info["strategic_features"], float32 [B, 5, H, W]: features.strategic_features of the observation
-                             they return, distances capped at feature_cap.  One extra launch per call."""
+                             they return, distances capped at feature_cap.  One extra launch per call.
+        reward_config=RewardConfig  `step`'s reward is the reference's CalculateRewardWithConfig with these weights
+                             (reward.py) instead of GeneralsEnv._calculate_reward: two extra launches per step (a reward-only
+                             snapshot before it, the rewards after it) on the same stream; a refused action - which this env
+                             does not play - yields exactly config.invalid_action.  info["reward_terms"] (device mode):
+                             int32 [B, 8].  Everything else a step returns is unchanged.  None: today's reward, no extra launch."""
         feat_cap = self._feature_option(strategic_features, feature_cap, device_outputs)
+        reward_c = self._reward_option(reward_config)
         if opponent not in ("random", "bot"):
             raise ValueError(f"opponent must be 'random' or 'bot', not {opponent!r}")
         if not 0 <= int(opponent_random_permille) <= 1000:
             raise ValueError("opponent_random_permille must be in [0, 1000]")
         self._require_gpu()
         super().__init__((), feat_cap, num_envs, board_width, board_height, max_players, fog_of_war, max_turns, seed, device,
-                         board_pool, device_outputs)
+                         board_pool, device_outputs, reward_c)
         self.player_id = 0  # "RL_Agent" joins first (generals_env.py:163-169)
         self.opponent, self.opponent_random_permille = opponent, int(opponent_random_permille)
         self._acts = None
@@ -86,6 +92,7 @@ class GeneralsVecEnv(GymVecEnvBase):
     def _step_device(self, actions):
         e = self.engine
         self.last_actions = actions = self._as_actions(actions)        # the tensor the launch reads (kept alive; a collector records it)
+        self._reward_begin()
         k = self._step_no
         self._step_no += 1
         self._obs_flip ^= 1
@@ -96,7 +103,7 @@ class GeneralsVecEnv(GymVecEnvBase):
         check(e.L.gvec_gym_step(e.h, self.player_id, self._seed + 1000 * self._episode + 1, actions.data_ptr(), *ptrs), "gvec_gym_step")
         self._episode += 1
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
+        return obs, out["reward"], out["terminated"], out["truncated"], self._reward_finish(out, self._add_features(obs, dict(info)))
 
     def _other_moves(self):
         """The [num_envs, max_players, 8] uint8 buffer of the composed step's gvec_action moves, made on first use."""
@@ -135,6 +142,7 @@ class GeneralsVecEnv(GymVecEnvBase):
         _, obs, out, info = self._step_args(k, self._obs_flip)
         cur, mask = self._d_step[k % 3], self._d_mask[self._obs_flip]
         L, pl = e.L, self.player_id
+        self._reward_begin()
         check(L.gvec_gym_actions(e.h, pl, actions.data_ptr(), prev_mask.data_ptr(), cur["needs_reset"].data_ptr(), acts.data_ptr(),
                                  out["played"].data_ptr(), out["invalid"].data_ptr(), out["error"].data_ptr()), "gvec_gym_actions")
         e.step_device(acts.data_ptr())
@@ -143,7 +151,7 @@ class GeneralsVecEnv(GymVecEnvBase):
                                      out["truncated"].data_ptr(), out["winner"].data_ptr(), out["needs_reset"].data_ptr(),
                                      out["turn"].data_ptr()), "gvec_gym_finish_step")
         self.valid_actions_mask = info["valid_actions_mask"]
-        return obs, out["reward"], out["terminated"], out["truncated"], self._add_features(obs, dict(info))
+        return obs, out["reward"], out["terminated"], out["truncated"], self._reward_finish(out, self._add_features(obs, dict(info)))
 
     # ---- gym API ------------------------------------------------------------------------------------
     def step(self, actions, other_actions=None):

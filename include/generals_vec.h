@@ -349,6 +349,57 @@ int32_t gvec_experience_begin(gvec_handle* h);
 int32_t gvec_experience_begin_range(gvec_handle* h, int32_t env_begin, int32_t n);
 int32_t gvec_experience_rewards(gvec_handle* h, float* rewards, uint8_t* done, int32_t mem);
 
+/* ---- configurable rewards: CalculateRewardWithConfig (internal/experience/rewards.go:45-85) with the caller's RewardConfig
+ * (:8-20) instead of DefaultRewardConfig (:23-37).  The struct holds the NINE weights the Go function reads - TerritoryLost
+ * and ArmyLost are never read there: a negative difference is multiplied by TerritoryGained / ArmyGained (:62, :68) - plus
+ * what a gym env adds: invalid_action and the clip flag.
+ *   win_game, lose_game              :49-56  a finished game with a winner: the value IS the reward (no shaped terms)
+ *   territory                        :59-62  (tiles owned now - before) * TerritoryGained
+ *   army                             :65-68  (armies owned now - before) * ArmyGained
+ *   capture_city, lose_city          :71-73  countCityChanges :110-129
+ *   capture_general, lose_general    :76-78  countGeneralChanges :132-151 (a captured general had an owner before)
+ *   army_advantage                   :81-82  calculateArmyAdvantage :153-175 of the CURRENT state, in [-1, 1]
+ *   flags bit 0 (GVEC_REWARD_CLIP)   NormalizeReward :215-223: the value clamped to [-1, 1]
+ *   invalid_action                   added AFTER the clip where the learner's byte of `invalid` is set
+ * float32, the reference's order of additions, no fused multiply-add: with gvec_reward_config_default the values equal
+ * gvec_experience_rewards' bit for bit. */
+#define GVEC_REWARD_CLIP 1u
+typedef struct gvec_reward_config {
+  float win_game, lose_game, capture_city, lose_city, capture_general, lose_general, territory, army, army_advantage;
+  float invalid_action;
+  uint32_t flags;     /* GVEC_REWARD_* */
+  uint32_t reserved;  /* must be 0 */
+} gvec_reward_config;
+/* DefaultRewardConfig (rewards.go:23-37); invalid_action = 0, flags = 0. */
+int32_t gvec_reward_config_default(gvec_reward_config* cfg);
+/* A snapshot that holds only what the REWARD reads of the state before the step - every player's ownership plane and the
+ * tail (territory, armies, turn, dimensions): about 250 bytes per env at 20x20 4P instead of gvec_experience_begin's 3.7 KB.
+ * It is written into the same snapshot buffer and leaves the visibility, mask and army sections as they were: experience
+ * RECORDS (gvec_experience_records) need the full gvec_experience_begin[_range]; after this call they would mix two turns.
+ * gvec_experience_rewards and gvec_experience_rewards_config give the same values after either snapshot.  Sharded handles
+ * fan out as gvec_experience_begin does. */
+int32_t gvec_experience_begin_rewards(gvec_handle* h);
+/* CalculateRewardWithConfig(prev, cur, p, cfg) for every env and every player of `players` (bit p = player p; 0 = all
+ * max_players; a bit at or above max_players: GVEC_E_INVALID).  K = the number of players asked for; columns in ascending
+ * player id.  Per (env, player):
+ *   r = win_game / lose_game for a finished game with a winner, else the shaped sum in the order listed above;
+ *   r = clamp(r, -1, 1) with GVEC_REWARD_CLIP;
+ *   r = 0 for an env that was re-dealt or not stepped since the snapshot (gvec_experience_rewards' rule) and for p >= the
+ *       env's own player count;
+ *   r += invalid_action where invalid[env][k] != 0 (invalid: uint8 [B][K], may be NULL) - also on a row that was not stepped:
+ *       a gym env that does not play a refused turn hands out exactly invalid_action.
+ * Outputs, each may be NULL (all three NULL: GVEC_E_INVALID):
+ *   rewards float32 [B][K]
+ *   terms   int32   [B][K][8]: d_territory, d_army, cities gained, cities lost, generals gained, generals lost, outcome
+ *           (+1 the winner of a finished game, -1 a loser, 0 otherwise), the army advantage's float32 bits; all zero where
+ *           the reward is forced to 0.  What a caller recombines, or builds other shaping on.
+ *   done    uint8   [B]: GameState.IsGameOver (state.go:73-82)
+ * Refused with GVEC_E_INVALID and a gvec_last_error message before any launch: cfg NULL, a weight that is not finite,
+ * reserved != 0, unknown flag bits, a players bit at or above max_players, all outputs NULL, no snapshot taken yet.
+ * Sharded handles: host memory only, as gvec_experience_rewards. */
+int32_t gvec_experience_rewards_config(gvec_handle* h, const gvec_reward_config* cfg, uint32_t players, const uint8_t* invalid,
+                                       float* rewards, int32_t* terms, uint8_t* done, int32_t mem);
+
 /* ---- experience records: what a rank ships to the process feeding StreamAggregator ----
  * One compact record per env transition = everything SimpleCollector.OnStateTransition
  * (internal/experience/collector.go:30-98) puts into the experiencepb.Experience of every player that
