@@ -7,8 +7,10 @@ per step (gvec_arena_update), and ratings on the Elo scale fitted to who outlast
     python examples/evaluate_arena.py a.pt b.pt --random --episodes 4
 
 Each positional argument is a checkpoint written by train_ppo_selfplay.py --save; every --random adds an entrant that plays
-uniformly over its legal moves.  Entrants are seated so that each sits in every column (player seat) equally often
-(arena.balanced_seating), every env contributes exactly --episodes finished games, and nothing synchronises with the host
+uniformly over its legal moves; --playouts K:R:D adds a flat Monte Carlo searcher (search.playout_policy: K candidates, R
+playouts of D turns each per candidate, one launch per step) whose candidates come from the first checkpoint's logits, or
+from a uniform draw when there is no checkpoint.
+Entrants are seated so that each sits in every column (player seat) equally often (arena.balanced_seating), every env contributes exactly --episodes finished games, and nothing synchronises with the host
 between polls.  A multi-player game's pairwise results are treated as independent games by the fit: the ratings rank, their
 error bars are not calibrated.  An example, not part of the measured hot path.
 """
@@ -23,6 +25,7 @@ import torch
 
 from generalsreinforcementlearning_amd.arena import Arena, random_policy, torch_policy
 from generalsreinforcementlearning_amd.features import strategic_features
+from generalsreinforcementlearning_amd.search import PlayoutSearch, playout_policy
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
 
 
@@ -44,7 +47,8 @@ class _WithFeatures(torch.nn.Module):
         return self.net(torch.cat([obs, strategic_features(obs)], dim=1))
 
 
-def load_entrant(path, board, dev, greedy, seed):
+def load_net(path, board, dev):
+    """the network of a checkpoint, in eval mode, taking the observation's nine planes"""
     ck = torch.load(path, map_location=dev)
     if ck["board"] != board:
         raise SystemExit(f"{path} was trained on a {ck['board']}x{ck['board']} board, the arena plays {board}x{board}")
@@ -54,13 +58,30 @@ def load_entrant(path, board, dev, greedy, seed):
     net = _trainer().ActorCritic((ck["channels"], board, board), board * board * 5).to(dev)
     net.load_state_dict(ck["model"])
     net.eval()
-    return torch_policy(_WithFeatures(net) if ck["features"] else net, greedy=greedy, seed=seed)
+    return _WithFeatures(net) if ck["features"] else net
+
+
+def load_entrant(path, board, dev, greedy, seed):
+    return torch_policy(load_net(path, board, dev), greedy=greedy, seed=seed)
+
+
+def parse_playouts(text):
+    """'K:R:D' -> (candidates, replicas, depth), each an int >= 1"""
+    try:
+        k, r, d = (int(x) for x in text.split(":"))
+    except ValueError:
+        raise SystemExit(f"--playouts wants K:R:D (candidates:replicas:depth), not {text!r}")
+    if min(k, r, d) < 1:
+        raise SystemExit(f"--playouts {text}: candidates, replicas and depth must be at least 1")
+    return k, r, d
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoints", nargs="*", help="files written by train_ppo_selfplay.py --save")
     ap.add_argument("--random", action="count", default=0, help="add an entrant that plays uniformly over its legal moves (repeatable)")
+    ap.add_argument("--playouts", metavar="K:R:D", default=None,
+                    help="add a playout-search entrant: K candidates, R playouts each, D turns deep; its prior is the first checkpoint")
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--board", type=int, default=15)
     ap.add_argument("--players", type=int, default=2)
@@ -74,12 +95,18 @@ def main(argv=None):
 
     dev = torch.device("cuda", 0)
     names = [os.path.basename(p) for p in a.checkpoints] + [f"random-{k}" for k in range(a.random)]
+    krd = parse_playouts(a.playouts) if a.playouts else None
+    if krd:
+        names.append("playouts-%d:%d:%d" % krd)
     if not names:
         raise SystemExit("nothing to evaluate: give checkpoints and / or --random")
     entrants = [load_entrant(p, a.board, dev, a.greedy, a.seed + k) for k, p in enumerate(a.checkpoints)]
     entrants += [random_policy(seed=a.seed + 1000 + k) for k in range(a.random)]
     env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
                                  seed=a.seed, device_outputs=True)
+    if krd:
+        prior = load_net(a.checkpoints[0], a.board, dev) if a.checkpoints else None
+        entrants.append(playout_policy(PlayoutSearch(env, candidates=krd[0], replicas=krd[1], depth=krd[2]), net=prior, seed=a.seed + 2000))
     arena = Arena(env, entrants, names=names)
     steps = arena.run(episodes_per_env=a.episodes, poll_every=a.poll_every, max_steps=a.max_steps)
     res = arena.results()

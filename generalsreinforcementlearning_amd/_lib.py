@@ -162,6 +162,15 @@ class ArenaArgs(C.Structure):
                                              "pair2")])
 
 
+class SearchArgs(C.Structure):
+    """gvec_search_args (include/generals_vec.h): every pointer is device memory; root_envs may be None."""
+    _fields_ = ([(n, C.c_int32) for n in ("num_roots", "num_candidates", "replicas", "depth")]
+                + [(n, C.c_void_p) for n in ("root_envs", "root_players", "candidates")]
+                + [("seed", C.c_uint64), ("terms", C.c_void_p)])
+
+
+SEARCH_TERMS, SEARCH_PASS, SEARCH_NONE = 8, -1, -2     # GVEC_SEARCH_* in include/generals_vec.h
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -202,6 +211,7 @@ SYMBOLS = {
     "gvec_set_agent_mix": (_i32, [_vp, _i32, _i32]),
     "gvec_agent_actions": (_i32, [_vp, _u64, _i32, _vp, _i32]),
     "gvec_bot_actions": (_i32, [_vp, C.c_uint32, _u64, _i32, _vp, _i32]),
+    "gvec_search_playouts": (_i32, [_vp, C.POINTER(SearchArgs)]),
     "gvec_counters": (_i32, [_vp, C.POINTER(RolloutStats)]),
     "gvec_step_traffic_bytes": (_i32, [_vp, C.POINTER(C.c_int64)]),
     "gvec_experience_begin": (_i32, [_vp]),

@@ -383,6 +383,9 @@ class Arena:
         flat = t.from_numpy(seat.reshape(-1)).to(dev)
         self._rows = [t.nonzero(flat == e).reshape(-1) for e in range(E)]          # built once: a sync here, none per step
         self._rows = [r if r.numel() else None for r in self._rows]
+        for p, r in zip(self.entrants, self._rows):
+            if hasattr(p, "bind"):
+                p.bind(env, r)              # an entrant that needs to know where it sits (search.playout_policy)
         for p in self.entrants:
             if isinstance(p, (_RandomPolicy, _TorchPolicy)) and p.head is None:
                 if head is None:

@@ -448,4 +448,64 @@ int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_
   return GVEC_OK;
 }
 
+int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args) {
+  static const char* fn = "gvec_search_playouts";
+  // the arguments first, the handle last: every check of a field holds without a device
+  if (!args) {
+    set_err("%s: args is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  const struct {
+    const void* p;
+    const char* name;
+  } required[] = {{args->root_players, "root_players"}, {args->candidates, "candidates"}, {args->terms, "terms"}};
+  for (const auto& r : required)
+    if (!r.p) {
+      set_err("%s: %s is NULL", fn, r.name);
+      return GVEC_E_INVALID;
+    }
+  if (args->num_roots < 0) {
+    set_err("%s: num_roots %d is negative", fn, args->num_roots);
+    return GVEC_E_INVALID;
+  }
+  const struct {
+    int32_t v;
+    const char* name;
+  } counts[] = {{args->num_candidates, "num_candidates"}, {args->replicas, "replicas"}, {args->depth, "depth"}};
+  for (const auto& c : counts)
+    if (c.v < 1) {
+      set_err("%s: %s %d is below 1", fn, c.name, c.v);
+      return GVEC_E_INVALID;
+    }
+  // n * K * R < 2^31, without overflowing on the way
+  const long long kr = (long long)args->num_candidates * args->replicas;
+  if (kr >= (1ll << 31) || (long long)args->num_roots * kr >= (1ll << 31)) {
+    set_err("%s: num_roots * num_candidates * replicas = %d * %d * %d playouts is not below 2^31", fn, args->num_roots, args->num_candidates,
+            args->replicas);
+    return GVEC_E_INVALID;
+  }
+  if (!h) {
+    set_err("%s: h is NULL", fn);
+    return GVEC_E_INVALID;
+  }
+  if (h->sharded()) return sharded::unsupported(fn);
+  if (args->num_roots == 0) return GVEC_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  StepArgs a = base_args(h);
+  a.flags = KF_AGENT;   // no re-deal, no mask emission: the kernel writes terms alone
+  set_agent_seed(&a, args->seed, 0);
+  SearchArgs g;
+  g.root_envs = args->root_envs;
+  g.root_players = args->root_players;
+  g.candidates = args->candidates;
+  g.terms = args->terms;
+  g.num_candidates = args->num_candidates;
+  g.replicas = args->replicas;
+  g.depth = args->depth;
+  g.num_playouts = (int32_t)((long long)args->num_roots * kr);
+  g.stride = h->stride;
+  HIPCHK(launch_search(h->var, a, g, h->stream));
+  return GVEC_OK;
+}
+
 }  // extern "C"

@@ -53,11 +53,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void setup_kernel(ImportArgs 
 // gym_observe_players_kernel read the plain Board layout, gym_step_kernel and gym_step_players_kernel play the turn on the
 // packed Turn layout; every rule of the reference is cited once, on its phase.
 // =========================================================================================
-// What the proto shows one player: `own` its tiles, `seen` the tiles it sees (ComputePlayerVisibility,
-// visibility_optimized.go:166-195: everything when the fog is off), as replicated flat planes.
-struct GymView {
-  uint32_t own, seen;
-};
+// GymView, the Turn layout's player_view / turn_view, gym_sources, gym_decode, turn_tile_counts, army_counts and gym_winner
+// are gvec_turn.hpp's: the playout search (gvec_search.hip) reads a board the same way.
 // Board layout: one register per player and plane kind.  pl is wave-uniform.
 template <int MAXP, typename BT>
 __device__ __forceinline__ GymView board_view(const BT& b, int pl) {
@@ -68,28 +65,6 @@ __device__ __forceinline__ GymView board_view(const BT& b, int pl) {
     vis_p = (p == pl) ? b.vis[p] : vis_p;
   }
   return GymView{own_p, (b.hflags & HF_FOG) ? vis_p : b.valid};
-}
-// Turn layout: player pl's plane, replicated into every row, is row pl % PPR of register pl / PPR.  pl is wave-uniform (a
-// kernel argument or the counter of a loop every lane runs); every lane calls it.
-template <typename B>
-__device__ __forceinline__ uint32_t player_view(int pl, const uint32_t (&reg)[B::NR]) {
-  uint32_t out = 0u;
-#pragma unroll
-  for (int k = 0; k < B::NR; ++k) {
-    const uint32_t g = bperm(player_lane<B::ROWL>(pl, B::col()) << 2, reg[k]);
-    out = (pl / B::PPR == k) ? g : out;
-  }
-  return out;
-}
-template <typename B>
-__device__ __forceinline__ GymView turn_view(const B& b, int pl) {
-  const uint32_t own_p = player_view<B>(pl, b.own);
-  return GymView{own_p, (b.hflags & HF_FOG) ? player_view<B>(pl, b.vis) : b.valid};
-}
-// _get_valid_actions_mask's source tiles: a tile the proto shows as ours (visible, owner == player) with army > 1
-template <typename BT>
-__device__ __forceinline__ uint32_t gym_sources(const BT& b, const GymView& v) {
-  return v.own & v.seen & b.gt1;
 }
 
 // channel 7: min(turn_count / max_turns, 1.0) in float64, stored as float32 (:338-339)
@@ -142,29 +117,6 @@ __device__ __forceinline__ uint32_t turn_own_any(const B& b) {
 #pragma unroll
   for (int k = 0; k < B::NR; ++k) own_any |= b.own[k];
   return B::or_rows(own_any);
-}
-// Every player's stats, player p's in lane p < MAXP.  tile_counts: len(OwnedTiles) of the Turn layout, row totals in the
-// rows' last lanes, handed to lane p.  army_counts: lanes H_ARMYCNT + p of the header register hold ArmyCount[p], fetched
-// by every lane (a cross-lane read must not sit under a divergent branch: masked-off source lanes read as 0).
-template <typename B>
-__device__ __forceinline__ uint32_t turn_tile_counts(const B& b) {
-  const int lane = lane_id();
-  uint32_t tcl = 0u;
-#pragma unroll
-  for (int k = 0; k < B::NR; ++k) {
-    const uint32_t sc = row_scan_add<B::ROWL>((uint32_t)__builtin_popcount(b.lst[k]));
-    const uint32_t got = row_result<B::ROWL>(sc, lane % B::PPR);
-    tcl = (lane / B::PPR == k) ? got : tcl;
-  }
-  return tcl;
-}
-template <int MAXP, typename BT>
-__device__ __forceinline__ uint32_t army_counts(const BT& b) {
-  return bperm((H_ARMYCNT + (lane_id() & (MAXP - 1))) << 2, b.hv);
-}
-
-__device__ __forceinline__ int gym_winner(bool over, int P, uint32_t alive) {   // Engine.GetWinner
-  return (over && P > 1 && __builtin_popcount(alive) == 1) ? (31 - __builtin_clz(alive)) : -1;
 }
 // _calculate_reward (generals_env.py:499-561) for player `pl` against the stats the previous call stored.  cur_tc / cur_ac:
 // the player's tile_count and ArmyCount now.  With several learners the caller stores the new stats (gym_store_stats) only
@@ -232,50 +184,6 @@ __device__ __forceinline__ void gym_bookkeeping(int env, int pl, int P, uint32_t
     if (O.done) O.done[env] = (uint8_t)(over ? 1 : 0);
   }
   gym_store_stats<MAXP>(prev, tcl, acl, alive);
-}
-
-// GeneralsEnv.step's action handling (generals_env.py:226-259, :389-441; gym_actions_kernel does the same from mask bytes):
-// Discrete(N*5) action `a` of the player whose source tiles are `src`, decoded against the valid-action mask of the
-// resident state (recomputed from the planes in registers - the bytes gym_observe wrote are not read back).
-//   valid:    the mask has the action's bit (:226-241)
-//   accepted: the move it turns into is legal too.  A half move, index 4, takes the FIRST of up / right / down / left whose
-//             target is on the board (mountains are not checked there, :389-441), and the server validates the move it
-//             received (action_validator.go:114-139)
-//   from, d, tt: source tile, direction, target tile (on the board and legal by construction of the mask when accepted)
-// a and src are wave-uniform in value; every lane calls it (the rdlanes sit outside every lane-dependent condition).
-struct GymMove {
-  bool valid, accepted, half;
-  int from, d, tt;
-};
-template <typename B>
-__device__ __forceinline__ GymMove gym_decode(const B& b, uint32_t src, long long a, int stride) {
-  GymMove mv;
-  const long long n5 = 5ll * stride;
-  const bool in_range = a >= 0 && a < n5;
-  mv.from = in_range ? (int)(a / 5) : 0;
-  const int from = mv.from, info = in_range ? (int)(a % 5) : 0;
-  const int fy = (int)(__umul24((uint32_t)from, (uint32_t)b.recipW) >> 16), fx = from - (int)__umul24((uint32_t)fy, (uint32_t)b.W);  // from < 1024
-  mv.half = info == 4;
-  int d = mv.half ? 3 : info;
-  if (mv.half) {
-    if (fx - 1 >= 0) d = 3;
-    if (fy + 1 < b.H) d = 2;
-    if (fx + 1 < b.W) d = 1;
-    if (fy - 1 >= 0) d = 0;
-  }
-  mv.d = d;
-  // a tile index beyond the env's own board has no mask bit: the planes are zero there
-  const uint32_t wsrc = rdlane(src, from >> 5);
-  const uint32_t o0 = rdlane(b.ok[0], from >> 5), o1 = rdlane(b.ok[1], from >> 5), o2 = rdlane(b.ok[2], from >> 5), o3 = rdlane(b.ok[3], from >> 5);
-  const uint32_t bit = 1u << (from & 31);
-  const bool s_ok = (wsrc & bit) != 0u;
-  const bool k0 = s_ok && (o0 & bit), k1 = s_ok && (o1 & bit), k2 = s_ok && (o2 & bit), k3 = s_ok && (o3 & bit);
-  const bool kinfo = (info == 0) ? k0 : (info == 1) ? k1 : (info == 2) ? k2 : (info == 3) ? k3 : (k0 || k1 || k2 || k3);
-  mv.valid = in_range && kinfo;
-  const bool kd = (d == 0) ? k0 : (d == 1) ? k1 : (d == 2) ? k2 : k3;
-  mv.accepted = mv.valid && kd;
-  mv.tt = from + ((d == 0) ? -b.W : (d == 1) ? 1 : (d == 2) ? b.W : -1);
-  return mv;
 }
 
 // The two step kernels' geometry K is a VariantGeom (ODD: see step_kernel).

@@ -7,12 +7,7 @@
 namespace gvec {
 
 // ONE engine turn per launch, straight-line (gvec_step; per-turn rollouts).  AGENT: actions are
-// sampled on device from the legal-move planes of the resident state.
-constexpr int waves_for_regs(int need) {  // the waves per SIMD that leave every wave `need` registers (allocated in eights)
-  const int alloc = (need + 7) / 8 * 8;
-  const int w = 512 / alloc;
-  return w > 8 ? 8 : (w < 2 ? 2 : w);
-}
+// sampled on device from the legal-move planes of the resident state.  (waves_for_regs: gvec_turn.hpp)
 // Waves per SIMD asked of the register allocator: the board state a variant holds (planes, army
 // slots, mask planes) plus ~32 working registers.  <4,7> fits 64 registers = 8 waves/SIMD without a
 // spill, which is worth 7 % over 7 waves (one-process A/B): the turn is a long dependent chain of
@@ -115,14 +110,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (step_waves<MAXP, NSLOT>())) 
     b.template legal_planes<false>(m);
     b.store_masks_staged(m, A.legal + (size_t)env * A.pstride * A.mask_dw, FD, A.pstride);
   }
-}
-
-// Waves per SIMD to ask of the register allocator for the fused rollout kernel.  With no HBM traffic
-// inside the turn loop the kernel is latency / issue bound, and occupancy pays even at the price of
-// a few scratch spills; a spill inside the turn loop of the big variants costs far more than a wave.
-template <int MAXP, int NSLOT>
-constexpr int rollout_waves() {
-  return waves_for_regs(Turn<MAXP, NSLOT>::STATE_REGS + (NSLOT >= 16 ? 100 : NSLOT >= 10 ? 68 : 44));
 }
 
 // `turns` engine turns per launch with the board kept in registers / LDS (fused rollouts; always

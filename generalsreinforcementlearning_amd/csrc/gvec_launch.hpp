@@ -141,6 +141,18 @@ struct BotArgs {
   int32_t random_permille;
 };
 hipError_t launch_bot(const Variant& v, const StepArgs& a, const BotArgs& g, hipStream_t s);
+// flat Monte Carlo search (gvec_search_playouts; gvec_search.hip): playout (i * K + k) * R + j = root i, candidate k, replica j
+struct SearchArgs {
+  const int32_t* root_envs;     // [n] or null = 0..n-1
+  const int32_t* root_players;  // [n]
+  const int64_t* candidates;    // [n][K] gym action indices, GVEC_SEARCH_PASS, GVEC_SEARCH_NONE
+  int32_t* terms;               // [n][K][R][GVEC_SEARCH_TERMS]
+  int32_t num_candidates, replicas, depth;
+  int32_t num_playouts;         // n * K * R
+  int32_t stride;               // the handle's tile stride: candidates index Discrete(stride * 5)
+};
+// a.seed_lo / seed_hi: the call's seed; a.env_base is ignored (the playout index is the key)
+hipError_t launch_search(const Variant& v, const StepArgs& a, const SearchArgs& g, hipStream_t s);
 
 // internal/experience side channel
 struct ExperienceArgs {

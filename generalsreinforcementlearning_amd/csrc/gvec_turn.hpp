@@ -145,4 +145,120 @@ __device__ __forceinline__ void redeal(BT& b, const StepArgs& A, int env, int fd
   hdr_set(b, H_CNT_DONE, cd);
 }
 
+// =========================================================================================
+// register budgets of the kernels that keep a board for many turns (rollout_kernel, search_kernel)
+// =========================================================================================
+constexpr int waves_for_regs(int need) {  // the waves per SIMD that leave every wave `need` registers (allocated in eights)
+  const int alloc = (need + 7) / 8 * 8;
+  const int w = 512 / alloc;
+  return w > 8 ? 8 : (w < 2 ? 2 : w);
+}
+// Waves per SIMD to ask of the register allocator for the fused rollout kernel.  With no HBM traffic
+// inside the turn loop the kernel is latency / issue bound, and occupancy pays even at the price of
+// a few scratch spills; a spill inside the turn loop of the big variants costs far more than a wave.
+template <int MAXP, int NSLOT>
+constexpr int rollout_waves() {
+  return waves_for_regs(Turn<MAXP, NSLOT>::STATE_REGS + (NSLOT >= 16 ? 100 : NSLOT >= 10 ? 68 : 44));
+}
+
+// =========================================================================================
+// one player's view of a board in the Turn layout, and a gym action decoded against it (the gym step kernels of
+// gvec_gym.hip, where the reference's rules are cited phase by phase, and the playout search of gvec_search.hip)
+// =========================================================================================
+// What the proto shows one player: `own` its tiles, `seen` the tiles it sees (ComputePlayerVisibility,
+// visibility_optimized.go:166-195: everything when the fog is off), as replicated flat planes.
+struct GymView {
+  uint32_t own, seen;
+};
+// Turn layout: player pl's plane, replicated into every row, is row pl % PPR of register pl / PPR.  pl is wave-uniform (a
+// kernel argument or the counter of a loop every lane runs); every lane calls it.
+template <typename B>
+__device__ __forceinline__ uint32_t player_view(int pl, const uint32_t (&reg)[B::NR]) {
+  uint32_t out = 0u;
+#pragma unroll
+  for (int k = 0; k < B::NR; ++k) {
+    const uint32_t g = bperm(player_lane<B::ROWL>(pl, B::col()) << 2, reg[k]);
+    out = (pl / B::PPR == k) ? g : out;
+  }
+  return out;
+}
+template <typename B>
+__device__ __forceinline__ GymView turn_view(const B& b, int pl) {
+  const uint32_t own_p = player_view<B>(pl, b.own);
+  return GymView{own_p, (b.hflags & HF_FOG) ? player_view<B>(pl, b.vis) : b.valid};
+}
+// _get_valid_actions_mask's source tiles: a tile the proto shows as ours (visible, owner == player) with army > 1
+template <typename BT>
+__device__ __forceinline__ uint32_t gym_sources(const BT& b, const GymView& v) {
+  return v.own & v.seen & b.gt1;
+}
+
+// Every player's stats, player p's in lane p < MAXP.  tile_counts: len(OwnedTiles) of the Turn layout, row totals in the
+// rows' last lanes, handed to lane p.  army_counts: lanes H_ARMYCNT + p of the header register hold ArmyCount[p], fetched
+// by every lane (a cross-lane read must not sit under a divergent branch: masked-off source lanes read as 0).
+template <typename B>
+__device__ __forceinline__ uint32_t turn_tile_counts(const B& b) {
+  const int lane = lane_id();
+  uint32_t tcl = 0u;
+#pragma unroll
+  for (int k = 0; k < B::NR; ++k) {
+    const uint32_t sc = row_scan_add<B::ROWL>((uint32_t)__builtin_popcount(b.lst[k]));
+    const uint32_t got = row_result<B::ROWL>(sc, lane % B::PPR);
+    tcl = (lane / B::PPR == k) ? got : tcl;
+  }
+  return tcl;
+}
+template <int MAXP, typename BT>
+__device__ __forceinline__ uint32_t army_counts(const BT& b) {
+  return bperm((H_ARMYCNT + (lane_id() & (MAXP - 1))) << 2, b.hv);
+}
+
+__device__ __forceinline__ int gym_winner(bool over, int P, uint32_t alive) {   // Engine.GetWinner
+  return (over && P > 1 && __builtin_popcount(alive) == 1) ? (31 - __builtin_clz(alive)) : -1;
+}
+
+// GeneralsEnv.step's action handling (generals_env.py:226-259, :389-441; gym_actions_kernel does the same from mask bytes):
+// Discrete(N*5) action `a` of the player whose source tiles are `src`, decoded against the valid-action mask of the
+// resident state (recomputed from the planes in registers - the bytes gym_observe wrote are not read back).
+//   valid:    the mask has the action's bit (:226-241)
+//   accepted: the move it turns into is legal too.  A half move, index 4, takes the FIRST of up / right / down / left whose
+//             target is on the board (mountains are not checked there, :389-441), and the server validates the move it
+//             received (action_validator.go:114-139)
+//   from, d, tt: source tile, direction, target tile (on the board and legal by construction of the mask when accepted)
+// a and src are wave-uniform in value; every lane calls it (the rdlanes sit outside every lane-dependent condition).
+struct GymMove {
+  bool valid, accepted, half;
+  int from, d, tt;
+};
+template <typename B>
+__device__ __forceinline__ GymMove gym_decode(const B& b, uint32_t src, long long a, int stride) {
+  GymMove mv;
+  const long long n5 = 5ll * stride;
+  const bool in_range = a >= 0 && a < n5;
+  mv.from = in_range ? (int)(a / 5) : 0;
+  const int from = mv.from, info = in_range ? (int)(a % 5) : 0;
+  const int fy = (int)(__umul24((uint32_t)from, (uint32_t)b.recipW) >> 16), fx = from - (int)__umul24((uint32_t)fy, (uint32_t)b.W);  // from < 1024
+  mv.half = info == 4;
+  int d = mv.half ? 3 : info;
+  if (mv.half) {
+    if (fx - 1 >= 0) d = 3;
+    if (fy + 1 < b.H) d = 2;
+    if (fx + 1 < b.W) d = 1;
+    if (fy - 1 >= 0) d = 0;
+  }
+  mv.d = d;
+  // a tile index beyond the env's own board has no mask bit: the planes are zero there
+  const uint32_t wsrc = rdlane(src, from >> 5);
+  const uint32_t o0 = rdlane(b.ok[0], from >> 5), o1 = rdlane(b.ok[1], from >> 5), o2 = rdlane(b.ok[2], from >> 5), o3 = rdlane(b.ok[3], from >> 5);
+  const uint32_t bit = 1u << (from & 31);
+  const bool s_ok = (wsrc & bit) != 0u;
+  const bool k0 = s_ok && (o0 & bit), k1 = s_ok && (o1 & bit), k2 = s_ok && (o2 & bit), k3 = s_ok && (o3 & bit);
+  const bool kinfo = (info == 0) ? k0 : (info == 1) ? k1 : (info == 2) ? k2 : (info == 3) ? k3 : (k0 || k1 || k2 || k3);
+  mv.valid = in_range && kinfo;
+  const bool kd = (d == 0) ? k0 : (d == 1) ? k1 : (d == 2) ? k2 : k3;
+  mv.accepted = mv.valid && kd;
+  mv.tt = from + ((d == 0) ? -b.W : (d == 1) ? 1 : (d == 2) ? b.W : -1);
+  return mv;
+}
+
 }  // namespace gvec

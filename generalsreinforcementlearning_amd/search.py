@@ -1,0 +1,275 @@
+"""Flat Monte Carlo search on the device: what happens if this seat plays move a here?  (include/generals_vec.h "flat Monte
+Carlo search")
+
+    env = GeneralsSelfPlayVecEnv(4096, max_players=2, device_outputs=True)
+    search = PlayoutSearch(env, candidates=8, replicas=4, depth=8)
+    obs, info = env.reset()
+    mask = info["valid_actions_mask"].view(-1, env.single_action_n)
+    actions, found = search.act(mask, logits=net(obs.flatten(0, 1)), seed=step)   # one launch: n * 8 * 4 playouts of 8 turns
+    target = search.policy_target(found["candidates"], found["q"], found["valid"])   # the AlphaZero-style policy target
+    arena = Arena(env, [playout_policy(search), random_policy(seed=1)])           # ... or a baseline to measure against
+
+One HIP launch per evaluation (gvec_search_playouts: one wavefront per playout; the roots are read only and 32 bytes come
+back per playout); proposing the candidates and reducing the terms are a handful of torch calls on [n, K]-sized tensors.
+The playouts see the true state, not the seat's fogged view: a baseline and a teacher, not a fair fogged player.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import SEARCH_NONE, SEARCH_PASS, SEARCH_TERMS, SearchArgs, check
+
+TERM_NAMES = ("valid", "turns", "alive", "won", "land", "army", "land_others", "army_others")   # terms[..., i]
+T_VALID, T_TURNS, T_ALIVE, T_WON, T_LAND, T_ARMY, T_LAND_OTHERS, T_ARMY_OTHERS = range(SEARCH_TERMS)
+
+
+def search_playouts_device(engine, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed=0,
+                           root_envs_ptr=None):
+    """gvec_search_playouts on device memory (VecEngine.search_playouts_device): pointers are ints or None; enqueued on the
+    engine's stream, not synchronised."""
+    a = SearchArgs(num_roots=int(num_roots), num_candidates=int(num_candidates), replicas=int(replicas), depth=int(depth),
+                   root_envs=root_envs_ptr, root_players=root_players_ptr, candidates=candidates_ptr, seed=int(seed) & (2 ** 64 - 1),
+                   terms=terms_ptr)
+    check(engine.L.gvec_search_playouts(engine.h, C.byref(a)), "gvec_search_playouts")
+
+
+def _terms_tensor(terms):
+    import torch
+    if not isinstance(terms, torch.Tensor) or terms.dtype != torch.int32 or terms.dim() < 1 or terms.shape[-1] != SEARCH_TERMS:
+        raise ValueError(f"terms must be an int32 tensor [..., {SEARCH_TERMS}], not "
+                         f"{tuple(terms.shape) if isinstance(terms, torch.Tensor) else type(terms).__name__}")
+    return terms
+
+
+class PlayoutScore:
+    """The value of one playout row, float64: `win` if the seat won, `loss` if it is not alive, else
+    land * land / (land + land_others) + army * army / (army + army_others) - (land + army) / 2 with the weights `land` and
+    `army` (a ratio with a zero denominator counts as 0.5): 0 for an even position, in [-(land + army) / 2, (land + army) / 2]."""
+
+    def __init__(self, win=1.0, loss=-1.0, land=0.5, army=0.5):
+        self.win, self.loss, self.land, self.army = float(win), float(loss), float(land), float(army)
+        if not all(np.isfinite(v) for v in (self.win, self.loss, self.land, self.army)):
+            raise ValueError("PlayoutScore weights must be finite")
+
+    def __call__(self, terms):
+        """terms int32 [..., 8] -> float64 [...] (the value of an invalid row means nothing: PlayoutSearch.scores drops it)"""
+        import torch
+        t = _terms_tensor(terms).to(torch.float64)
+
+        def ratio(mine, others):
+            den = mine + others
+            return torch.where(den != 0, mine / torch.where(den != 0, den, torch.ones_like(den)), torch.full_like(den, 0.5))
+
+        shaped = (self.land * ratio(t[..., T_LAND], t[..., T_LAND_OTHERS]) + self.army * ratio(t[..., T_ARMY], t[..., T_ARMY_OTHERS])
+                  - (self.land + self.army) / 2)
+        out = torch.where(t[..., T_ALIVE] == 0, torch.full_like(shaped, self.loss), shaped)
+        return torch.where(t[..., T_WON] != 0, torch.full_like(shaped, self.win), out)
+
+
+def _uniform_keys(seed, n, A, device):
+    """float64 [n, A] in [0, 1): a counter hash of (seed, row, action index) - the same keys on any device, whatever the
+    batch is split into.  With no prior the Gumbel key -log(-log(u)) ranks the actions as u itself does."""
+    import torch
+    M = 0xFFFFFFFF
+    r = torch.arange(n, dtype=torch.int64, device=device)[:, None]
+    a = torch.arange(A, dtype=torch.int64, device=device)[None, :]
+    s = int(seed) & (2 ** 64 - 1)
+    x = ((s & M) ^ ((s >> 32) * 0x9E3779B1 & M)) + r * 0x85EBCA6B + a * 0xC2B2AE35
+    for mul in (0x7FEB352D, 0x846CA68B):                    # two multiply-xorshift rounds on 32 bits, in int64 lanes
+        x = x & M
+        x = x ^ (x >> 16)
+        x = (x * mul) & M
+    x = x ^ (x >> 15)
+    return (x & M).to(torch.float64) / 4294967296.0
+
+
+class PlayoutSearch:
+    def __init__(self, env_or_engine, candidates=8, replicas=4, depth=8, score=None):
+        """env_or_engine: a gym vector env (GeneralsVecEnv / GeneralsSelfPlayVecEnv with device_outputs=True; rows are its
+        (env, learner column) pairs) or a VecEngine (rows are (env, seat) pairs the caller names).  candidates K, replicas R
+        and depth D >= 1: every evaluated row costs K * R playouts of at most D turns."""
+        for name, v in (("candidates", candidates), ("replicas", replicas), ("depth", depth)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1, not {v!r}")
+        self.K, self.R, self.D = int(candidates), int(replicas), int(depth)
+        self.score = PlayoutScore() if score is None else score
+        self.env = env_or_engine if hasattr(env_or_engine, "engine") else None
+        self.engine = env_or_engine.engine if self.env is not None else env_or_engine
+        e = self.engine
+        self.W, self.H, self.num_actions = int(e.max_w), int(e.max_h), 5 * int(e.max_w) * int(e.max_h)
+        self._ids = None
+
+    # ---- argument checks (before any library call) ---------------------------------------------------------------------
+    def _device(self):
+        import torch
+        return torch.device("cuda", int(self.engine.device))
+
+    def _check(self, t, name, dtype, shape, device=None):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+            raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} {tuple(t.shape)} is not {tuple(shape)}")
+        if device is not None and t.device != device:
+            raise ValueError(f"{name} is on {t.device}, the engine on {device}")
+        return t
+
+    # ---- the launch ----------------------------------------------------------------------------------------------------
+    def evaluate(self, env_ids, players, candidates, seed=0):
+        """env_ids int32 [n] (None: envs 0..n-1), players int32 [n], candidates int64 [n, K]: contiguous CUDA tensors on the
+        engine's device -> terms int32 [n, K, R, 8] (TERM_NAMES).  One launch on the engine's stream, no host sync."""
+        import torch
+        dev = self._device()
+        cand = self._check(candidates, "candidates", torch.int64, None, dev)
+        if cand.dim() != 2 or cand.shape[1] != self.K:
+            raise ValueError(f"candidates {tuple(cand.shape)} is not [n, {self.K}]")
+        n = int(cand.shape[0])
+        self._check(players, "players", torch.int32, (n,), dev)
+        if env_ids is not None:
+            self._check(env_ids, "env_ids", torch.int32, (n,), dev)
+        for name, t in (("candidates", cand), ("players", players), ("env_ids", env_ids)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if n * self.K * self.R >= 2 ** 31:
+            raise ValueError(f"{n} * {self.K} * {self.R} playouts is not below 2^31")
+        terms = torch.empty((n, self.K, self.R, SEARCH_TERMS), dtype=torch.int32, device=dev)
+        if n == 0:                      # nothing to play (an empty tensor has no address to hand over)
+            return terms
+        self.engine.search_playouts_device(n, cand.data_ptr(), players.data_ptr(), terms.data_ptr(), self.K, self.R, self.D, seed,
+                                           None if env_ids is None else env_ids.data_ptr())
+        return terms
+
+    # ---- reductions (torch, on whatever device holds the terms) ---------------------------------------------------------
+    def scores(self, terms):
+        """terms int32 [n, K, R, 8] -> (q float32 [n, K]: the mean score over the valid replicas, 0 where there is none;
+        valid bool [n, K]: some replica was played)"""
+        import torch
+        t = _terms_tensor(terms)
+        if t.dim() != 4:
+            raise ValueError(f"terms {tuple(t.shape)} is not [n, K, R, {SEARCH_TERMS}]")
+        ok = t[..., T_VALID] != 0
+        s = torch.where(ok, self.score(t), torch.zeros((), dtype=torch.float64, device=t.device))
+        cnt = ok.sum(dim=-1)
+        q = s.sum(dim=-1) / cnt.clamp(min=1).to(torch.float64)
+        return q.to(torch.float32), cnt > 0
+
+    def propose(self, mask, logits=None, seed=0):
+        """mask bool / uint8 [n, 5 * H * W] (a row's valid-action mask), logits float [n, 5 * H * W] or None -> candidates
+        int64 [n, K]: the K legal actions with the largest logits - with logits None: with the largest keys of a counter
+        hash of (seed, row, action), a uniform draw without replacement - in that order, padded with GVEC_SEARCH_NONE where
+        fewer than K are legal."""
+        import torch
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 2 \
+                or mask.shape[1] != self.num_actions:
+            raise ValueError(f"mask must be a bool / uint8 tensor [n, {self.num_actions}]")
+        legal = mask != 0
+        n = int(legal.shape[0])
+        if logits is not None:
+            if not isinstance(logits, torch.Tensor) or not logits.is_floating_point() or tuple(logits.shape) != tuple(legal.shape):
+                raise ValueError(f"logits must be a floating-point tensor {tuple(legal.shape)}")
+            if logits.device != legal.device:
+                raise ValueError(f"logits is on {logits.device}, mask on {legal.device}")
+            keys = logits.detach().to(torch.float64)
+        else:
+            keys = _uniform_keys(seed, n, self.num_actions, legal.device)
+        keys = torch.where(legal, keys, torch.full_like(keys, -float("inf")))
+        k = min(self.K, self.num_actions)
+        top = torch.topk(keys, k, dim=1)                      # [n, K]-sized output: not the hot path
+        cand = torch.where(torch.isinf(top.values) & (top.values < 0), torch.full_like(top.indices, SEARCH_NONE), top.indices)
+        if k < self.K:
+            cand = torch.cat([cand, torch.full((n, self.K - k), SEARCH_NONE, dtype=torch.int64, device=cand.device)], dim=1)
+        return cand.contiguous()
+
+    def _rows_to_ids(self, n, rows):
+        """(env_ids int32 [n], players int32 [n]) of the flat (env, column) rows of a gym env (None: all of them)"""
+        import torch
+        env = self.env
+        if env is None:
+            raise ValueError("act() on a bare VecEngine has no learner columns: use evaluate(env_ids, players, candidates)")
+        ids = env._learner_ids() if hasattr(env, "_learner_ids") else list(getattr(env, "player_ids", [0]))
+        L = len(ids)
+        dev = self._device()
+        if self._ids is None:
+            flat = torch.arange(env.num_envs * L, device=dev)
+            seats = torch.tensor(ids, dtype=torch.int32, device=dev)
+            self._ids = ((flat // L).to(torch.int32), seats[flat % L].contiguous())
+        if rows is None:
+            if n != env.num_envs * L:
+                raise ValueError(f"mask has {n} rows, the env {env.num_envs} x {L}: name the rows")
+            return self._ids
+        self._check(rows, "rows", (torch.int64, torch.int32), (n,), dev)
+        r = rows.to(torch.int64)
+        return self._ids[0].index_select(0, r), self._ids[1].index_select(0, r)
+
+    def act(self, mask, logits=None, seed=0, rows=None):
+        """mask [n, 5 * H * W] of the rows `rows` (flat (env, column) indices of the gym env, None: all, in order) ->
+        (actions int64 [n], info): the candidate with the largest q among the valid ones; 0 for a row without one (the env
+        refuses it, as it does for an eliminated learner).  info: candidates [n, K], q [n, K], valid [n, K], terms."""
+        import torch
+        dev = self._device()
+        if isinstance(mask, torch.Tensor) and mask.device != dev:
+            raise ValueError(f"mask is on {mask.device}, the engine on {dev}")
+        cand = self.propose(mask, logits, seed)
+        env_ids, players = self._rows_to_ids(int(cand.shape[0]), rows)
+        terms = self.evaluate(env_ids, players, cand, seed)
+        q, valid = self.scores(terms)
+        best = torch.where(valid, q, torch.full_like(q, -float("inf"))).argmax(dim=1, keepdim=True)
+        actions = torch.where(valid.any(dim=1), cand.gather(1, best).squeeze(1), torch.zeros((), dtype=torch.int64, device=dev))
+        return actions, {"candidates": cand, "q": q, "valid": valid, "terms": terms}
+
+    def policy_target(self, candidates, q, valid, temperature=1.0):
+        """candidates int64 [n, K], q float [n, K], valid bool [n, K] -> float32 [n, 5 * H * W]: softmax(q / temperature)
+        over a row's valid candidates at their action indices, zero elsewhere; all zeros for a row without one.  A valid
+        candidate that is GVEC_SEARCH_PASS has no action index: it takes part in the softmax and its share is dropped."""
+        import torch
+        if not (isinstance(temperature, (int, float)) and temperature > 0 and np.isfinite(temperature)):
+            raise ValueError(f"temperature must be a finite number > 0, not {temperature!r}")
+        self._check(candidates, "candidates", torch.int64, None)
+        if candidates.dim() != 2:
+            raise ValueError(f"candidates {tuple(candidates.shape)} is not [n, K]")
+        if not isinstance(q, torch.Tensor) or not q.is_floating_point() or tuple(q.shape) != tuple(candidates.shape):
+            raise ValueError(f"q must be a floating-point tensor {tuple(candidates.shape)}")
+        self._check(valid, "valid", torch.bool, tuple(candidates.shape))
+        if q.device != candidates.device or valid.device != candidates.device:
+            raise ValueError("candidates, q and valid must be on one device")
+        z = torch.where(valid, q.to(torch.float64) / float(temperature), torch.full(q.shape, -float("inf"), dtype=torch.float64, device=q.device))
+        top = z.max(dim=1, keepdim=True).values
+        e = torch.where(valid, torch.exp(z - torch.where(torch.isinf(top), torch.zeros_like(top), top)), torch.zeros_like(z))
+        den = e.sum(dim=1, keepdim=True)
+        p = e / torch.where(den > 0, den, torch.ones_like(den))
+        on_board = valid & (candidates >= 0) & (candidates < self.num_actions)
+        out = torch.zeros((candidates.shape[0], self.num_actions), dtype=torch.float64, device=q.device)
+        out.scatter_add_(1, torch.where(on_board, candidates, torch.zeros_like(candidates)), torch.where(on_board, p, torch.zeros_like(p)))
+        return out.to(torch.float32)
+
+
+class _PlayoutPolicy:
+    """An Arena entrant: search.act on the rows it is seated at (Arena binds them), the prior from net or uniform."""
+
+    def __init__(self, search, net=None, seed=0):
+        self.search, self.net, self.seed, self._calls, self._rows, self._single = search, net, int(seed), 0, None, False
+
+    def bind(self, env, rows):
+        if env is not self.search.env:
+            raise ValueError("playout_policy: the search was built on another env than the arena's")
+        self._rows = rows
+        self._single = rows is not None and int(rows.numel()) == env.num_envs * env.num_learners
+
+    def __call__(self, obs, mask):
+        import torch
+        logits = None
+        if self.net is not None:
+            with torch.no_grad():
+                out = self.net(obs)
+            logits = (out[0] if isinstance(out, (tuple, list)) else out).reshape(mask.shape)
+        self._calls += 1
+        rows = None if self._single or self._rows is None else self._rows
+        return self.search.act(mask, logits, seed=(self.seed << 32) + self._calls, rows=rows)[0]
+
+
+def playout_policy(search, net=None, seed=0):
+    """An Arena entrant that plays PlayoutSearch.act: the candidates are the top K legal actions by net(obs)'s logits
+    (net returns logits [n, 5 * H * W] or (logits, value)), or a uniform draw of K legal actions when net is None."""
+    return _PlayoutPolicy(search, net, seed)

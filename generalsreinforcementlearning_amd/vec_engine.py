@@ -342,6 +342,16 @@ class VecEngine:
         check(self.L.gvec_bot_actions(self.h, int(players_mask), int(seed), int(random_permille), C.c_void_p(int(actions_ptr)), MEM_DEVICE),
               "gvec_bot_actions")
 
+    def search_playouts_device(self, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed=0,
+                               root_envs_ptr=None):
+        """gvec_search_playouts (flat Monte Carlo search; search.PlayoutSearch is the front): for root i < num_roots - env
+        root_envs[i], None: env i - candidate k and replica j, one playout that plays candidates[i][k] for seat
+        root_players[i], then random-agent turns up to `depth`, into terms[i][k][j][8] (search.TERM_NAMES).  Device pointers
+        (ints): int32 [n], int32 [n], int64 [n][K], int32 [n][K][R][8].  The engine's envs are read only.  Enqueued on the
+        engine's stream, not synchronised."""
+        from .search import search_playouts_device
+        search_playouts_device(self, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed, root_envs_ptr)
+
     def rollout(self, turns, seed, invalid_permille=0, fused=True, want_stats=True):
         st = RolloutStats()
         check(self.L.gvec_rollout(self.h, turns, seed, invalid_permille, int(bool(fused)), C.byref(st) if want_stats else None),

@@ -321,6 +321,45 @@ int32_t gvec_agent_actions(gvec_handle* h, uint64_t seed, int32_t invalid_permil
 int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_t random_permille,
                          gvec_action* actions, int32_t mem);
 
+/* ---- flat Monte Carlo search: what happens if this seat plays move a here? ------------
+ * For every root i < num_roots, candidate k < num_candidates and replica j < replicas, playout v = (i*K + k)*R + j starts
+ * from the state of env root_envs[i] (NULL: env i), plays candidates[i][k] for seat root_players[i] on its first turn while
+ * every other alive seat plays the on-device random agent, then up to depth - 1 further turns with the agent on every seat,
+ * and writes terms[v][GVEC_SEARCH_TERMS]:
+ *   0 valid        the row was played (an invalid row is all zeros)
+ *   1 turns        turns played, <= depth: a finished game ends its playout (never re-dealt, whatever auto_reset says)
+ *   2 alive        the seat is alive at the end
+ *   3 won          the game is over and the seat is Engine.GetWinner
+ *   4 land, 5 army the seat's tile_count and ArmyCount at the end
+ *   6 land_others, 7 army_others   the sums over the other seats
+ * A candidate is a gym action index, tile*5 + {up, right, down, left, half}, decoded against the seat's own valid-action
+ * mask exactly as gvec_gym_step_players decodes a learner's action, or GVEC_SEARCH_PASS: the seat plays no move on its
+ * first turn.  A row is invalid when the candidate is anything else that the decode does not accept (GVEC_SEARCH_NONE, the
+ * padding value, among them), when the root env is outside [0, num_envs) (checked on the device), when the root game is
+ * over, or when the seat is not alive (which covers a seat at or above the env's player count).
+ * The agent's draws are keyed by (seed, PLAYOUT index v, turn, player) under the handle's current gvec_set_agent_mix, with
+ * no unchecked moves: the call equals gvec_copy_envs of the roots, each repeated K*R times, into a scratch handle of n*K*R
+ * envs without a board pool, one gvec_step with gvec_agent_actions(seed, 0)'s moves in which the seat's slot is replaced
+ * by the candidate, gvec_rollout(depth - 1, seed, 0, fused) and the eight numbers read from gvec_read_state - bit for bit,
+ * in one launch that writes 32 bytes per playout and nothing else.  The roots are read only: their headers (lifetime
+ * counters included), planes, armies, the legal-mask buffer, the per-env error codes and the recorded actions keep every
+ * byte.  The playouts see the true state, not the seat's fogged view.
+ * Every pointer is device memory.  Enqueued on the handle's stream; nothing is synchronised.  num_roots == 0: nothing to do.
+ * GVEC_E_INVALID with a gvec_last_error message naming the field: args, root_players, candidates, terms or h NULL, a negative
+ * num_roots, num_candidates / replicas / depth below 1, n*K*R at or above 2^31.  Sharded handles: call it on gvec_shard. */
+#define GVEC_SEARCH_TERMS 8
+#define GVEC_SEARCH_PASS  (-1)
+#define GVEC_SEARCH_NONE  (-2)
+typedef struct gvec_search_args {
+  int32_t num_roots, num_candidates, replicas, depth;   /* n, K, R, D >= 1 */
+  const int32_t* root_envs;     /* device [n], NULL = 0..n-1 */
+  const int32_t* root_players;  /* device [n] */
+  const int64_t* candidates;    /* device [n][K] */
+  uint64_t seed;
+  int32_t* terms;               /* device [n][K][R][GVEC_SEARCH_TERMS] */
+} gvec_search_args;
+int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args);
+
 /* ---- internal/experience side channel ------------------------------
  * gvec_experience_begin   = TurnProcessor.captureStateForExperience
  *                           (turn_processor.go:116-121: GameState.Clone before the step):
