@@ -10,6 +10,9 @@ age_batch works on a VecEngine and an OracleBatch alike (game_state / read_state
 time, and plants the same values into the same boards: twin batches stay twins."""
 import numpy as np
 
+import _harness as H
+import _oracle as O
+
 HF_DONE, HF_FOG, HF_WIDE, HF_SYNC, HF_FEWSPECIAL, HF_LDIFF = 1, 2, 4, 16, 64, 128
 NARROW_MAX = 65535
 # what age_batch plants, by env id % period (ids >= 4 of the period stay as they are)
@@ -125,6 +128,32 @@ def age_batch(target, seed, env_begin=0, n=None, period=AGED_KINDS + 2, turn_off
         if turn_offsets:
             out["turn"] = (st["turn"] + ids % 25).astype(np.int32)
         target.write_state(out, lo)
+
+
+def aged_pair(g, mw, mh, maxp, sizes, seed, fog=True, warm=8, warm_permille=80):
+    """A VecEngine and an oracle dealt the same boards and pool, `warm` lock-step turns with invalid moves, then aged.
+    g: the loaded package; None: the oracle alone, played and aged the same way (the engine returned is None)."""
+    army, owner, typ, ws, hs, ps = H.gen_boards(seed, sizes, mw, mh)
+    B = len(sizes)
+    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=fog, auto_reset=True) if g is not None else None
+    ora = O.OracleBatch(B, mw, mh, maxp, fog=fog)
+    pool = min(16, B)
+    for e in (eng, ora) if eng is not None else (ora,):
+        e.reset(army, owner, typ, ws, hs, ps)
+    ora.set_pool(pool, 70 + seed, ws[:pool], hs[:pool], ps[:pool])
+    if eng is None:
+        for _ in range(warm):
+            ora.step(ora.agent_actions(seed, warm_permille))
+        age_batch(ora, seed)
+        return None, ora
+    eng.build_board_pool(pool, 70 + seed, ws[:pool], hs[:pool], ps[:pool])
+    H.run_lockstep(eng, ora, warm, seed, invalid_permille=warm_permille, check_every=warm, want_mask=False, ctx="warm-up")
+    age_batch(eng, seed)
+    age_batch(ora, seed)
+    st = eng.game_state()
+    H.assert_states_equal(st, ora.read_state(), "after aging")
+    check_flag_invariants(eng, st, "write_state of the aged values")
+    return eng, ora
 
 
 class FormsTally:

@@ -11,6 +11,8 @@ import _equivariance as Q
 import _gym_reference as G
 import _harness as H
 import _oracle as O
+import _reward_cases as RC
+import _reward_reference as RR
 import _symmetry_reference as S
 
 ABORT_CODES = (1, 2, 3, 4, 6, 7, 8)                     # a move the turn refuses: the turn is aborted (5 is ErrGameOver)
@@ -97,12 +99,16 @@ class OracleAsEngine:
     def serializer_mask_bits(self):
         return self.ora.serializer_mask()
 
-    def experience_begin(self):
+    def experience_begin(self, rewards_only=False):
         self.ora.experience_begin()
+        self.prev = self.ora.read_state(fields=RC.STATE)     # what either snapshot of the engine holds of the state
 
-    def experience_rewards(self):
-        r, d = self.ora.rewards()
-        return r, d.astype(bool)
+    def experience_rewards(self, config=None, players=None, invalid=None, terms=False):
+        if config is None and players is None and invalid is None and not terms:
+            r, d = self.ora.rewards()
+            return r, d.astype(bool)
+        r, t, d = RR.reward_reference(self.prev, self.ora.read_state(fields=RC.STATE), config, players=players, invalid=invalid)
+        return (r, d, t) if terms else (r, d)
 
     def compute_player_visibility(self, player):
         vis, fog = np.zeros((self.B, self.stride), bool), np.zeros((self.B, self.stride), bool)
@@ -132,6 +138,27 @@ def compare_rows(orb, rows, image, what, ctx):
             bad = np.argwhere(got != want)
             raise AssertionError(f"{ctx}: {what} of env {i} (sym {orb.sym[i]} of env {orb.base[i]}, base board {orb.dims(i)}) is not the "
                                  f"image of the base env's at {len(bad)} place(s), first {tuple(bad[0])}")
+
+
+def awkward_config():
+    from generalsreinforcementlearning_amd import RewardConfig
+    return RC.configs(RewardConfig)["awkward"]
+
+
+def compare_configured_rewards(orb, target, ctx):
+    """gvec_experience_rewards_config with the "awkward" weights, for all seats and for {0, last seat}: rewards do not depend on
+    where tiles lie, so every image env's rows are its base env's, bit for bit.  -> the nonzero terms on the base envs"""
+    cfg = awkward_config()
+    ra, da, ta = target.experience_rewards(config=cfg, terms=True)
+    pair = [0, target.max_p - 1]
+    rs, ds, ts = target.experience_rewards(config=cfg, players=pair, terms=True)
+    for what, rows in (("configured rewards", RC.bits(ra)), ("configured terms", ta), ("configured done flags", da),
+                       (f"configured rewards of seats {pair}", RC.bits(rs)), (f"configured terms of seats {pair}", ts),
+                       (f"configured done flags of seats {pair}", ds)):
+        bad = np.flatnonzero((rows != rows[orb.base]).reshape(orb.B, -1).any(1))
+        assert len(bad) == 0, f"{ctx}: the {what} differ from the base env's in envs {bad[:8]}"
+    assert np.array_equal(RC.bits(rs), RC.bits(ra)[:, pair]) and np.array_equal(ts, ta[:, pair]), f"{ctx}: seats {pair} are not the all-seats columns"
+    return int(np.count_nonzero(ta[orb.bases]))
 
 
 def compare_outputs(orb, target, rewards, ctx):
@@ -164,12 +191,13 @@ def compare_outputs(orb, target, rewards, ctx):
 def drive(case, orb, target, ora, turns, outputs_every=5, seed_offset=0, on_state=None):
     """`turns` lock-step turns: the oracle's agent moves the base envs, every image env plays the image of its base env's
     moves, and after every turn each image env of `target` must be the image of its base env - err, full state, packed legal
-    masks; every `outputs_every`-th turn also every player's observation, serializer mask, visibility, rewards and (on the
-    device) stream deltas.  `ora` supplies the moves (and, when `target` wraps it, is the engine under test).  Returns the
-    coverage counted on the base envs of the oracle."""
+    masks; every `outputs_every`-th turn also every player's observation, serializer mask, visibility, rewards (the fixed
+    weights and the configured ones, after the reward-only snapshot on every second such turn and the full one otherwise) and
+    (on the device) stream deltas.  `ora` supplies the moves (and, when `target` wraps it, is the engine under test).  Returns
+    the coverage counted on the base envs of the oracle."""
     own = isinstance(target, OracleAsEngine) and target.ora is ora
     cov = dict.fromkeys(FLOORS, 0)
-    cov["rewards"] = cov["turnover"] = 0
+    cov["rewards"] = cov["config_terms"] = cov["turnover"] = 0
     cov["transposed_nonsquare"] = int(sum(1 for i in range(orb.B) if orb.sym[i] & 4 and orb.w[i] != orb.h[i]))
     alive = ora.read_state(fields=("alive",))["alive"].copy()
     for k in range(turns):
@@ -177,7 +205,7 @@ def drive(case, orb, target, ora, turns, outputs_every=5, seed_offset=0, on_stat
         acts = orb.image_actions(ora.agent_actions(case["seed"] + seed_offset, case["permille"]))
         outputs = (k + 1) % outputs_every == 0
         if outputs:
-            target.experience_begin()
+            target.experience_begin(rewards_only=((k + 1) // outputs_every) % 2 == 0)
         err, bits = target.step(acts, want_mask=True)
         oerr = err if own else ora.step(acts)
         assert np.array_equal(err, err[orb.base]), f"{ctx}: err differs from the base env's in envs {np.flatnonzero(err != err[orb.base])[:8]}: " \
@@ -187,6 +215,7 @@ def drive(case, orb, target, ora, turns, outputs_every=5, seed_offset=0, on_stat
         compare_rows(orb, bits, lambda b, w, h, s: Q.image_packed_mask(b, w, h, s, Q.ENGINE_VECTORS), "the post-step legal mask", ctx)
         if outputs:
             cov["rewards"] += compare_outputs(orb, target, target.experience_rewards(), ctx)
+            cov["config_terms"] += compare_configured_rewards(orb, target, ctx)
         if on_state is not None:
             on_state(st)
         # coverage, on the oracle's base envs
@@ -326,7 +355,7 @@ def test_oracle_is_equivariant_on_the_step_cases(case):
     orb, ora, target = oracle_run(case)
     cov = drive(case, orb, target, ora, case["turns"])
     assert_floors(cov, case)
-    assert cov["rewards"] > 0
+    assert cov["rewards"] > 0 and cov["config_terms"] > 0
 
 
 # ---- the aged forms (test_hip_equivariance.py (b)) --------------------------------------------------------------------------

@@ -53,11 +53,12 @@ def _twins(case):
 @pytest.mark.parametrize("case", R.STEP_CASES + [R.FOG_OFF_CASE], ids=lambda c: c["id"])
 def test_step_commutes_with_the_symmetries(case):
     """One launch steps every orientation side by side: err, game_state() and the packed legal masks every turn; observe(-1),
-    the serializer mask, every player's visibility, the rewards and the stream deltas every 5th turn."""
+    the serializer mask, every player's visibility, the rewards (fixed weights and configured, after either snapshot) and the
+    stream deltas every 5th turn."""
     orb, eng, ora = _twins(case)
     cov = R.drive(case, orb, eng, ora, case["turns"])
     R.assert_floors(cov, case)
-    assert cov["rewards"] > 0
+    assert cov["rewards"] > 0 and cov["config_terms"] > 0
     eng.close()
 
 

@@ -10,6 +10,7 @@ import pytest
 
 import _harness as H
 import _oracle as O
+import _reward_cases as RC
 import _reward_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -25,17 +26,7 @@ def g():
     return g
 
 
-def _configs(g):
-    C = g.RewardConfig
-    return {"go_default": C.go_default(),
-            "awkward": C(win_game=0.3, lose_game=-0.7, capture_city=1e-3, lose_city=-2.5, capture_general=0.123, lose_general=-3.3,
-                         territory_gained=0.3, territory_lost=-0.3, army_gained=-0.7, army_lost=0.7, army_advantage=1e-3),
-            "clip": C(capture_city=3.0, lose_city=-3.0, capture_general=5.0, lose_general=-5.0, territory_gained=0.5, territory_lost=-0.5,
-                      invalid_action=-0.25, clip=True)}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+_bits = RC.bits
 
 
 # the scripted bot plays `bots`; the other seats are the random agent.  On the CPU oracle (tests/_bot_reference.py playing the
@@ -52,7 +43,7 @@ def test_configured_rewards_and_terms_equal_the_restatement(g, name, w, h, P, bo
     full.build_board_pool(17, 4)
     lean.build_board_pool(17, 4)
     ora.set_pool(17, 4)
-    cfgs = _configs(g)
+    cfgs = RC.configs(g.RewardConfig)
     rng = np.random.default_rng(seed)
     seen = np.zeros(8, np.int64)
     wins = redeals = clipped = penalised = 0
@@ -129,7 +120,7 @@ def test_sharded_handle_gives_the_single_device_answers(g):
     B, w, h, P = 50, 10, 10, 3
     one = g.VecEngine(B, w, h, P, auto_reset=True)
     many = g.VecEngine(B, w, h, P, auto_reset=True, devices=[0, 0, 0])
-    cfg = _configs(g)["clip"]
+    cfg = RC.configs(g.RewardConfig)["clip"]
     rng = np.random.default_rng(4)
     for e in (one, many):
         e.reset_generated(5)
@@ -161,11 +152,12 @@ def _actions(torch, mask, step, bad_share):
     return torch.where(pick_bad, bad, good)
 
 
-def _run_env_triplet(g, make, learners_of, steps=40):
-    """on: reward_config; off: the same env without it; hand: without it, the three launches made by hand around its step"""
+def _run_env_triplet(g, make, learners_of, B=48, w=9, h=7, steps=40):
+    """make(B, w, h, **options) -> an env.  on: reward_config; off: the same env without it; hand: without it, the three
+    launches made by hand around its step"""
     import torch
     cfg = g.RewardConfig(capture_city=3.0, lose_city=-3.0, territory_gained=0.25, territory_lost=-0.25, invalid_action=-0.375, clip=True)
-    on, off, hand = make(reward_config=cfg), make(), make()
+    on, off, hand = make(B, w, h, reward_config=cfg), make(B, w, h), make(B, w, h)
     o_on, i_on = on.reset(seed=5)
     o_off, i_off = off.reset(seed=5)
     hand.reset(seed=5)
@@ -202,7 +194,8 @@ def _run_env_triplet(g, make, learners_of, steps=40):
 @pytest.mark.parametrize("opponent", ["random", "bot"])
 def test_single_learner_env_with_reward_config(g, opponent):
     from generalsreinforcementlearning_amd.vector_env import GeneralsVecEnv
-    make = lambda **kw: GeneralsVecEnv(48, 9, 7, 2, max_turns=12, seed=5, board_pool=32, device_outputs=True, opponent=opponent, **kw)   # noqa: E731
+    make = lambda B, w, h, **kw: GeneralsVecEnv(B, w, h, 2, max_turns=12, seed=5, board_pool=32, device_outputs=True,   # noqa: E731
+                                                opponent=opponent, **kw)
     _run_env_triplet(g, make, lambda env: [env.player_id])
 
 
@@ -219,12 +212,14 @@ def test_single_learner_env_refused_action_is_exactly_invalid_action(g):
     env.close()
 
 
-@pytest.mark.parametrize("players,learners", [(2, None), (3, [0, 2])])
+@pytest.mark.parametrize("players,learners", [(2, None), (3, [0, 2]), (8, None), (8, [1, 4, 7])])
 def test_selfplay_env_with_reward_config(g, players, learners):
+    """eight seats on 16x16 (the map generator needs 240 tiles to seat eight): with every seat a learner reward_terms is
+    [B, 8, 8], one dword per lane of the kernel's wavefront"""
     from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
-    make = lambda **kw: GeneralsSelfPlayVecEnv(48, 9, 7, players, learners=learners, max_turns=12, seed=5, board_pool=32,   # noqa: E731
-                                               device_outputs=True, **kw)
-    _run_env_triplet(g, make, lambda env: env.player_ids)
+    make = lambda B, w, h, **kw: GeneralsSelfPlayVecEnv(B, w, h, players, learners=learners, max_turns=12, seed=5,   # noqa: E731
+                                                        board_pool=32, device_outputs=True, **kw)
+    _run_env_triplet(g, make, lambda env: env.player_ids, **(dict(B=24, w=16, h=16) if players == 8 else {}))
 
 
 def test_numpy_mode_returns_the_same_rewards(g):

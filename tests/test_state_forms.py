@@ -45,26 +45,6 @@ def _gpu():
     return g
 
 
-def _aged_pair(g, mw, mh, maxp, sizes, seed, fog=True, warm=8, warm_permille=80):
-    """A VecEngine and an oracle dealt the same boards and pool, `warm` lock-step turns with invalid moves, then aged."""
-    army, owner, typ, ws, hs, ps = H.gen_boards(seed, sizes, mw, mh)
-    B = len(sizes)
-    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=fog, auto_reset=True)
-    ora = O.OracleBatch(B, mw, mh, maxp, fog=fog)
-    eng.reset(army, owner, typ, ws, hs, ps)
-    ora.reset(army, owner, typ, ws, hs, ps)
-    pool = min(16, B)
-    eng.build_board_pool(pool, 70 + seed, ws[:pool], hs[:pool], ps[:pool])
-    ora.set_pool(pool, 70 + seed, ws[:pool], hs[:pool], ps[:pool])
-    H.run_lockstep(eng, ora, warm, seed, invalid_permille=warm_permille, check_every=warm, want_mask=False, ctx="warm-up")
-    F.age_batch(eng, seed)
-    F.age_batch(ora, seed)
-    st = eng.game_state()
-    H.assert_states_equal(st, ora.read_state(), "after aging")
-    F.check_flag_invariants(eng, st, "write_state of the aged values")
-    return eng, ora
-
-
 # ---- 1. the per-turn agent step (the benchmarked path) over every compiled layout --------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("maxp", [2, 4, 8])
@@ -75,7 +55,7 @@ def test_per_turn_agent_step_on_aged_envs(maxp, slots, parity):
     g = _gpu()
     B, turns, seed = 54, 90, 40 + slots
     mw, mh, sizes = H.variant_batch(maxp, slots, parity, B)
-    eng, ora = _aged_pair(g, mw, mh, maxp, sizes, seed)
+    eng, ora = F.aged_pair(g, mw, mh, maxp, sizes, seed)
     ctx = f"<{maxp},{slots},{parity}>"
     tally = F.FormsTally()
     tally.add(eng.game_state())
@@ -322,7 +302,7 @@ def test_stream_deltas_on_aged_envs(fog):
     g = _gpu()
     B = 48
     per = [[(10, 8, 3), (15, 15, 2), (20, 20, 4), (20, 17, 4)][i % 4] for i in range(B)]
-    eng, ora = _aged_pair(g, 20, 20, 4, per, 17, fog=fog)
+    eng, ora = F.aged_pair(g, 20, 20, 4, per, 17, fog=fog)
     tally = F.FormsTally()
     seen = {1: 0, 2: 0, "wide_rows": 0}
     for k in range(50):
@@ -375,7 +355,7 @@ def test_experience_channel_on_aged_envs(w, h, P, fog):
     from generalsreinforcementlearning_amd.vec_engine import unpack_legal_bits
     g = _gpu()
     B = 48
-    eng, ora = _aged_pair(g, w, h, P, [(w, h, P)] * B, 23, fog=fog)
+    eng, ora = F.aged_pair(g, w, h, P, [(w, h, P)] * B, 23, fog=fog)
     lay = eng.experience_record_layout()
     off, n = record_offsets(lay), w * h
     slab = torch.zeros(B * lay["record_dw"], dtype=torch.int32, device="cuda")
