@@ -71,6 +71,27 @@ extern "C" __device__ int gvec_llvm_writelane(int value, int lane, int vdst_in) 
 #define GVEC_LEAN 7
 #endif
 
+// Which fixed-pattern cross-lane moves of the turn run on the vector ALU (v_permlane16/32_swap, DPP row_newbcast,
+// v_readlane into a lane mask) instead of as an LDS round trip (ds_bpermute / ds_swizzle), per idiom (bits; DESIGN.md 4.1
+// "Cross-lane moves"; one-process A/B per bit, scripts/ab_bench.py).  A cleared bit compiles the LDS spelling:
+// 1: shared_plane / spread_shared (row r of a register to every row)      2: replicate_row0 (refresh_gt1, the ballot planes)
+// 4: or_rows and multi_sum's lane^16 / lane^32 steps      8: row_last (a row's last lane to that row)
+// 16: the boards' own gather / gather_mask - production, the list sums, army_sum (a flat plane's dwords 2s, 2s+1 as a lane mask)
+// Both spellings of every idiom are always compiled (`*_lds`, `*_valu` below): selftest_kernel holds one to the other.
+// Measured (262,144 boards 20x20 4P, four sessions, profiles/xlane_ab.json): every bit alone is within 2 % of the LDS build and
+// inside its max-min spread (7-9 us of 218); bits 1 and 2 gain nothing alone (218.1 / 217.5 vs 218.2 us) and every combination
+// with them measured slower than the same without (16+2: 221.5 vs 220.0, 4+8+16+2: 222.7 vs 218.8, all five: 222.0 us), so they
+// default to off.  No setting clears the project's margin (twice the parent's spread): LDS instructions per wave fall as
+// counted, the wave's life does not.
+#ifndef GVEC_XLANE
+#define GVEC_XLANE 28
+#endif
+#define GVEC_XL_SPREAD 1
+#define GVEC_XL_ROW0 2
+#define GVEC_XL_ORROWS 4
+#define GVEC_XL_ROWLAST 8
+#define GVEC_XL_GATHER 16
+
 namespace gvec {
 
 // The same knob as constants of a kernel variant (NSLOT 64-tile slots, FD = 2*NSLOT or - `odd` - 2*NSLOT-1 plane dwords):
@@ -82,6 +103,16 @@ constexpr bool lean_derive_ok(int nslot) { return (GVEC_LEAN & 1) != 0 && 2 * ns
 constexpr bool lean_half_last(int nslot, bool odd) { return (GVEC_LEAN & 2) != 0 && odd && (nslot & 1) != 0; }
 // dwords of the GEN plane the staged plane store rewrites to end on a 16-byte boundary (mutable_planes = Planes<MAXP>::MUTABLE)
 constexpr int lean_fold_dwords(int mutable_planes, int fd) { return (GVEC_LEAN & 4) != 0 ? ((mutable_planes * fd + 3) & ~3) - mutable_planes * fd : 0; }
+// GVEC_XLANE per variant: no kernel may lose a wave per SIMD or gain scratch for it (scripts/kernel_regs.py, every kernel of
+// the library against the LDS build).  A swap of a register with itself needs a second register for its other result; the
+// largest variant - eight players on full 32-lane rows - has none left in its gym step kernel (bit 1 alone: 12 bytes of
+// scratch, bit 4 alone: 8), and the eight-player one-slot rollout kernel, which spills already, spills more (bit 4: +12
+// bytes, bit 16: +4): these two keep the LDS spelling of those idioms.
+constexpr bool xlane_tight(int maxp, int nslot) { return maxp >= 8 && nslot <= 1; }
+constexpr bool xlane_swaps_ok(int maxp, int nslot) { return !(maxp >= 8 && nslot >= 16) && !xlane_tight(maxp, nslot); }
+constexpr bool xlane_spread(int maxp, int nslot) { return (GVEC_XLANE & 1) != 0 && xlane_swaps_ok(maxp, nslot); }
+constexpr bool xlane_or_rows(int maxp, int nslot) { return (GVEC_XLANE & 4) != 0 && xlane_swaps_ok(maxp, nslot); }
+constexpr bool xlane_gather(int maxp, int nslot) { return (GVEC_XLANE & 16) != 0 && !xlane_tight(maxp, nslot); }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -372,9 +403,70 @@ __device__ __forceinline__ void wave_argmax(float& v, int& idx) {
 __device__ __forceinline__ uint32_t bperm(int byte_addr, uint32_t v) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
 }
+// ---- fixed-pattern moves between rows, on the vector ALU (GVEC_XLANE) ---------------------------------
+// EXEC: ds_bpermute / ds_swizzle return 0 from a lane that is masked off; v_permlane16/32_swap and DPP row_newbcast leave the
+// lanes of a masked-off lane's pair UNTOUCHED instead.  Every routine below must therefore run with EXEC full: at the top
+// level of a kernel whose waves are whole, or under conditions that are wave-uniform in VALUE (header flags, kernel
+// arguments, ballots) - which is what the LDS spellings already demanded (the NOTE above).  The builtins, never asm strings:
+// the hazard recognizer pads a swap that follows a VALU write of its operands by itself.
+struct LanePair {
+  uint32_t a, b;
+};
+// v_permlane16_swap_b32 of (x, x): with x's four 16-lane rows [A, B, C, D], a = [A, A, C, C] and b = [B, B, D, D]
+__device__ __forceinline__ LanePair swap16(uint32_t x) {
+  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  return LanePair{(uint32_t)r[0], (uint32_t)r[1]};
+}
+// v_permlane32_swap_b32 of (x, x): with x's two halves [L, H], a = [L, L] and b = [H, H]
+__device__ __forceinline__ LanePair swap32(uint32_t x) {
+  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+  return LanePair{(uint32_t)r[0], (uint32_t)r[1]};
+}
+// Two values whose OR / sum is x[lane] (op) x[lane ^ D], D = 16 or 32: the lane's own and its partner's (LDS), or the pair's
+// two values in an order that depends on the lane (a swap of x with itself) - any commutative op gives the same result.
+template <int D>
+__device__ __forceinline__ LanePair with_partner_lds(uint32_t x) {
+  static_assert(D == 16 || D == 32, "lane ^ 16 or lane ^ 32");
+  if constexpr (D == 16) return LanePair{x, (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x401F)};
+  return LanePair{x, bperm((lane_id() ^ 32) << 2, x)};
+}
+template <int D>
+__device__ __forceinline__ LanePair with_partner_valu(uint32_t x) {
+  static_assert(D == 16 || D == 32, "lane ^ 16 or lane ^ 32");
+  if constexpr (D == 16) return swap16(x);
+  return swap32(x);
+}
+template <int D, bool VALU>
+__device__ __forceinline__ LanePair with_partner(uint32_t x) {
+  if constexpr (VALU) return with_partner_valu<D>(x);
+  return with_partner_lds<D>(x);
+}
+// row r (ROWL lanes: r < 64 / ROWL, a compile-time constant once inlined) of x in every row
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_to_all_lds(uint32_t x, int r) {
+  return bperm((r * ROWL + (lane_id() & (ROWL - 1))) << 2, x);
+}
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_to_all_valu(uint32_t x, int r) {
+  static_assert(ROWL == 16 || ROWL == 32, "four rows of 16 lanes or two of 32");
+  if constexpr (ROWL == 16) {
+    const LanePair h = swap16(x);  // [A,A,C,C] / [B,B,D,D]: one swap serves all four rows of a register, one more each pair
+    x = (r & 1) ? h.b : h.a;
+    r >>= 1;
+  }
+  const LanePair g = swap32(x);
+  return r ? g.b : g.a;
+}
+template <int ROWL, bool VALU>
+__device__ __forceinline__ uint32_t row_to_all(uint32_t x, int r) {
+  if constexpr (VALU) return row_to_all_valu<ROWL>(x, r);
+  return row_to_all_lds<ROWL>(x, r);
+}
+
 // ---- flat <-> tile domain ------------------------------------------------------------------
 // tile-domain all-ones / zero mask (gather_mask) or 0/1 (gather) of a flat plane: tile 64s+l is bit l&31 of dword
-// 2s + (l>>5) - of the wave (row 0 of a replicated PBoard plane), or of the row that starts at lane row_base (a packed one)
+// 2s + (l>>5) - of the wave (row 0 of a replicated PBoard plane), or of the row that starts at lane row_base (a packed one).
+// One ds_bpermute and a bit-field extract: the spelling of every kernel that turns planes into per-tile records.
 __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s, int row_base = 0) {
   const int lane = lane_id();
   return __builtin_amdgcn_sbfe((int32_t)bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
@@ -382,6 +474,26 @@ __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s, int row_ba
 __device__ __forceinline__ uint32_t gather(uint32_t plane, int s, int row_base = 0) {
   const int lane = lane_id();
   return __builtin_amdgcn_ubfe(bperm(((row_base + (lane >> 5)) << 2) + 8 * s, plane), (uint32_t)(lane & 31), 1u);
+}
+// The same on the vector ALU, for the turn's own gathers (the boards' members gather / gather_mask: production, the list
+// sums, army_sum), where s and row_base are wave-uniform - a slot loop's counter, a player's row: dwords 2s, 2s+1 ARE the
+// 64 tiles' lane mask - two v_readlane into a scalar pair, one select.  v_readlane reads its lane whatever EXEC says: this
+// spelling has no EXEC rule of its own.
+__device__ __forceinline__ bool gather_flag_valu(uint32_t plane, int s, int row_base = 0) {
+  const uint64_t tiles = ((uint64_t)rdlane(plane, row_base + 2 * s + 1) << 32) | (uint64_t)rdlane(plane, row_base + 2 * s);
+  return __builtin_amdgcn_inverse_ballot_w64(tiles);
+}
+__device__ __forceinline__ int32_t gather_mask_valu(uint32_t plane, int s, int row_base = 0) { return gather_flag_valu(plane, s, row_base) ? -1 : 0; }
+__device__ __forceinline__ uint32_t gather_valu(uint32_t plane, int s, int row_base = 0) { return gather_flag_valu(plane, s, row_base) ? 1u : 0u; }
+template <bool VALU>
+__device__ __forceinline__ int32_t gather_mask_as(uint32_t plane, int s, int row_base) {
+  if constexpr (VALU) return gather_mask_valu(plane, s, row_base);
+  return gather_mask(plane, s, row_base);
+}
+template <bool VALU>
+__device__ __forceinline__ uint32_t gather_as(uint32_t plane, int s, int row_base) {
+  if constexpr (VALU) return gather_valu(plane, s, row_base);
+  return gather(plane, s, row_base);
 }
 // tile-domain predicates -> flat plane: the ballot of slot s is dwords 2s, 2s+1 of the bit string (lanes 2s, 2s+1: row 0)
 __device__ __forceinline__ void ballot_to_row0(uint32_t& plane, unsigned long long ballot, int s) {
@@ -619,6 +731,7 @@ struct Board {
 
   // ---- internal/experience/rewards.go helpers ---------------------------------------------------
   // sum of Tile.Army over a flat plane (countPlayerArmies, rewards.go:98-107)
+  static __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s) { return gather_mask_as<(GVEC_XLANE & GVEC_XL_GATHER) != 0>(plane, s, 0); }
   __device__ __forceinline__ int32_t army_sum(uint32_t plane) const {
     int32_t acc = 0;
 #pragma unroll

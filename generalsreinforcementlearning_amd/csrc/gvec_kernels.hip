@@ -470,8 +470,55 @@ __global__ void selftest_kernel(int32_t* out) {
   }
   if ((uint32_t)gvec_llvm_writelane(777, 5, (int)v) != (lane == 5 ? 777u : v)) fail = fail ? fail : 11;
   if (mad24(v, 3u, 5u) != v * 3u + 5u) fail = fail ? fail : 12;
+  {  // the fixed-pattern moves between rows (GVEC_XLANE): the LDS and the vector-ALU spelling of each, both held to plain
+     // arithmetic on data that differs in every lane (and so in every row).  Every cross-lane result lands in a local first:
+     // the comparisons below diverge, the moves above them must not.
+    auto val = [](int l) { return ((uint32_t)l * 0x9E3779B1u) ^ 0x80000105u; };
+    const uint32_t w = val(lane);
+    for (int r = 0; r < 4; ++r) {  // 16: row r of 16 lanes to every row
+      const uint32_t a = row_to_all_lds<16>(w, r), c = row_to_all_valu<16>(w, r), e = val(16 * r + (lane & 15));
+      if (a != e || c != e) fail = fail ? fail : 16;
+    }
+    for (int r = 0; r < 2; ++r) {  // 17: row r of 32 lanes to every row
+      const uint32_t a = row_to_all_lds<32>(w, r), c = row_to_all_valu<32>(w, r), e = val(32 * r + (lane & 31));
+      if (a != e || c != e) fail = fail ? fail : 17;
+    }
+    {  // 18, 19: the lane ^ 16 and lane ^ 32 partners under OR and under addition
+      const LanePair a = with_partner_lds<16>(w), c = with_partner_valu<16>(w);
+      const uint32_t o = val(lane ^ 16);
+      if ((a.a | a.b) != (w | o) || (c.a | c.b) != (w | o) || a.a + a.b != w + o || c.a + c.b != w + o) fail = fail ? fail : 18;
+      const LanePair a2 = with_partner_lds<32>(w), c2 = with_partner_valu<32>(w);
+      const uint32_t o2 = val(lane ^ 32);
+      if ((a2.a | a2.b) != (w | o2) || (c2.a | c2.b) != (w | o2) || a2.a + a2.b != w + o2 || c2.a + c2.b != w + o2) fail = fail ? fail : 19;
+    }
+    {  // 20: or_rows, four rows of 16 and two of 32
+      const uint32_t a = PBoard<4, 7>::or_rows<false>(w), c = PBoard<4, 7>::or_rows<true>(w);
+      const uint32_t a2 = PBoard<4, 16>::or_rows<false>(w), c2 = PBoard<4, 16>::or_rows<true>(w);
+      const int c16 = lane & 15, c32 = lane & 31;
+      const uint32_t e = val(c16) | val(c16 + 16) | val(c16 + 32) | val(c16 + 48), e2 = val(c32) | val(c32 + 32);
+      if (a != e || c != e || a2 != e2 || c2 != e2) fail = fail ? fail : 20;
+    }
+    {  // 21: a row's last lane to the row
+      const uint32_t a = row_last_lds<16>(w), c = row_last_valu<16>(w), a2 = row_last_lds<32>(w), c2 = row_last_valu<32>(w);
+      if (a != val(lane | 15) || c != val(lane | 15) || a2 != val(lane | 31) || c2 != val(lane | 31)) fail = fail ? fail : 21;
+    }
+    // 22, 23: dwords 2s, 2s+1 of the row at row_base as the 64 tiles' lane mask (they differ: every lane's value does), for
+    // every slot a row of 16 (7 slots) or 32 lanes (16 slots) can hold
+    for (int rows = 4; rows >= 2; rows -= 2) {
+      const int rowl = 64 / rows, slots = rows == 4 ? 7 : 16;
+      for (int rb = 0; rb < 64; rb += rowl) {
+        for (int s = 0; s < slots; ++s) {
+          const uint32_t g0 = gather(w, s, rb), g1 = gather_valu(w, s, rb);
+          const int32_t m0 = gather_mask(w, s, rb), m1 = gather_mask_valu(w, s, rb);
+          const uint32_t e = (val(rb + 2 * s + (lane >> 5)) >> (lane & 31)) & 1u;
+          if (g0 != e || g1 != e || m0 != -(int32_t)e || m1 != -(int32_t)e) fail = fail ? fail : (rows == 4 ? 22 : 23);
+        }
+      }
+    }
+  }
+  // lane * 64 + code (callers only test for 0)
   const unsigned long long any = __builtin_amdgcn_ballot_w64(fail != 0);
-  if (lane == 0) out[0] = any ? (int32_t)(__builtin_ctzll(any) * 16 + rdlane((uint32_t)fail, (int)__builtin_ctzll(any))) : 0;
+  if (lane == 0) out[0] = any ? (int32_t)(__builtin_ctzll(any) * 64 + rdlane((uint32_t)fail, (int)__builtin_ctzll(any))) : 0;
 }
 
 // =========================================================================================

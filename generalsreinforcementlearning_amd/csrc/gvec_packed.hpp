@@ -80,11 +80,24 @@ __device__ __forceinline__ int player_lane(int p, int c) { return player_row<ROW
 // what the LAST lane of row r holds (a row-wise scan's result), per lane: lane p asks for its player's row, r = p % PPR
 template <int ROWL>
 __device__ __forceinline__ uint32_t row_result(uint32_t v, int r) { return bperm(((r * ROWL) + ROWL - 1) << 2, v); }
-// every lane receives the value of its row's LAST lane (ds_swizzle bit mode: lane = (lane & and) | or)
+// every lane receives the value of its row's LAST lane.  LDS: ds_swizzle bit mode, lane = (lane & and) | or.  VALU (EXEC full,
+// see gvec_device.hpp "fixed-pattern moves"): DPP row_newbcast:15 hands every 16-lane row its lane 15; a 32-lane row then
+// takes the odd 16-lane row of each pair (swap16's b = [B, B, D, D]).
 template <int ROWL>
-__device__ __forceinline__ uint32_t row_last(uint32_t v) {
+__device__ __forceinline__ uint32_t row_last_lds(uint32_t v) {
   if constexpr (ROWL == 16) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x10 | (0x0F << 5));
   return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x1F << 5);
+}
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_last_valu(uint32_t v) {
+  const uint32_t l15 = dpp0<0x15F>(v);  // row_newbcast:15
+  if constexpr (ROWL == 16) return l15;
+  return swap16(l15).b;
+}
+template <int ROWL>
+__device__ __forceinline__ uint32_t row_last(uint32_t v) {
+  if constexpr ((GVEC_XLANE & GVEC_XL_ROWLAST) != 0) return row_last_valu<ROWL>(v);
+  return row_last_lds<ROWL>(v);
 }
 
 // position of the r-th (0-based) set bit of w, per lane (r < popcount(w), else unspecified)
@@ -186,10 +199,15 @@ struct PBoard {
   __device__ __forceinline__ uint32_t dil3(uint32_t m) const { return dil_v(dil_h(m)); }
 
   // OR of the rows of a packed plane, replicated into every row
+  static constexpr bool XL_SPREAD = xlane_spread(MAXP, NSLOT), XL_ORROWS = xlane_or_rows(MAXP, NSLOT);  // GVEC_XLANE bits 1, 4
+  template <bool VALU = XL_ORROWS>
   static __device__ __forceinline__ uint32_t or_rows(uint32_t x) {
-    if constexpr (PPR == 4) x |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x401F);  // lane ^ 16
-    x |= bperm((lane_id() ^ 32) << 2, x);
-    return x;
+    if constexpr (PPR == 4) {
+      const LanePair h = with_partner<16, VALU>(x);  // lane ^ 16
+      x = h.a | h.b;
+    }
+    const LanePair g = with_partner<32, VALU>(x);  // lane ^ 32
+    return g.a | g.b;
   }
 
   // ---- header (unpack_hdr / pack_hdr: gvec_device.hpp) ---------------------------------------------
@@ -258,7 +276,7 @@ struct PBoard {
   // immediate offset and no select on the data.  The shared planes come in PPR at a time as well (a load per shared
   // plane with every row reading the same dwords is 13 vector-memory instructions instead of 4, and the memory
   // pipeline, not the bytes, then sets the pace: scripts/microbench/copy_pattern2.hip) and are spread over the rows
-  // afterwards, one ds_bpermute each (spread_shared).  PACK = false: the shared planes one load each, every row reading
+  // afterwards (spread_shared: row swaps on the vector ALU, or one ds_bpermute each - GVEC_XLANE).  PACK = false: the shared planes one load each, every row reading
   // the same dwords - for the kernels that load a board once and then play many turns on it (no spread_shared, and
   // no registers held for it).
   template <bool PACK = true>
@@ -325,7 +343,10 @@ struct PBoard {
       if (col() < fd && (k * PPR + row() < MAXP)) gp[(PL::LST + k * PPR) * fd] = lst[k];
   }
   // shared plane j (CHG + j), replicated in every row
-  __device__ __forceinline__ uint32_t shared_plane(int j) const { return bperm((((j % PPR) * ROWL) + col()) << 2, shp[j / PPR]); }
+  // (VALU: the swaps of one shp register are shared by the planes it holds - three serve four planes at ROWL 16)
+  __device__ __forceinline__ uint32_t shared_plane(int j) const {
+    return row_to_all<ROWL, XL_SPREAD>(shp[j / PPR], j % PPR);
+  }
   __device__ __forceinline__ void spread_shared() {
     chg = shared_plane(PL::CHG - PL::CHG);
     vch = shared_plane(PL::VCH - PL::CHG);
@@ -418,14 +439,18 @@ struct PBoard {
   __device__ __forceinline__ uint32_t tile_bit(int t) const { return (col() == (t >> 5)) ? (1u << (t & 31)) : 0u; }
 
   // ---- flat <-> tile domain (gather / gather_mask / ballot_to_row0: gvec_device.hpp) -----------------------
-  static __device__ __forceinline__ uint32_t replicate_row0(uint32_t plane) { return bperm(col() << 2, plane); }
+  // the turn's own gathers - the slot and the row base are constants of the unrolled loops they sit in (GVEC_XLANE bit 16)
+  static constexpr bool XL_GATHER = xlane_gather(MAXP, NSLOT);
+  static __device__ __forceinline__ int32_t gather_mask(uint32_t plane, int s, int row_base = 0) { return gather_mask_as<XL_GATHER>(plane, s, row_base); }
+  static __device__ __forceinline__ uint32_t gather(uint32_t plane, int s, int row_base = 0) { return gather_as<XL_GATHER>(plane, s, row_base); }
+  static __device__ __forceinline__ uint32_t replicate_row0(uint32_t plane) { return row_to_all<ROWL, (GVEC_XLANE & GVEC_XL_ROW0) != 0>(plane, 0); }
   // popcount of a replicated plane: row 0's lanes summed (the scan's zero fill keeps other rows out)
   __device__ __forceinline__ int count_shared(uint32_t plane) const {
     return (int)rdlane(row_scan_add<ROWL>((uint32_t)__builtin_popcount(plane)), ROWL - 1);
   }
   static __device__ __forceinline__ bool any_bit(uint32_t plane) { return __builtin_amdgcn_ballot_w64(plane != 0u) != 0ull; }
   // Tile.Army > 1 as a replicated flat plane: the ballot of slot s is dwords 2s, 2s+1 of the bit string
-  // (written into row 0 with v_writelane: 2*NSLOT <= ROWL), one ds_bpermute copies row 0 into every row
+  // (written into row 0 with v_writelane: 2*NSLOT <= ROWL), replicate_row0 copies row 0 into every row
   __device__ __forceinline__ void refresh_gt1() {
     uint32_t g = 0u;
 #pragma unroll
@@ -476,7 +501,7 @@ struct PBoard {
   // adds each).  First the accumulators are folded into one register, lane l keeping class
   // l & (MAXP-1): at each level a lane keeps its own class's half and hands the other half to its
   // partner (quad_perm / row_ror swaps).  Then lanes of equal class are summed: row_shr inside a row of
-  // 16, ds_swizzle (xor 16) and ds_bpermute (xor 32) across rows.  Returns a register whose lanes
+  // 16, then lane ^ 16 and lane ^ 32 across rows (with_partner).  Returns a register whose lanes
   // H_ARMYCNT+p hold the total of acc[p].
   __device__ __forceinline__ uint32_t multi_sum(const int32_t (&acc)[MAXP]) const {
     static_assert(MAXP == 2 || MAXP == 4 || MAXP == 8, "fold levels are written for 2, 4 or 8 players");
@@ -510,8 +535,11 @@ struct PBoard {
     if constexpr (MAXP <= 2) r += dpp0<0x112>(r);  // row_shr:2
     if constexpr (MAXP <= 4) r += dpp0<0x114>(r);  // row_shr:4
     r += dpp0<0x118>(r);                           // row_shr:8 -> the last MAXP lanes of each row hold the row's sums
-    r += (uint32_t)__builtin_amdgcn_ds_swizzle((int)r, 0x401F);  // lane ^ 16
-    r += bperm((lane ^ 32) << 2, r);
+    constexpr bool VALU = XL_ORROWS;
+    const LanePair h = with_partner<16, VALU>(r);  // lane ^ 16
+    r = h.a + h.b;
+    const LanePair g = with_partner<32, VALU>(r);  // lane ^ 32
+    r = g.a + g.b;
     return dpp0<0x100 + 12 - MAXP>(r);  // row_shl: lanes 16-MAXP.. of row 0 -> lanes 4..
   }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of two builds of libgvec_hip.so in ONE process on ONE device
-(cdna_hip_programming.md 5.4 rule 24).   usage: scripts/ab_bench.py [--dup] libA.so libB.so [libC.so ...] [rounds] [steps]"""
+(cdna_hip_programming.md 5.4 rule 24).   usage: scripts/ab_bench.py [--dup] [--json=OUT.json] libA.so libB.so [libC.so ...] [rounds] [steps]
+--json=OUT.json also writes every round's raw per-turn and fused times (us) per build."""
 import statistics as st
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,6 +9,8 @@ import torch
 from generalsreinforcementlearning_amd import _lib
 from generalsreinforcementlearning_amd.vec_engine import VecEngine
 
+json_out = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--json=")), None)
+sys.argv = [a for a in sys.argv if not a.startswith("--json=")]
 paths = [a for a in sys.argv[1:] if a.endswith(".so")]
 if "--dup" in sys.argv:  # every build twice, interleaved: shows how much of a difference is buffer placement / order
     sys.argv.remove("--dup")
@@ -42,4 +45,13 @@ for r in range(rounds):
         fres[i].append(a.elapsed_time(b) / 32)
 for i, p in enumerate(paths):
     m, f = st.median(res[i]), st.median(fres[i])
-    print(f"{p}: per-turn median {m*1e3:.1f} us/step (min {min(res[i])*1e3:.1f}) -> {B/m/1e3:.1f} M steps/s | fused {f*1e3:.1f} us/turn -> {B/f/1e3:.1f} M steps/s")
+    print(f"{p}: per-turn median {m*1e3:.1f} us/step (min {min(res[i])*1e3:.1f}, max-min {(max(res[i])-min(res[i]))*1e3:.1f}) -> {B/m/1e3:.1f} M steps/s | "
+          f"fused {f*1e3:.1f} us/turn (max-min {(max(fres[i])-min(fres[i]))*1e3:.1f}) -> {B/f/1e3:.1f} M steps/s")
+if json_out:
+    import json
+    us = lambda v: [round(x * 1e3, 2) for x in v]
+    json.dump({"boards": [B, W, H, P], "rounds": rounds, "steps_per_round": steps, "order": "interleaved, one process, one device",
+               "builds": [{"lib": p, "per_turn_us": us(res[i]), "per_turn_median_us": round(st.median(res[i]) * 1e3, 2),
+                           "per_turn_max_minus_min_us": round((max(res[i]) - min(res[i])) * 1e3, 2),
+                           "fused_us_per_turn": us(fres[i]), "fused_median_us": round(st.median(fres[i]) * 1e3, 2)} for i, p in enumerate(paths)]},
+              open(json_out, "w"), indent=1)

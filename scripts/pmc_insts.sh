@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for L in "$@"; do
   D=gpurun_out/pmc_$(basename $L .so)
   rm -rf $D
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $D -- python3 scripts/ab_bench.py $L 1 10 > $D.log 2>&1 || { echo "rocprofv3 failed for $L" >> gpurun_out/pmc_insts.txt; continue; }
+  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $D -- python3 scripts/ab_bench.py $L 1 10 > $D.log 2>&1 || { echo "rocprofv3 failed for $L" >> $(dirname $D)/pmc_insts.txt; continue; }
   python3 - "$L" $D >> gpurun_out/pmc_insts.txt <<'PY'
 import sys, glob, csv, collections, statistics
 lib, d = sys.argv[1:3]
