@@ -92,6 +92,21 @@ extern "C" __device__ int gvec_llvm_writelane(int value, int lane, int vdst_in) 
 #define GVEC_XL_ROWLAST 8
 #define GVEC_XL_GATHER 16
 
+// The per-turn step kernel's straight-line path for the ORDINARY turn (bits; DESIGN.md 4.1 "Ordinary turn"; one-process A/B
+// per bit, scripts/ab_bench.py).  A wave decides ONCE, from the header words the scalar cache hands it, whether its env is live,
+// in narrow army form, with lists equal to ownership, stats in sync, at most one captured tile per player and few special
+// tiles (PBoard::ordinary_turn) - and then runs an instantiation of the turn in which every guard on those facts is folded to
+// its known answer.  0 compiles the parent's step_kernel; the fused rollout, gym, search and bot kernels never take the path.
+// 1: the path itself      4: growth turns (turn % interval == 0) are not ordinary: the path folds `grow` to false as well
+// (2 was production's gathers reading their lane mask one slot ahead of the select that consumes it: six `s_nop` fewer on
+// the path, 1.2-2.0 us SLOWER than bit 1 alone in three sessions of three - measured and taken out)
+// Measured (262,144 boards 20x20 4P, three sessions, profiles/ordturn_ab.json): see DESIGN.md 4.1 "Ordinary turn".
+#ifndef GVEC_ORDTURN
+#define GVEC_ORDTURN 5
+#endif
+#define GVEC_OT_PATH 1
+#define GVEC_OT_NOGROW 4
+
 namespace gvec {
 
 // The same knob as constants of a kernel variant (NSLOT 64-tile slots, FD = 2*NSLOT or - `odd` - 2*NSLOT-1 plane dwords):
@@ -113,6 +128,22 @@ constexpr bool xlane_swaps_ok(int maxp, int nslot) { return !(maxp >= 8 && nslot
 constexpr bool xlane_spread(int maxp, int nslot) { return (GVEC_XLANE & 1) != 0 && xlane_swaps_ok(maxp, nslot); }
 constexpr bool xlane_or_rows(int maxp, int nslot) { return (GVEC_XLANE & 4) != 0 && xlane_swaps_ok(maxp, nslot); }
 constexpr bool xlane_gather(int maxp, int nslot) { return (GVEC_XLANE & 16) != 0 && !xlane_tight(maxp, nslot); }
+// GVEC_ORDTURN per step_kernel variant, as the ORD argument of the turn's templates (0: the general code alone).  No variant
+// may lose a wave per SIMD or gain scratch for carrying two instantiations of the turn, nor grow past 40 KB of code (the
+// instruction cache is 64 KB for two CUs; only <4,7,true,true> was timed) - scripts/isa_diff.py against the GVEC_ORDTURN=0
+// build, every step_kernel.  The kernels that read their actions (AGENT false) hold fewer registers than the agent's and
+// the allocator spends the difference: from ten slots on, and with eight players from two, they would drop from 8 waves to
+// 7, 6 or 5 (<2,16>: 24-28 bytes of scratch).  Of the agent's kernels <8,10> (6 -> 5 waves) and <8,2,odd> (8 -> 7) would
+// lose a wave, <4,16>, <8,4>, <8,7> would be 42-50 KB and <8,16> 79 KB.  These keep the general code: 43 of 72 carry the path.
+// NOT held: "no more VGPRs than the parent".  Below the 64 registers of 8 waves the allocator takes what is free: the
+// action-reading kernels that carry the path go from 50-55 to 55-64, seven of the agent's gain one; the waves per SIMD stay.
+constexpr bool ordturn_fits(int maxp, int nslot, bool agent, bool odd) {
+  if (!agent) return maxp <= 4 ? nslot <= 7 : nslot <= 1;
+  return maxp <= 2 || (maxp <= 4 ? nslot <= 10 : (nslot <= 2 && !(nslot == 2 && odd)));
+}
+constexpr int ordturn_bits(int maxp, int nslot, bool agent, bool odd) {
+  return (GVEC_ORDTURN & GVEC_OT_PATH) != 0 && ordturn_fits(maxp, nslot, agent, odd) ? (GVEC_ORDTURN & (GVEC_OT_PATH | GVEC_OT_NOGROW)) : 0;
+}
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 

@@ -18,6 +18,55 @@ constexpr int step_waves() {
   return waves_for_regs(state + (state + 32 <= 62 ? 32 : 40));  // 8 waves only where they fit with room to spare
 }
 
+// The ORDINARY turn of the per-turn kernel (GVEC_ORDTURN, gvec_device.hpp), from the header's landing on: step_kernel found
+// PBoard::ordinary_turn<ORD>() true and no forced re-deal.  The env is live and plays: no re-deal, no frozen env, no second
+// fetch for lists or wide armies, the turn's guards on the loaded state folded (turn_step<ORD>), the mutable planes alone
+// to store and the masks always stale.  What the turn itself brings about - an abort, an elimination, a finished game, an
+// army beyond u16 - is tested here as in the general code below, whose statements these are.
+template <int ORD, int MAXP, int NSLOT, bool AGENT, bool ODD>
+__device__ __forceinline__ void step_ordinary(Turn<MAXP, NSLOT>& b, const StepArgs& A, int env, const uint32_t* rows_in, const ArmyRef& army_env) {
+  constexpr int FD = VariantGeom<MAXP, NSLOT, ODD>::FD, ROW_DW = VariantGeom<MAXP, NSLOT, ODD>::ROW_DW;
+  using B = Turn<MAXP, NSLOT>;
+  const int lane = lane_id();
+  load_turn_tail<ORD>(b, rows_in, army_env, FD);
+  b.small = true;
+  uint32_t m[B::NR][4];
+  typename B::ActVec av;
+  if constexpr (AGENT) {
+    b.template legal_planes<false>(m);
+    const uint32_t mine = agent_sample<MAXP, NSLOT>(b, m, env_key_of(A.seed_base, (uint32_t)env), A);
+    av = agent_actvec<MAXP, NSLOT>(b, mine, A.invalid_permille > 0);
+    if (A.actions_out) {
+      uint32_t alo, ahi;
+      agent_words<MAXP, NSLOT>(b, mine, alo, ahi);
+      if (lane < A.pstride) reinterpret_cast<uint2*>(A.actions_out)[(size_t)env * A.pstride + lane] = make_uint2(alo, ahi);
+    }
+  } else {
+    uint32_t alo = 0u, ahi = 0u;
+    if (lane < A.pstride) {
+      const uint2 w = reinterpret_cast<const uint2*>(A.actions)[(size_t)env * A.pstride + lane];
+      alo = w.x;
+      ahi = w.y;
+    }
+    av = b.prevalidate(alo, ahi);
+  }
+  bool aborted;
+  const uint32_t err = b.template turn_step<ORD>(av, A, aborted);
+  b.refresh_gt1();
+  hdr_set(b, H_CNT_STEPS, hdr_get(b, H_CNT_STEPS) + 1u);
+  if (aborted) hdr_set(b, H_CNT_ABORT, hdr_get(b, H_CNT_ABORT) + 1u);
+  if (b.hflags & HF_DONE) hdr_set(b, H_CNT_DONE, hdr_get(b, H_CNT_DONE) + 1u);
+  store_army<true>(b, army_env);
+  settle_lists(b);
+  b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
+  b.store_planes_staged(A.rows + (size_t)env * ROW_DW, FD);
+  if (A.err && lane == 0) A.err[env] = (int32_t)err;
+  if (A.flags & KF_EMIT) {
+    b.template legal_planes<false>(m);
+    b.store_masks_staged(m, A.legal + (size_t)env * A.pstride * A.mask_dw, FD, A.pstride);
+  }
+}
+
 // ODD: the planes are 2*NSLOT-1 dwords long (else 2*NSLOT): the plane stride is a compile-time
 // constant here, so every plane access is one instruction with an immediate offset.
 template <int MAXP, int NSLOT, bool AGENT, bool ODD>
@@ -44,7 +93,20 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (step_waves<MAXP, NSLOT>())) 
   b.larmy = army_shadow[wave];
   b.lscr = act_scratch[wave];
   const ArmyRef army_env = army_ref<NSLOT>(A.army16, A.army32, env);
-  load_turn<true, lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
+  // GVEC_ORDTURN: ONE wave-uniform branch, taken as soon as the header words are there, sends the ordinary turn down its own
+  // instantiation; everything below is the general code (profiling builds count phases of that code alone)
+  constexpr int ORD = (GVEC_PROFILE_SKIP | GVEC_PROFILE_DUP) != 0 ? 0 : ordturn_bits(MAXP, NSLOT, AGENT, ODD);
+  if constexpr (ORD != 0) {
+    const uint32_t* rows_env = A.rows + (size_t)env * ROW_DW;
+    load_turn_issue<lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, rows_env, army_env, FD, A.zeros);
+    if (!force_redeal && b.template ordinary_turn<ORD>(A)) {
+      step_ordinary<ORD, MAXP, NSLOT, AGENT, ODD>(b, A, env, rows_env, army_env);
+      return;
+    }
+    load_turn_tail<0>(b, rows_env, army_env, FD);
+  } else {
+    load_turn<true, lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
+  }
   b.small = !(b.hflags & HF_WIDE);  // one turn from armies <= 65535: every sum of the turn stays below 2^23
   const bool emit = (A.flags & KF_EMIT) != 0u;
   uint32_t m[B::NR][4];

@@ -322,11 +322,12 @@ struct PBoard {
     }
   }
   // OwnedTiles: the board's ownership unless the header says otherwise (HF_LDIFF: a second round trip, for the few
-  // envs an aborted turn has left out of step, H6).  Needs hflags and own[].
+  // envs an aborted turn has left out of step, H6).  Needs hflags and own[].  ORD: an ordinary turn's flag is clear.
+  template <int ORD = 0>
   __device__ __forceinline__ void load_lists(const uint32_t* rows_env, int fd) {
 #pragma unroll
     for (int k = 0; k < NR; ++k) lst[k] = own[k];
-    if (hflags & HF_LDIFF) {
+    if (!ORD && (hflags & HF_LDIFF)) {
       const uint32_t* lane_base = rows_env + (row() * fd + col());
 #pragma unroll
       for (int k = 0; k < NR; ++k) {
@@ -342,6 +343,38 @@ struct PBoard {
     for (int k = 0; k < NR; ++k)
       if (col() < fd && (k * PPR + row() < MAXP)) gp[(PL::LST + k * PPR) * fd] = lst[k];
   }
+  // ---- the ORDINARY turn (GVEC_ORDTURN, gvec_device.hpp) ------------------------------------------------------------
+  // Wave-uniform, from the header words alone (decode_hdr_scalar: no vector result is waited for), BEFORE the turn is
+  // counted: the env is live, its armies are in narrow form, its lists equal its ownership (lists_match() holds without
+  // looking: load_lists copies them), its stats are in sync, V holds at most a tile per player and stays below the
+  // fog's threshold (P <= N / 10), the board has few special tiles, and the turn about to be played is not turn 0 -
+  // nor, with NOGROW, a growth turn.  turn_step<ORD> and its phases fold exactly these facts; whatever the turn itself
+  // brings about (two moves on one tile, an elimination, an abort, an army beyond u16) stays a run-time test there.
+  // tests/_ordinary_turn.py restates it.
+  // turn t is a growth turn (production_manager.go:27).  interval_magic = ceil(2^32 / interval) (host): t % interval
+  // without the vector unit's float reciprocal (a scalar `%` by a run-time value compiles to v_cvt / v_rcp / v_mul / v_cvt +
+  // 20 scalar instructions).  q = mulhi(t, magic) is floor(t / interval) or one more while t * interval < 2^32; beyond
+  // that the plain `%`.
+  static __device__ __forceinline__ bool growth_turn(int t, int interval, uint32_t interval_magic) {
+    bool g;
+    if ((uint32_t)t < 0x10000u && (uint32_t)interval < 0x10000u) {
+      const uint32_t q = __umulhi((uint32_t)t, interval_magic);  // wave-uniform operands: s_mul_hi_u32
+      int32_t r = t - (int32_t)(q * (uint32_t)interval);
+      r = r < 0 ? r + interval : r;
+      g = r == 0;
+    } else {
+      g = (t % interval) == 0;  // :27
+    }
+    return g;
+  }
+  template <int ORD>
+  __device__ __forceinline__ bool ordinary_turn(const StepArgs& A) const {
+    constexpr uint32_t need = HF_SYNC | HF_VSMALL | HF_FEWSPECIAL, bar = HF_DONE | HF_WIDE | HF_LDIFF;
+    bool ord = (hflags & (need | bar)) == need && turn >= 0 && 10 * P <= N;
+    if constexpr ((ORD & GVEC_OT_NOGROW) != 0) ord = ord && !growth_turn(turn + 1, A.interval, A.interval_magic);
+    return ord;
+  }
+
   // shared plane j (CHG + j), replicated in every row
   // (VALU: the swaps of one shp register are shared by the planes it holds - three serve four planes at ROWL 16)
   __device__ __forceinline__ uint32_t shared_plane(int j) const {
@@ -401,8 +434,9 @@ struct PBoard {
   // narrow (u16 pairs) / wide (int32 escape) army storage: load_army / store_army, gvec_device.hpp "army storage"
   template <bool HALF_LAST = false>
   __device__ __forceinline__ void load_army_narrow(const ArmyCRef& a) { army_load_narrow<NSLOT, HALF_LAST>(army, a.n); }  // needs no header
+  template <int ORD = 0>
   __device__ __forceinline__ void load_army_wide_if_flagged(const ArmyCRef& a) {
-    if (hflags & HF_WIDE) army_load_wide<NSLOT>(army, a.w);
+    if (!ORD && (hflags & HF_WIDE)) army_load_wide<NSLOT>(army, a.w);
   }
 
   // ---- LDS army shadow of the action phase ---------------------------------------------------------
@@ -460,10 +494,12 @@ struct PBoard {
 
   // ---- Engine.updateFogOfWarOptimized (visibility_optimized.go:16-97) ---------------------------------
   // matched: lists_match() holds (the caller needs it too)
+  // ORD (here and below): the turn is an ordinary one (ordinary_turn) - what that says is folded in
+  template <int ORD = 0>
   __device__ __forceinline__ void update_fog(bool matched = false) {
     if (!(hflags & HF_FOG)) return;  // :17-19
     bool full, none;
-    if ((hflags & HF_VSMALL) && turn > 0 && P <= N / 10) {  // at most P tiles in V: below the threshold whatever they are
+    if (ORD || ((hflags & HF_VSMALL) && turn > 0 && P <= N / 10)) {  // at most P tiles in V: below the threshold whatever they are
       full = false;
       none = !any_bit(vch);
     } else {
@@ -550,15 +586,16 @@ struct PBoard {
   //   went through act_vector (or nobody moved): ArmyCount' = ArmyCount + move_delta + rate * |produced tiles the player
   //   holds now| - what the sums over the new lists give, without visiting the armies.  Lists that did not change keep
   //   Alive / GeneralIdx as the last pass left them.
+  template <int ORD = 0>
   __device__ __forceinline__ void update_stats(bool end_of_turn = false, bool delta = false) {
     bool full;
-    if (end_of_turn && !grow && (hflags & HF_FEWSPECIAL) && turn > 0) {
+    if (end_of_turn && !grow && (ORD || ((hflags & HF_FEWSPECIAL) && turn > 0))) {
       if (!any_bit(chg)) return;  // :10-14
       full = false;               // |C| <= 2P + generals + cities <= N/5
     } else {
       const int nc = count_shared(chg);
-      if (nc == 0 && turn > 0) return;       // :10-14
-      full = turn == 0 || nc > N / 5;        // :20-21
+      if (nc == 0 && (ORD || turn > 0)) return;       // :10-14
+      full = (!ORD && turn == 0) || nc > N / 5;        // :20-21
     }
     uint32_t moved = 0u;
 #pragma unroll
@@ -587,7 +624,7 @@ struct PBoard {
       int32_t acc[MAXP];
 #pragma unroll
       for (int p = 0; p < MAXP; ++p) acc[p] = 0;
-      if (small) {  // bit * army + acc in one full-rate v_mad_u32_u24
+      if (ORD || small) {  // bit * army + acc in one full-rate v_mad_u32_u24
 #pragma unroll
         for (int s = 0; s < NSLOT; ++s) {
 #pragma unroll
@@ -623,18 +660,10 @@ struct PBoard {
   }
 
   // ---- ProductionManager.ProcessTurnProduction (production_manager.go:26-101) ------------------------
-  // interval_magic = ceil(2^32 / interval) (host): turn % interval without the vector unit's float reciprocal
-  // (a scalar `%` by a run-time value compiles to v_cvt / v_rcp / v_mul / v_cvt + 20 scalar instructions).
-  // q = mulhi(turn, magic) is floor(turn / interval) or one more while turn * interval < 2^32; beyond that the plain `%`.
+  template <int ORD = 0>
   __device__ __forceinline__ void production(int pg, int pc, int pn, int interval, uint32_t interval_magic) {
-    if ((uint32_t)turn < 0x10000u && (uint32_t)interval < 0x10000u) {
-      const uint32_t q = __umulhi((uint32_t)turn, interval_magic);  // wave-uniform operands: s_mul_hi_u32
-      int32_t r = turn - (int32_t)(q * (uint32_t)interval);
-      r = r < 0 ? r + interval : r;
-      grow = r == 0;
-    } else {
-      grow = (turn % interval) == 0;  // :27
-    }
+    if constexpr ((ORD & GVEC_OT_NOGROW) != 0) grow = false;  // ordinary_turn<ORD> looked
+    else grow = growth_turn(turn, interval, interval_magic);
     uint32_t listed_alive = 0u;                // :39-45: lists of alive players, owner NOT re-checked (H7)
 #pragma unroll
     for (int k = 0; k < NR; ++k) listed_alive |= lane_flag(alive, k) ? lst[k] : 0u;
@@ -886,17 +915,20 @@ struct PBoard {
   __device__ __forceinline__ uint32_t turn_step(uint32_t acts_lo, uint32_t acts_hi, const StepArgs& A, bool& aborted) {
     return turn_step(prevalidate(acts_lo, acts_hi), A, aborted);
   }
+  // ORD: the caller found ordinary_turn<ORD>() true on the state as loaded.  Every mid-turn event leaves the straight line
+  // through the same run-time tests as the general code, on the same PBoard members: nothing is handed over.
   // av: lane p holds player p's move after the static checks (prevalidate, or the on-device agent's own output)
+  template <int ORD = 0>
   __device__ __forceinline__ uint32_t turn_step(const ActVec& av, const StepArgs& A, bool& aborted) {
     aborted = false;
     turn++;  // initializeTurn :124-135
-    const bool matched = lists_match(*this);
-    if (!(GVEC_PROFILE_SKIP & 2)) update_fog(matched);
-    if (GVEC_PROFILE_DUP & 2) { opaque(); update_fog(matched); }
+    const bool matched = ORD ? true : lists_match(*this);
+    if (!(GVEC_PROFILE_SKIP & 2)) update_fog<ORD>(matched);
+    if (GVEC_PROFILE_DUP & 2) { opaque(); update_fog<ORD>(matched); }
     chg = 0u;
     vch = 0u;
     hflags |= HF_VSMALL;  // the moves add one captured tile per player at most; a turnover clears the flag
-    bool delta = matched && (hflags & HF_SYNC) != 0u;
+    bool delta = ORD ? true : matched && (hflags & HF_SYNC) != 0u;
     move_delta = 0;
     uint32_t first_err = 0u, elim_seen = 0u;
     uint64_t orders = 0ull;
@@ -913,16 +945,16 @@ struct PBoard {
     }
     if (n_orders > 0) {  // engine.go:101-109
       eliminate(orders, n_orders);
-      update_stats();
+      update_stats<ORD>();
     }
     if (first_err) {  // engine.go:111-113 -> turn_processor.go:55-57: production, stats, game-over skipped (H5)
       if (n_orders == 0) hflags &= ~HF_SYNC;  // armies moved and no pass followed
       aborted = true;
       return first_err;
     }
-    if (!(GVEC_PROFILE_SKIP & 8)) production(A.prod_general, A.prod_city, A.prod_normal, A.interval, A.interval_magic);  // :60
-    if (!(GVEC_PROFILE_SKIP & 16)) update_stats(n_orders == 0, delta && n_orders == 0);                  // :65,170-179
-    if (GVEC_PROFILE_DUP & 16) { opaque_v(); update_stats(n_orders == 0, false); }
+    if (!(GVEC_PROFILE_SKIP & 8)) production<ORD>(A.prod_general, A.prod_city, A.prod_normal, A.interval, A.interval_magic);  // :60
+    if (!(GVEC_PROFILE_SKIP & 16)) update_stats<ORD>(n_orders == 0, delta && n_orders == 0);                  // :65,170-179
+    if (GVEC_PROFILE_DUP & 16) { opaque_v(); update_stats<ORD>(n_orders == 0, false); }
     check_game_over();
     return 0u;
   }

@@ -112,9 +112,27 @@ __device__ __forceinline__ void load_board(BT& b, const uint32_t* hdr, const uin
 // trip per board instead of two, worth 10 % there (one-process A/B: 338.7 -> 305.6 us per 262,144 boards).  The fused
 // rollout amortises its loads over many turns and runs 4 % faster with the plain order (fewer live registers).
 // HALF_LAST (EARLY only): the board has at most 32*(2*NSLOT-1) tiles - see army_load_narrow.
+// The EARLY order in its two halves: everything up to the point where the header words have landed (where the per-turn
+// kernel decides what kind of turn this is, PBoard::ordinary_turn), and the tail that depends on the header's flags -
+// ORD: of an ordinary turn, which has neither list planes nor wide armies to fetch.
+template <bool HALF_LAST, typename BT>
+__device__ __forceinline__ void load_turn_issue(BT& b, const uint32_t* hdr, const uint32_t* rows, const ArmyCRef& army, int fd, const uint32_t* zeros) {
+  b.issue_hdr(hdr);
+  b.load_planes(rows, fd, zeros);
+  b.template load_army_narrow<HALF_LAST>(army);
+  b.decode_hdr_scalar(hdr);   // SMEM: in flight with the vector loads above
+  b.land();
+  b.land_scalars();
+}
+template <int ORD, typename BT>
+__device__ __forceinline__ void load_turn_tail(BT& b, const uint32_t* rows, const ArmyCRef& army, int fd) {
+  b.spread_shared();
+  b.template load_lists<ORD>(rows, fd);
+  b.template load_army_wide_if_flagged<ORD>(army);
+}
 template <bool EARLY = false, bool HALF_LAST = false, typename BT>
 __device__ __forceinline__ void load_turn(BT& b, const uint32_t* hdr, const uint32_t* rows, const ArmyCRef& army, int fd, const uint32_t* zeros) {
-  if constexpr (EARLY) {
+  if constexpr (EARLY) {  // load_turn_issue + load_turn_tail<0>, statement for statement
     b.issue_hdr(hdr);
     b.load_planes(rows, fd, zeros);
     b.template load_army_narrow<HALF_LAST>(army);
