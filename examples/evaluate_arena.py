@@ -82,6 +82,8 @@ def main(argv=None):
     ap.add_argument("--random", action="count", default=0, help="add an entrant that plays uniformly over its legal moves (repeatable)")
     ap.add_argument("--playouts", metavar="K:R:D", default=None,
                     help="add a playout-search entrant: K candidates, R playouts each, D turns deep; its prior is the first checkpoint")
+    ap.add_argument("--playout-rollout", choices=("agent", "bot"), default="agent",
+                    help="what the playouts play after the candidate: the random agent, or the scripted opponent's rule on every seat")
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--board", type=int, default=15)
     ap.add_argument("--players", type=int, default=2)
@@ -97,7 +99,7 @@ def main(argv=None):
     names = [os.path.basename(p) for p in a.checkpoints] + [f"random-{k}" for k in range(a.random)]
     krd = parse_playouts(a.playouts) if a.playouts else None
     if krd:
-        names.append("playouts-%d:%d:%d" % krd)
+        names.append(("playouts-bot-%d:%d:%d" if a.playout_rollout == "bot" else "playouts-%d:%d:%d") % krd)
     if not names:
         raise SystemExit("nothing to evaluate: give checkpoints and / or --random")
     entrants = [load_entrant(p, a.board, dev, a.greedy, a.seed + k) for k, p in enumerate(a.checkpoints)]
@@ -106,7 +108,8 @@ def main(argv=None):
                                  seed=a.seed, device_outputs=True)
     if krd:
         prior = load_net(a.checkpoints[0], a.board, dev) if a.checkpoints else None
-        entrants.append(playout_policy(PlayoutSearch(env, candidates=krd[0], replicas=krd[1], depth=krd[2]), net=prior, seed=a.seed + 2000))
+        search = PlayoutSearch(env, candidates=krd[0], replicas=krd[1], depth=krd[2], rollout=a.playout_rollout)
+        entrants.append(playout_policy(search, net=prior, seed=a.seed + 2000))
     arena = Arena(env, entrants, names=names)
     steps = arena.run(episodes_per_env=a.episodes, poll_every=a.poll_every, max_steps=a.max_steps)
     res = arena.results()

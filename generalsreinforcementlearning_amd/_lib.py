@@ -212,6 +212,7 @@ SYMBOLS = {
     "gvec_agent_actions": (_i32, [_vp, _u64, _i32, _vp, _i32]),
     "gvec_bot_actions": (_i32, [_vp, C.c_uint32, _u64, _i32, _vp, _i32]),
     "gvec_search_playouts": (_i32, [_vp, C.POINTER(SearchArgs)]),
+    "gvec_search_playouts_bot": (_i32, [_vp, C.POINTER(SearchArgs), C.c_uint32, _i32]),
     "gvec_counters": (_i32, [_vp, C.POINTER(RolloutStats)]),
     "gvec_step_traffic_bytes": (_i32, [_vp, C.POINTER(C.c_int64)]),
     "gvec_experience_begin": (_i32, [_vp]),

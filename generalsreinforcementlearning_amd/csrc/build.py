@@ -23,7 +23,7 @@ SRCS = ["gvec_kernels.hip", "gvec_gym.hip", "gvec_experience.hip", "gvec_state.h
         "gvec_api.hip", "gvec_api_engine.hip", "gvec_api_state.hip", "gvec_api_experience.hip", "gvec_api_gym.hip", "gvec_api_replay.hip",
         "gvec_api_obs.hip"]
 DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_handle.hpp", "gvec_dispatch.hpp", "gvec_turn.hpp", "gvec_gym_emit.hpp", "gvec_collect.hpp",
-        "gvec_waves.hpp", "gvec_rows.hpp",
+        "gvec_waves.hpp", "gvec_rows.hpp", "gvec_bot.hpp",
         "go_rand_cooked.inc", os.path.join(ROOT, "include", "generals_vec.h")]
 HOST_DEPS = ["gvec_handle.hpp"]  # included by the gvec_api* units alone: an edit to it recompiles no kernel either
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",

@@ -448,9 +448,13 @@ int32_t gvec_bot_actions(gvec_handle* h, uint32_t players, uint64_t seed, int32_
   return GVEC_OK;
 }
 
-int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args) {
-  static const char* fn = "gvec_search_playouts";
-  // the arguments first, the handle last: every check of a field holds without a device
+}  // extern "C"
+
+// The checks of gvec_search_args that both search entry points make, under the caller's name: the arguments first, the handle
+// last, so that every check of a field holds without a device.  `tail` is the caller's own checks of its further
+// arguments, made after the struct's and before the handle; it sets the message itself.
+template <typename Tail>
+static int32_t search_check(const char* fn, gvec_handle* h, const gvec_search_args* args, Tail tail) {
   if (!args) {
     set_err("%s: args is NULL", fn);
     return GVEC_E_INVALID;
@@ -484,17 +488,19 @@ int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args) {
             args->replicas);
     return GVEC_E_INVALID;
   }
+  if (const int32_t rc = tail()) return rc;
   if (!h) {
     set_err("%s: h is NULL", fn);
     return GVEC_E_INVALID;
   }
-  if (h->sharded()) return sharded::unsupported(fn);
-  if (args->num_roots == 0) return GVEC_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  StepArgs a = base_args(h);
+  return GVEC_OK;
+}
+
+// the launch arguments of a checked call on an unsharded handle
+static void search_launch_args(gvec_handle* h, const gvec_search_args* args, StepArgs& a, SearchArgs& g) {
+  a = base_args(h);
   a.flags = KF_AGENT;   // no re-deal, no mask emission: the kernel writes terms alone
   set_agent_seed(&a, args->seed, 0);
-  SearchArgs g;
   g.root_envs = args->root_envs;
   g.root_players = args->root_players;
   g.candidates = args->candidates;
@@ -502,9 +508,52 @@ int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args) {
   g.num_candidates = args->num_candidates;
   g.replicas = args->replicas;
   g.depth = args->depth;
-  g.num_playouts = (int32_t)((long long)args->num_roots * kr);
+  g.num_playouts = (int32_t)((long long)args->num_roots * args->num_candidates * args->replicas);
   g.stride = h->stride;
+}
+
+extern "C" {
+
+int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args) {
+  static const char* fn = "gvec_search_playouts";
+  if (const int32_t rc = search_check(fn, h, args, [] { return (int32_t)GVEC_OK; })) return rc;
+  if (h->sharded()) return sharded::unsupported(fn);
+  if (args->num_roots == 0) return GVEC_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  StepArgs a;
+  SearchArgs g;
+  search_launch_args(h, args, a, g);
   HIPCHK(launch_search(h->var, a, g, h->stream));
+  return GVEC_OK;
+}
+
+int32_t gvec_search_playouts_bot(gvec_handle* h, const gvec_search_args* args, uint32_t bot_players, int32_t bot_random_permille) {
+  static const char* fn = "gvec_search_playouts_bot";
+  // gvec_bot_actions' two checks in its wording; the seat mask against the largest handle first, which needs no handle
+  const auto seats_above = [&](int maxp) {
+    if (maxp >= 32 || (bot_players >> maxp) == 0u) return (int32_t)GVEC_OK;
+    set_err("%s: bot_players names a seat at or above max_players", fn);
+    return (int32_t)GVEC_E_INVALID;
+  };
+  const auto tail = [&] {
+    if (bot_random_permille < 0 || bot_random_permille > 1000) {
+      set_err("%s: bot_random_permille must be in [0, 1000]", fn);
+      return (int32_t)GVEC_E_INVALID;
+    }
+    return seats_above(GVEC_MAX_PLAYERS);
+  };
+  if (const int32_t rc = search_check(fn, h, args, tail)) return rc;
+  if (const int32_t rc = seats_above(h->maxp)) return rc;
+  if (h->sharded()) return sharded::unsupported(fn);
+  if (args->num_roots == 0) return GVEC_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  StepArgs a;
+  SearchArgs g;
+  search_launch_args(h, args, a, g);
+  BotArgs bot;
+  bot.players = bot_players;
+  bot.random_permille = bot_random_permille;
+  HIPCHK(launch_search_bot(h->var, a, g, bot, h->stream));
   return GVEC_OK;
 }
 

@@ -153,6 +153,8 @@ struct SearchArgs {
 };
 // a.seed_lo / seed_hi: the call's seed; a.env_base is ignored (the playout index is the key)
 hipError_t launch_search(const Variant& v, const StepArgs& a, const SearchArgs& g, hipStream_t s);
+// ... with the seats of bot.players on the scripted opponent's rule in every playout turn (gvec_search_playouts_bot)
+hipError_t launch_search_bot(const Variant& v, const StepArgs& a, const SearchArgs& g, const BotArgs& bot, hipStream_t s);
 
 // internal/experience side channel
 struct ExperienceArgs {

@@ -1,6 +1,8 @@
-// gvec_search.hip — flat Monte Carlo search (gvec_search_playouts): one wavefront per playout loads a root
-// board read-only, plays one candidate action for one seat, then random-agent turns, and writes back eight numbers instead
-// of a board.
+// gvec_search.hip — flat Monte Carlo search (gvec_search_playouts, gvec_search_playouts_bot): one
+// wavefront per playout loads a root board read-only, plays one candidate action for one seat, then random-agent turns - or
+// turns in which named seats play the scripted opponent's rule (gvec_bot.hpp) - and writes back eight numbers instead of a
+// board.
+#include "gvec_bot.hpp"
 #include "gvec_dispatch.hpp"
 #include "gvec_turn.hpp"
 
@@ -18,54 +20,42 @@ namespace gvec {
 //   turns 1 .. depth - 1: rollout_kernel's inner loop.  A finished game ends the playout; it is never re-dealt.
 //   terms[v][8]: valid, turns, alive, won, land, army, land_others, army_others - the counts from the sources the gym
 //           kernels use (turn_tile_counts, army_counts)
-template <int MAXP, int NSLOT>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>())) void search_kernel(StepArgs A, SearchArgs S) {
-  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
-  using B = Turn<MAXP, NSLOT>;
-  __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
-  const int wave = block_wave(), lane = lane_id();
-  const int v = wave_item();
-  if (v >= S.num_playouts) return;
+// What the two kernels share is the helpers below; only the turn loop differs.  They take and return plain values: a helper
+// that returns the row through references, or one that holds the two early returns, compiles search_kernel to other
+// instructions than before (all 18 instantiations), and these do not.
+
+// playout v's root i (returned) and candidate k
+__device__ __forceinline__ int search_root_index(const SearchArgs& S, int v, int& k) {
   const int per_root = S.num_candidates * S.replicas;
-  const int i = v / per_root, k = (v - i * per_root) / S.replicas;
-  const int env = S.root_envs ? uni(S.root_envs[i]) : i;
-  const int pl = uni(S.root_players[i]);
-  const long long a = (long long)uni64((uint64_t)S.candidates[(size_t)i * S.num_candidates + k]);
-  int32_t* out = S.terms + (size_t)v * GVEC_SEARCH_TERMS;
-  if (env < 0 || env >= A.num_envs) {   // wave-uniform; checked here, so that the call needs no host copy of the ids
-    if (lane < GVEC_SEARCH_TERMS) out[lane] = 0;
-    return;
-  }
-  B b;
-  b.larmy = army_shadow[wave];
-  b.lscr = act_scratch[wave];
-  load_turn(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd, A.zeros);
-  const bool seat_ok = pl >= 0 && pl < MAXP && ((b.alive >> (pl & 31)) & 1u) != 0u;
-  const int seat = seat_ok ? pl : 0;   // the view of a seat the board has: every lane takes part in the cross-lane reads below
-  const GymMove mv = gym_decode(b, gym_sources(b, turn_view(b, seat)), a, S.stride);
-  const bool pass = a == (long long)GVEC_SEARCH_PASS;
-  if (!seat_ok || (b.hflags & HF_DONE) || !(pass || mv.accepted)) {   // wave-uniform
-    if (lane < GVEC_SEARCH_TERMS) out[lane] = 0;
-    return;
-  }
-  const uint32_t c_meta = pass ? 0u : (16u | (mv.half ? 32u : 0u));
-  uint32_t m[B::NR][4];
-  const uint32_t ek = env_key_of(A.seed_base, (uint32_t)v);
-  int t = 0;
-  b.template legal_planes<false>(m);
-  while (t < S.depth && !(b.hflags & HF_DONE)) {
-    const uint32_t mine = agent_sample<MAXP, NSLOT>(b, m, ek, A);
-    typename B::ActVec av = agent_actvec<MAXP, NSLOT>(b, mine, A.invalid_permille > 0);
-    const bool cand = t == 0 && lane == seat;   // turn 0: the seat's slot is the candidate
-    av.meta = cand ? c_meta : av.meta;
-    av.ft = cand ? mv.from : av.ft;
-    av.tt = cand ? mv.tt : av.tt;
-    bool aborted;
-    (void)b.turn_step(av, A, aborted);
-    ++t;
-    b.refresh_gt1();
-    b.template legal_planes<false>(m);
-  }
+  const int i = v / per_root;
+  k = (v - i * per_root) / S.replicas;
+  return i;
+}
+__device__ __forceinline__ int search_root_env(const SearchArgs& S, int i) { return S.root_envs ? uni(S.root_envs[i]) : i; }
+__device__ __forceinline__ long long search_candidate(const SearchArgs& S, int i, int k) {
+  return (long long)uni64((uint64_t)S.candidates[(size_t)i * S.num_candidates + k]);
+}
+// an INVALID row: all zeros, nothing is played
+__device__ __forceinline__ void search_invalid_row(int32_t* out, int lane) {
+  if (lane < GVEC_SEARCH_TERMS) out[lane] = 0;
+}
+// the seat is one the board has, and alive (alive implies below the env's player count)
+template <int MAXP>
+__device__ __forceinline__ bool search_seat_ok(uint32_t alive, int pl) {
+  return pl >= 0 && pl < MAXP && ((alive >> (pl & 31)) & 1u) != 0u;
+}
+// the candidate's ActVec meta: the pass plays no move
+__device__ __forceinline__ uint32_t search_meta(bool pass, bool half) { return pass ? 0u : (16u | (half ? 32u : 0u)); }
+// turn 0 (cand: this lane is the seat's, on turn 0): the seat's slot is the candidate
+template <typename AV>
+__device__ __forceinline__ void search_override(AV& av, bool cand, uint32_t c_meta, int from, int tt) {
+  av.meta = cand ? c_meta : av.meta;
+  av.ft = cand ? from : av.ft;
+  av.tt = cand ? tt : av.tt;
+}
+// the eight terms of the board as the playout left it after t turns
+template <int MAXP, int NSLOT>
+__device__ __forceinline__ void search_terms(const Turn<MAXP, NSLOT>& b, int32_t* out, int seat, int lane, int t) {
   const uint32_t tcl = turn_tile_counts(b), acl = army_counts<MAXP>(b);
   const bool other = lane < MAXP && lane != seat;
   const uint32_t land = rdlane(tcl, seat), army = rdlane(acl, seat);
@@ -76,12 +66,130 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>()
                        : lane == 6 ? land_others : army_others;
   if (lane < GVEC_SEARCH_TERMS) out[lane] = (int32_t)val;
 }
+template <int MAXP, int NSLOT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>())) void search_kernel(StepArgs A, SearchArgs S) {
+  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
+  using B = Turn<MAXP, NSLOT>;
+  __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
+  const int wave = block_wave(), lane = lane_id();
+  const int v = wave_item();
+  if (v >= S.num_playouts) return;
+  int k;
+  const int i = search_root_index(S, v, k);
+  const int env = search_root_env(S, i);
+  const int pl = uni(S.root_players[i]);
+  const long long a = search_candidate(S, i, k);
+  int32_t* out = S.terms + (size_t)v * GVEC_SEARCH_TERMS;
+  if (env < 0 || env >= A.num_envs) {   // wave-uniform; checked here, so that the call needs no host copy of the ids
+    search_invalid_row(out, lane);
+    return;
+  }
+  B b;
+  b.larmy = army_shadow[wave];
+  b.lscr = act_scratch[wave];
+  load_turn(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd, A.zeros);
+  const bool seat_ok = search_seat_ok<MAXP>(b.alive, pl);
+  const int seat = seat_ok ? pl : 0;   // the view of a seat the board has: every lane takes part in the cross-lane reads below
+  const GymMove mv = gym_decode(b, gym_sources(b, turn_view(b, seat)), a, S.stride);
+  const bool pass = a == (long long)GVEC_SEARCH_PASS;
+  if (!seat_ok || (b.hflags & HF_DONE) || !(pass || mv.accepted)) {   // wave-uniform
+    search_invalid_row(out, lane);
+    return;
+  }
+  const uint32_t c_meta = search_meta(pass, mv.half);
+  uint32_t m[B::NR][4];
+  const uint32_t ek = env_key_of(A.seed_base, (uint32_t)v);
+  int t = 0;
+  b.template legal_planes<false>(m);
+  while (t < S.depth && !(b.hflags & HF_DONE)) {
+    const uint32_t mine = agent_sample<MAXP, NSLOT>(b, m, ek, A);
+    typename B::ActVec av = agent_actvec<MAXP, NSLOT>(b, mine, A.invalid_permille > 0);
+    search_override(av, t == 0 && lane == seat, c_meta, mv.from, mv.tt);
+    bool aborted;
+    (void)b.turn_step(av, A, aborted);
+    ++t;
+    b.refresh_gt1();
+    b.template legal_planes<false>(m);
+  }
+  search_terms<MAXP, NSLOT>(b, out, seat, lane, t);
+}
 
-hipError_t launch_search(const Variant& v, const StepArgs& in, const SearchArgs& g, hipStream_t s) {
+// The same playout with the seats of G.players on the scripted opponent's rule (gvec_search_playouts_bot):
+// every turn is gvec_agent_actions, then gvec_bot_actions(G.players, seed, G.random_permille) over it, then gvec_step, of
+// the playout's own board - env v of a scratch handle of n * K * R copies draws what playout v draws, for the agent and for
+// the exploration mix alike (both keyed by ek and the board's own turn counter).  Load, decode, invalid rows and terms are
+// search_kernel's; a second kernel, not a flag, so that search_kernel's instruction stream stays what it was.
+//   The agent's draw comes before bot_sample, which overwrites m; the turn's legal_planes refill it.
+//   Every seat the rule can move being a mover (all the living on the rule, no exploration), nobody plays the agent's draw:
+//   a seat that is not alive draws no action (agent_sample: act needs alive), so the draw is skipped - wave-uniform.
+//   A seat on the rule that finds no move plays none (word 0), as gvec_bot_actions writes it.
+template <int MAXP, int NSLOT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>())) void search_bot_kernel(StepArgs A, SearchArgs S, BotArgs G) {
+  __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
+  using B = Turn<MAXP, NSLOT>;
+  __shared__ uint32_t act_scratch[WAVES_PER_BLOCK][B::ACT_SCRATCH_DW];
+  const int wave = block_wave(), lane = lane_id();
+  const int v = wave_item();
+  if (v >= S.num_playouts) return;
+  int k;
+  const int i = search_root_index(S, v, k);
+  const int env = search_root_env(S, i);
+  const int pl = uni(S.root_players[i]);
+  const long long a = search_candidate(S, i, k);
+  int32_t* out = S.terms + (size_t)v * GVEC_SEARCH_TERMS;
+  if (env < 0 || env >= A.num_envs) {   // wave-uniform; checked here, so that the call needs no host copy of the ids
+    search_invalid_row(out, lane);
+    return;
+  }
+  B b;
+  b.larmy = army_shadow[wave];
+  b.lscr = act_scratch[wave];
+  load_turn(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * A.row_dw, army_cref<NSLOT>(A.army16, A.army32, env), A.fd, A.zeros);
+  const bool seat_ok = search_seat_ok<MAXP>(b.alive, pl);
+  const int seat = seat_ok ? pl : 0;   // the view of a seat the board has: every lane takes part in the cross-lane reads below
+  const GymMove mv = gym_decode(b, gym_sources(b, turn_view(b, seat)), a, S.stride);
+  const bool pass = a == (long long)GVEC_SEARCH_PASS;
+  if (!seat_ok || (b.hflags & HF_DONE) || !(pass || mv.accepted)) {   // wave-uniform
+    search_invalid_row(out, lane);
+    return;
+  }
+  const uint32_t c_meta = search_meta(pass, mv.half);
+  uint32_t m[B::NR][4];
+  const uint32_t ek = env_key_of(A.seed_base, (uint32_t)v);
+  int t = 0;
+  b.template legal_planes<false>(m);
+  while (t < S.depth && !(b.hflags & HF_DONE)) {
+    const uint32_t rnd_bits = G.random_permille > 0 ? bot_random_seats<MAXP>(ek, (uint32_t)b.turn, G.random_permille) : 0u;
+    const uint32_t movers = G.players & b.alive & ~rnd_bits;
+    uint32_t agent_mine = 0u;
+    if (movers != b.alive) agent_mine = agent_sample<MAXP, NSLOT>(b, m, ek, A);   // somebody alive plays the agent's draw
+    const uint32_t bot_mine = bot_sample<MAXP, NSLOT>(b, m, movers);
+    const uint32_t mine = ((movers >> lane) & 1u) ? bot_mine : agent_mine;
+    typename B::ActVec av = agent_actvec<MAXP, NSLOT>(b, mine, A.invalid_permille > 0);
+    search_override(av, t == 0 && lane == seat, c_meta, mv.from, mv.tt);
+    bool aborted;
+    (void)b.turn_step(av, A, aborted);
+    ++t;
+    b.refresh_gt1();
+    b.template legal_planes<false>(m);
+  }
+  search_terms<MAXP, NSLOT>(b, out, seat, lane, t);
+}
+
+static StepArgs search_keyed(const StepArgs& in) {
   StepArgs keyed = in;
   keyed.env_base = 0;   // the playout index is the key, whichever handle the roots live in
-  const StepArgs a = with_seed_bases(keyed);
+  return with_seed_bases(keyed);
+}
+
+hipError_t launch_search(const Variant& v, const StepArgs& in, const SearchArgs& g, hipStream_t s) {
+  const StepArgs a = search_keyed(in);
   return dispatch(v, [&](auto P, auto S) { return launch_waves(search_kernel<P, S>, g.num_playouts, s, a, g); });
+}
+
+hipError_t launch_search_bot(const Variant& v, const StepArgs& in, const SearchArgs& g, const BotArgs& bot, hipStream_t s) {
+  const StepArgs a = search_keyed(in);
+  return dispatch(v, [&](auto P, auto S) { return launch_waves(search_bot_kernel<P, S>, g.num_playouts, s, a, g, bot); });
 }
 
 }  // namespace gvec

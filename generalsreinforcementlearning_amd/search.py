@@ -24,13 +24,19 @@ T_VALID, T_TURNS, T_ALIVE, T_WON, T_LAND, T_ARMY, T_LAND_OTHERS, T_ARMY_OTHERS =
 
 
 def search_playouts_device(engine, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed=0,
-                           root_envs_ptr=None):
+                           root_envs_ptr=None, bot_players=0, bot_random_permille=0):
     """gvec_search_playouts on device memory (VecEngine.search_playouts_device): pointers are ints or None; enqueued on the
-    engine's stream, not synchronised."""
+    engine's stream, not synchronised.  With bot_players (a seat mask) or bot_random_permille set: gvec_search_playouts_bot,
+    whose playouts play the scripted opponent's rule on those seats."""
     a = SearchArgs(num_roots=int(num_roots), num_candidates=int(num_candidates), replicas=int(replicas), depth=int(depth),
                    root_envs=root_envs_ptr, root_players=root_players_ptr, candidates=candidates_ptr, seed=int(seed) & (2 ** 64 - 1),
                    terms=terms_ptr)
-    check(engine.L.gvec_search_playouts(engine.h, C.byref(a)), "gvec_search_playouts")
+    if not bot_players and not bot_random_permille:
+        check(engine.L.gvec_search_playouts(engine.h, C.byref(a)), "gvec_search_playouts")
+        return
+    if not 0 <= int(bot_players) < 2 ** 32:
+        raise ValueError(f"bot_players must be a mask of seats below 32, not {bot_players!r}")
+    check(engine.L.gvec_search_playouts_bot(engine.h, C.byref(a), int(bot_players), int(bot_random_permille)), "gvec_search_playouts_bot")
 
 
 def _terms_tensor(terms):
@@ -84,13 +90,25 @@ def _uniform_keys(seed, n, A, device):
 
 
 class PlayoutSearch:
-    def __init__(self, env_or_engine, candidates=8, replicas=4, depth=8, score=None):
+    def __init__(self, env_or_engine, candidates=8, replicas=4, depth=8, score=None, rollout="agent", bot_players=None,
+                 bot_random_permille=0):
         """env_or_engine: a gym vector env (GeneralsVecEnv / GeneralsSelfPlayVecEnv with device_outputs=True; rows are its
         (env, learner column) pairs) or a VecEngine (rows are (env, seat) pairs the caller names).  candidates K, replicas R
-        and depth D >= 1: every evaluated row costs K * R playouts of at most D turns."""
+        and depth D >= 1: every evaluated row costs K * R playouts of at most D turns.
+        rollout: "agent" - every seat of a playout plays the random agent (gvec_search_playouts) - or "bot": the seats of
+        bot_players (seat ids or a bit mask; None: every seat) play the scripted opponent's rule in every playout turn, each
+        with probability bot_random_permille / 1000 the agent's move instead (gvec_search_playouts_bot).  The searched seat's
+        candidate is played on the first turn either way."""
         for name, v in (("candidates", candidates), ("replicas", replicas), ("depth", depth)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1, not {v!r}")
+        if rollout not in ("agent", "bot"):
+            raise ValueError(f"rollout must be 'agent' or 'bot', not {rollout!r}")
+        if isinstance(bot_random_permille, bool) or not isinstance(bot_random_permille, (int, np.integer)) \
+                or not 0 <= bot_random_permille <= 1000:
+            raise ValueError(f"bot_random_permille must be an int in [0, 1000], not {bot_random_permille!r}")
+        if rollout == "agent" and (bot_players is not None or bot_random_permille != 0):
+            raise ValueError("bot_players and bot_random_permille need rollout='bot'")
         self.K, self.R, self.D = int(candidates), int(replicas), int(depth)
         self.score = PlayoutScore() if score is None else score
         self.env = env_or_engine if hasattr(env_or_engine, "engine") else None
@@ -98,6 +116,25 @@ class PlayoutSearch:
         e = self.engine
         self.W, self.H, self.num_actions = int(e.max_w), int(e.max_h), 5 * int(e.max_w) * int(e.max_h)
         self._ids = None
+        self.rollout, self.bot_random_permille = rollout, int(bot_random_permille)
+        self.bot_players = 0 if rollout == "agent" else self._seat_mask(bot_players, int(e.max_p))
+
+    @staticmethod
+    def _seat_mask(players, max_p):
+        """the bit mask of seats below max_p from None (all of them), an int mask or an iterable of seat ids"""
+        if players is None:
+            return (1 << max_p) - 1
+        if isinstance(players, (int, np.integer)) and not isinstance(players, bool):
+            mask = int(players)
+        else:
+            mask = 0
+            for p in players:
+                if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= p < max_p:
+                    raise ValueError(f"seat {p!r} is not an int below max_players = {max_p}")
+                mask |= 1 << int(p)
+        if not 0 <= mask < (1 << max_p):
+            raise ValueError(f"bot_players {mask:#x} names a seat at or above max_players = {max_p}")
+        return mask
 
     # ---- argument checks (before any library call) ---------------------------------------------------------------------
     def _device(self):
@@ -137,8 +174,9 @@ class PlayoutSearch:
         terms = torch.empty((n, self.K, self.R, SEARCH_TERMS), dtype=torch.int32, device=dev)
         if n == 0:                      # nothing to play (an empty tensor has no address to hand over)
             return terms
+        bot = {} if self.rollout == "agent" else dict(bot_players=self.bot_players, bot_random_permille=self.bot_random_permille)
         self.engine.search_playouts_device(n, cand.data_ptr(), players.data_ptr(), terms.data_ptr(), self.K, self.R, self.D, seed,
-                                           None if env_ids is None else env_ids.data_ptr())
+                                           None if env_ids is None else env_ids.data_ptr(), **bot)
         return terms
 
     # ---- reductions (torch, on whatever device holds the terms) ---------------------------------------------------------

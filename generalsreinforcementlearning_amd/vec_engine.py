@@ -343,14 +343,17 @@ class VecEngine:
               "gvec_bot_actions")
 
     def search_playouts_device(self, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed=0,
-                               root_envs_ptr=None):
+                               root_envs_ptr=None, bot_players=0, bot_random_permille=0):
         """gvec_search_playouts (flat Monte Carlo search; search.PlayoutSearch is the front): for root i < num_roots - env
         root_envs[i], None: env i - candidate k and replica j, one playout that plays candidates[i][k] for seat
         root_players[i], then random-agent turns up to `depth`, into terms[i][k][j][8] (search.TERM_NAMES).  Device pointers
         (ints): int32 [n], int32 [n], int64 [n][K], int32 [n][K][R][8].  The engine's envs are read only.  Enqueued on the
-        engine's stream, not synchronised."""
+        engine's stream, not synchronised.  bot_players (a bit mask of seats) or bot_random_permille set: gvec_search_playouts_bot
+        - those seats play the scripted opponent's rule in every playout turn, mixed with the agent's moves as bot_actions
+        mixes them; with both 0 the call is gvec_search_playouts."""
         from .search import search_playouts_device
-        search_playouts_device(self, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed, root_envs_ptr)
+        search_playouts_device(self, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed, root_envs_ptr,
+                               bot_players, bot_random_permille)
 
     def rollout(self, turns, seed, invalid_permille=0, fused=True, want_stats=True):
         st = RolloutStats()

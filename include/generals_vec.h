@@ -359,6 +359,17 @@ typedef struct gvec_search_args {
   int32_t* terms;               /* device [n][K][R][GVEC_SEARCH_TERMS] */
 } gvec_search_args;
 int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args);
+/* The same search with playouts that play the game: in every playout turn the seats whose bit is set in bot_players (an
+ * absolute seat mask, gvec_bot_actions' `players`) play the scripted opponent's rule instead of the random agent's draw -
+ * each with probability bot_random_permille / 1000 the agent's draw after all, as gvec_bot_actions mixes it.  The searched
+ * seat's candidate still replaces its slot on the first turn, whether the seat is on the rule or not.  The call equals
+ * gvec_copy_envs of the roots into a scratch handle of n*K*R envs and then, per turn, gvec_agent_actions(seed, 0),
+ * gvec_bot_actions(bot_players, seed, bot_random_permille) over its result, the candidate on the first turn, gvec_step -
+ * bit for bit, in one launch: env v of the scratch handle draws what playout v draws, for the agent and for the mix.
+ * bot_players == 0 gives gvec_search_playouts' terms.  Everything else - args, terms, invalid rows, read-only roots - is as
+ * above.  GVEC_E_INVALID, besides the cases above: bot_random_permille outside [0, 1000], a bit of bot_players at or above
+ * max_players. */
+int32_t gvec_search_playouts_bot(gvec_handle* h, const gvec_search_args* args, uint32_t bot_players, int32_t bot_random_permille);
 
 /* ---- internal/experience side channel ------------------------------
  * gvec_experience_begin   = TurnProcessor.captureStateForExperience

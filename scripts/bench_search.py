@@ -19,7 +19,13 @@ Rates: playout env-steps/s = turns actually played (the sum of the `turns` term)
 fused rollout's env-steps/s on the scratch engine (n * K * R envs, `depth` turns, the same kernel variant).
   --strength   Arena: playout_policy (uniform prior, --playouts K:R:D) against random_policy on a two-player self-play env; and
                the same searcher as the learner of a GeneralsVecEnv whose other seat is the scripted bot.  Fixed seeds.
-usage: scripts/bench_search.py [--configs roots:K:R:D:WxH:players,...] [--calls N] [--repeats R] [--strength] [--out profiles/search_bench.json]"""
+  --rollout bot   the search whose playouts play the scripted opponent's rule on every seat (gvec_search_playouts_bot,
+               search_bot_kernel) against ITS composition: copy_envs, then per playout turn the agent's moves, gvec_bot_actions
+               over them (both into device memory), the candidate on turn 0, one step; and beside both the agent-playout search
+               of the same shape (`agent_search`), for the price of a playout turn.  With --strength every match is played once
+               with each rollout, in the same run.  Write it to profiles/search_bot_bench.json.
+usage: scripts/bench_search.py [--configs roots:K:R:D:WxH:players,...] [--calls N] [--repeats R] [--rollout agent|bot] [--strength]
+                               [--out profiles/search_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -36,6 +42,7 @@ ap.add_argument("--calls", type=int, default=10)
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--age", type=int, default=60)
 ap.add_argument("--strength", action="store_true")
+ap.add_argument("--rollout", choices=("agent", "bot"), default="agent")
 ap.add_argument("--playouts", default="8:4:8")
 ap.add_argument("--strength-envs", type=int, default=1024)
 ap.add_argument("--strength-episodes", type=int, default=2)
@@ -75,8 +82,9 @@ def aged_roots(n, W, H, P, age, seed=7):
 class Composition:
     """the same terms from copy_envs + step + fused rollout + read_state + torch, every buffer allocated once"""
 
-    def __init__(self, engine, n, K, R, D, W, H, P, players):
+    def __init__(self, engine, n, K, R, D, W, H, P, players, bot_players=0):
         self.src, self.n, self.K, self.R, self.D, self.W, self.P = engine, n, K, R, D, W, P
+        self.bot_players = bot_players                           # not 0: every turn is agent_actions + bot_actions + step
         self.V = V = n * K * R
         self.scratch = VecEngine(V, W, H, P)
         self.scratch.set_stream(torch.cuda.current_stream(DEV).cuda_stream)
@@ -107,9 +115,16 @@ class Composition:
         dx = (d == 1).to(torch.int64) - (d == 3).to(torch.int64)
         dy = (d == 2).to(torch.int64) - (d == 0).to(torch.int64)
         move = torch.stack([fx, fy, fx + dx, fy + dy, torch.ones_like(a)] + [torch.zeros_like(a)] * 3, dim=1).to(torch.uint8)
-        self.acts[self.rows, self.seat] = move
+        if self.bot_players:
+            assert L.gvec_bot_actions(s.h, self.bot_players, seed, 0, self.acts.data_ptr(), MEM_DEVICE) == 0
+        self.acts[self.rows, self.seat] = move                   # the candidate, whether the seat is on the rule or not
         s.step_device(self.acts)
-        if self.D > 1:
+        if self.bot_players:
+            for _ in range(self.D - 1):
+                assert L.gvec_agent_actions(s.h, seed, 0, self.acts.data_ptr(), MEM_DEVICE) == 0
+                assert L.gvec_bot_actions(s.h, self.bot_players, seed, 0, self.acts.data_ptr(), MEM_DEVICE) == 0
+                s.step_device(self.acts)
+        elif self.D > 1:
             s.rollout(self.D - 1, seed, fused=True, want_stats=False)
         assert L.gvec_read_state(s.h, 0, self.V, C.byref(self.view), MEM_DEVICE) == 0
         st = self.state
@@ -142,13 +157,15 @@ def bench_config(spec):
     players = (torch.arange(n, device=DEV) % P).to(torch.int32)
     seat_mask = mask[torch.arange(n, device=DEV), players.to(torch.int64)].clone()
     seat_mask.view(n, -1, 5)[:, :, 4] = False                   # full moves only: every candidate is accepted
-    search = PlayoutSearch(env, candidates=K, replicas=R, depth=D)
+    bot = args.rollout == "bot"
+    agent_search = PlayoutSearch(env, candidates=K, replicas=R, depth=D)
+    search = PlayoutSearch(env, candidates=K, replicas=R, depth=D, rollout="bot") if bot else agent_search
     cand = search.propose(seat_mask, None, seed=1)
     padded = cand < 0
     # padding rows: the composition needs a move to decode - give both paths the seat's first candidate again (a duplicate)
     cand = torch.where(padded, cand[:, :1].expand_as(cand), cand).contiguous()
     playable = bool((cand >= 0).all())
-    comp = Composition(env.engine, n, K, R, D, W, H, P, players)
+    comp = Composition(env.engine, n, K, R, D, W, H, P, players, search.bot_players)
     seed = 11
     ours = search.evaluate(None, players, cand, seed)
     theirs = comp.terms(cand, seed)
@@ -156,7 +173,7 @@ def bench_config(spec):
     rows_ok = ((cand >= 0) & live[:, None])[:, :, None].expand(n, K, R)
     equal = bool(torch.equal(ours[rows_ok], theirs[rows_ok]))
     q_ours, q_theirs = search.scores(ours)[0], search.scores(torch.where(rows_ok[..., None], theirs, torch.zeros_like(theirs)))[0]
-    res = {"config": spec, "roots": n, "candidates": K, "replicas": R, "depth": D, "board": [W, H], "players": P, "age": args.age,
+    res = {"config": spec, "rollout": args.rollout, "roots": n, "candidates": K, "replicas": R, "depth": D, "board": [W, H], "players": P, "age": args.age,
            "playouts": n * K * R, "padded_candidates": int(padded.sum()), "all_candidates_playable": playable,
            "valid_rows": int((ours[..., T_VALID] == 1).sum()), "terms_equal": equal, "q_equal": bool(torch.equal(q_ours, q_theirs)),
            "won_rows": int(ours[..., T_WON].sum()), "turns_played": int(ours[..., T_TURNS].sum())}
@@ -176,15 +193,23 @@ def bench_config(spec):
     def run_rollout():
         comp.scratch.rollout(D, seed, fused=True, want_stats=False)
 
-    for f in (run_search, run_comp):
+    def run_agent_search():
+        agent_search.scores(agent_search.evaluate(None, players, cand, seed))
+
+    for f in (run_search, run_comp) + ((run_agent_search,) if bot else ()):
         for _ in range(3):
             f()
     comp.scratch.copy_envs(src_ids=comp.root, src=env.engine)
     run_rollout()
     samples = {"search": [], "composition": [], "rollout": []}
+    if bot:
+        samples["agent_search"] = []
+        res["agent_turns_played"] = int(agent_search.evaluate(None, players, cand, seed)[..., T_TURNS].sum())
     for _ in range(args.repeats):
         samples["search"].append(timed(run_search, args.calls))
         samples["composition"].append(timed(run_comp, args.calls))
+        if bot:
+            samples["agent_search"].append(timed(run_agent_search, args.calls))
         comp.scratch.copy_envs(src_ids=comp.root, src=env.engine)          # the rollout starts from the roots every time
         samples["rollout"].append(timed(run_rollout, 1))
     med = lambda xs, k: float(np.median([x[k] for x in xs]))
@@ -194,18 +219,23 @@ def bench_config(spec):
     res["speedup_wall"] = res["composition"]["wall_us"] / res["search"]["wall_us"]
     res["playout_env_steps_per_s"] = res["turns_played"] / (res["search"]["device_us"] * 1e-6)
     res["rollout_env_steps_per_s"] = n * K * R * D / (res["rollout"]["device_us"] * 1e-6)   # an upper count: finished games freeze
+    if bot:                                                      # the price of a playout turn: ns of device time per turn played
+        res["ns_per_playout_turn"] = res["search"]["device_us"] * 1e3 / max(res["turns_played"], 1)
+        res["agent_ns_per_playout_turn"] = res["agent_search"]["device_us"] * 1e3 / max(res["agent_turns_played"], 1)
+        res["turn_cost_ratio"] = res["ns_per_playout_turn"] / res["agent_ns_per_playout_turn"]
     comp.scratch.close()
     env.close()
     return res
 
 
-def strength():
+def strength(rollout="agent"):
     K, R, D = (int(x) for x in args.playouts.split(":"))
     B, board, eps = args.strength_envs, args.strength_board, args.strength_episodes
-    out = {"playouts": [K, R, D], "envs": B, "board": board, "episodes_per_env": eps}
+    out = {"playouts": [K, R, D], "rollout": rollout, "envs": B, "board": board, "episodes_per_env": eps}
+    tag = "playouts" if rollout == "agent" else "playouts-bot"
     env = GeneralsSelfPlayVecEnv(B, board_width=board, board_height=board, max_players=2, device_outputs=True, seed=42, max_turns=500)
-    arena = Arena(env, [playout_policy(PlayoutSearch(env, candidates=K, replicas=R, depth=D), seed=1), random_policy(seed=2)],
-                  names=[f"playouts-{K}:{R}:{D}", "random"])
+    arena = Arena(env, [playout_policy(PlayoutSearch(env, candidates=K, replicas=R, depth=D, rollout=rollout), seed=1), random_policy(seed=2)],
+                  names=[f"{tag}-{K}:{R}:{D}", "random"])
     t0 = time.perf_counter()
     steps = arena.run(episodes_per_env=eps, poll_every=32, max_steps=500 * eps + 64)
     res = arena.results()
@@ -216,11 +246,12 @@ def strength():
     for opponent in ("bot", "random"):
         env = GeneralsVecEnv(B, board_width=board, board_height=board, max_players=2, device_outputs=True, seed=42, max_turns=500,
                              opponent=opponent)
-        search = PlayoutSearch(env, candidates=K, replicas=R, depth=D)
+        search = PlayoutSearch(env, candidates=K, replicas=R, depth=D, rollout=rollout)
         _, info = env.reset()
         mask = info["valid_actions_mask"]
         games = torch.zeros(B, dtype=torch.int64, device=DEV)
         wins, losses, steps = torch.zeros_like(games), torch.zeros_like(games), 0
+        t0 = time.perf_counter()
         while steps < 500 * eps + 64:
             actions, _ = search.act(mask.view(B, -1), seed=1000 + steps)
             _, _, terminated, truncated, info = env.step(actions)
@@ -233,7 +264,8 @@ def strength():
             if steps % 32 == 0 and int(games.min()) >= eps:
                 break
         g, w, lo = int(games.sum()), int(wins.sum()), int(losses.sum())
-        out[f"seat0_vs_{opponent}_seat"] = {"games": g, "wins": w, "losses": lo, "truncated": g - w - lo, "win_rate": w / max(g, 1), "steps": steps}
+        out[f"seat0_vs_{opponent}_seat"] = {"games": g, "wins": w, "losses": lo, "truncated": g - w - lo, "win_rate": w / max(g, 1), "steps": steps,
+                                            "seconds": time.perf_counter() - t0}
         env.close()
     return out
 
@@ -244,12 +276,17 @@ def main():
         r = bench_config(spec)
         print(json.dumps({k: r[k] for k in ("config", "terms_equal", "speedup_device", "speedup_wall", "playout_env_steps_per_s",
                                              "rollout_env_steps_per_s")}), flush=True)
-        print(json.dumps({k: r[k] for k in ("search", "composition", "rollout")}), flush=True)
+        print(json.dumps({k: r[k] for k in ("search", "composition", "rollout", "agent_search", "turn_cost_ratio") if k in r}), flush=True)
         out["configs"].append(r)
     if args.strength:
         out["strength"] = strength()
-        print(out["strength"]["vs_random"]["table"], flush=True)
-        print(json.dumps({k: v for k, v in out["strength"].items() if k.startswith("seat0")}), flush=True)
+        runs = [out["strength"]]
+        if args.rollout == "bot":                                # the same three matches with the other rollout, in the same run
+            out["strength_bot"] = strength("bot")
+            runs.append(out["strength_bot"])
+        for r in runs:
+            print(r["vs_random"]["table"], flush=True)
+            print(json.dumps({"rollout": r["rollout"], **{k: v for k, v in r.items() if k.startswith("seat0")}}), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
