@@ -107,6 +107,25 @@ extern "C" __device__ int gvec_llvm_writelane(int value, int lane, int vdst_in) 
 #define GVEC_OT_PATH 1
 #define GVEC_OT_NOGROW 4
 
+// What the ORDINARY turn of the per-turn step kernel leaves where it is because the turn did not change it (bits; DESIGN.md
+// 4.1 "Quiet planes"; one-process A/B per bit, scripts/ab_bench.py, profiles/quiet_ab.json).  0 compiles the parent's
+// step_kernel; the general code of step_kernel and every other kernel move all their planes whatever the value.  No plane
+// moves and no header bit is spent:
+// 1: the staged plane store leaves out the `own` chunks of a turn that changed no owner (every writer of own[] - act_vector,
+//    the sequential chain, eliminate's turnover - puts the tile into V: the test is any_bit(vch) at the store) and the `vis`
+//    chunks of a turn whose fog update was the identity (fog off, or V empty at the load).  ONE store instruction as before:
+//    the lanes of the chunks that stay do not take part in it.  It travels in the turn's ORD template argument, above
+//    GVEC_ORDTURN's own bits.
+// (2 was `vis` out of the early load burst, fetched by the ordinary path only when the fog update would use it.  With the
+// wait where update_fog stands it measured 1.5-5.7 us SLOWER than bit 1 alone in six sessions and alone no faster than the
+// parent; with the update split and applied right before the store 7-8 us slower than bit 1 alone and 2-3 us slower than
+// the parent (alone: 5 us slower than the parent): measured and taken out)
+#ifndef GVEC_QUIET
+#define GVEC_QUIET 1
+#endif
+#define GVEC_QT_STORE 1
+#define GVEC_OT_QSTORE 16
+
 namespace gvec {
 
 // The same knob as constants of a kernel variant (NSLOT 64-tile slots, FD = 2*NSLOT or - `odd` - 2*NSLOT-1 plane dwords):
@@ -143,6 +162,17 @@ constexpr bool ordturn_fits(int maxp, int nslot, bool agent, bool odd) {
 }
 constexpr int ordturn_bits(int maxp, int nslot, bool agent, bool odd) {
   return (GVEC_ORDTURN & GVEC_OT_PATH) != 0 && ordturn_fits(maxp, nslot, agent, odd) ? (GVEC_ORDTURN & (GVEC_OT_PATH | GVEC_OT_NOGROW)) : 0;
+}
+// GVEC_QUIET per step_kernel variant, as a bit of the same ORD argument (only where the variant carries the ordinary path).  The
+// own / vis boundary of the staged block (MAXP * fd dwords) must lie on a 16-byte chunk: at MAXP = 2 with an odd fd it does
+// not, and those variants keep the parent's store (no narrow store for the last own dwords was built).  Otherwise
+// ordturn_fits' rule: no wave per SIMD lost, no scratch gained, under 40 KB of code (scripts/kernel_regs.py): all hold it.
+constexpr bool quiet_fits(int maxp, int nslot, bool agent, bool odd) {
+  return ordturn_fits(maxp, nslot, agent, odd) && (maxp * (2 * nslot - (odd ? 1 : 0))) % 4 == 0;
+}
+constexpr int quiet_bits(int maxp, int nslot, bool agent, bool odd) {
+  if (ordturn_bits(maxp, nslot, agent, odd) == 0 || !quiet_fits(maxp, nslot, agent, odd)) return 0;
+  return (GVEC_QUIET & GVEC_QT_STORE) != 0 ? GVEC_OT_QSTORE : 0;
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -60,7 +60,7 @@ __device__ __forceinline__ void step_ordinary(Turn<MAXP, NSLOT>& b, const StepAr
   store_army<true>(b, army_env);
   settle_lists(b);
   b.store_hdr(A.hdr + (size_t)env * HDR_DW, err);
-  b.store_planes_staged(A.rows + (size_t)env * ROW_DW, FD);
+  b.template store_planes_staged<ORD>(A.rows + (size_t)env * ROW_DW, FD);
   if (A.err && lane == 0) A.err[env] = (int32_t)err;
   if (A.flags & KF_EMIT) {
     b.template legal_planes<false>(m);
@@ -96,7 +96,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (step_waves<MAXP, NSLOT>())) 
   const ArmyRef army_env = army_ref<NSLOT>(A.army16, A.army32, env);
   // GVEC_ORDTURN: ONE wave-uniform branch, taken as soon as the header words are there, sends the ordinary turn down its own
   // instantiation; everything below is the general code (profiling builds count phases of that code alone)
-  constexpr int ORD = (GVEC_PROFILE_SKIP | GVEC_PROFILE_DUP) != 0 ? 0 : ordturn_bits(MAXP, NSLOT, AGENT, ODD);
+  // (GVEC_QUIET rides in ORD: the planes the ordinary turn's store leaves in memory because the turn did not change them)
+  constexpr int ORD = (GVEC_PROFILE_SKIP | GVEC_PROFILE_DUP) != 0 ? 0 : (ordturn_bits(MAXP, NSLOT, AGENT, ODD) | quiet_bits(MAXP, NSLOT, AGENT, ODD));
   if constexpr (ORD != 0) {
     const uint32_t* rows_env = A.rows + (size_t)env * ROW_DW;
     load_turn_issue<lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, rows_env, army_env, FD, A.zeros);

@@ -167,6 +167,9 @@ struct PBoard {
   uint32_t prod_mask = 0u;     // the tiles production raised, replicated in every row ...
   int32_t prod_rate = 0;       // ... by this much each (prod_uniform), else the delta path is off
   bool prod_uniform = false, grow = false;
+  // GVEC_QUIET, the ordinary turn alone: this turn's fog update changed vis[] (fog on and V non-empty at the load).  Set by
+  // update_fog<ORD>, read by the staged store; wave-uniform.  The general code neither sets nor reads it.
+  bool vis_live = true;
 
   static __device__ __forceinline__ int col() { return lane_id() & (ROWL - 1); }
   static __device__ __forceinline__ int row() { return lane_id() / ROWL; }
@@ -495,13 +498,16 @@ struct PBoard {
   // ---- Engine.updateFogOfWarOptimized (visibility_optimized.go:16-97) ---------------------------------
   // matched: lists_match() holds (the caller needs it too)
   // ORD (here and below): the turn is an ordinary one (ordinary_turn) - what that says is folded in
+  // GVEC_QUIET (bit GVEC_OT_QSTORE of ORD): vis_live records whether this update is more than the identity
   template <int ORD = 0>
   __device__ __forceinline__ void update_fog(bool matched = false) {
+    if constexpr ((ORD & GVEC_OT_QSTORE) != 0) vis_live = false;
     if (!(hflags & HF_FOG)) return;  // :17-19
     bool full, none;
     if (ORD || ((hflags & HF_VSMALL) && turn > 0 && P <= N / 10)) {  // at most P tiles in V: below the threshold whatever they are
       full = false;
       none = !any_bit(vch);
+      if constexpr ((ORD & GVEC_OT_QSTORE) != 0) vis_live = !none;
     } else {
       const int nv = count_shared(vch);
       full = turn == 0 || nv > N / 10;
@@ -1022,8 +1028,31 @@ struct PBoard {
     const int tail = dwords & 3, l = lane_id();
     if (l < tail) st_stream<CLASS>(dst + 4 * chunks + l, reinterpret_cast<const uint32_t*>(larmy)[4 * chunks + l]);
   }
+  // flush_stage without the chunks [skip_lo, skip_hi): still one store instruction per 64 chunks - the lanes of the chunks
+  // that stay take no part in it (an EXEC mask on the store, as `i < chunks` is one already; no branch of its own)
+  template <int CLASS>
+  __device__ __forceinline__ void flush_stage_but(uint32_t* dst, int dwords, int skip_lo, int skip_hi) const {  // dst 16-byte aligned
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(larmy);
+    u32x4* g4 = reinterpret_cast<u32x4*>(dst);
+    const int chunks = dwords >> 2;
+    for (int i = lane_id(); i < chunks; i += 64) {
+      if ((uint32_t)(i - skip_lo) >= (uint32_t)(skip_hi - skip_lo)) st_stream<CLASS>(g4 + i, s4[i]);
+    }
+    const int tail = dwords & 3, l = lane_id();
+    if (l < tail) st_stream<CLASS>(dst + 4 * chunks + l, reinterpret_cast<const uint32_t*>(larmy)[4 * chunks + l]);
+  }
   // the planes that change in a turn (OWN .. GT1: contiguous in the block)
+  // ORD with GVEC_OT_QSTORE (GVEC_QUIET: the ordinary turn of step_kernel alone): own[] leaves only if the turn changed an
+  // owner - every writer of own[] (act_vector, apply_action, eliminate) puts the tile into the new V - and vis[] only if the
+  // fog update changed it (vis_live); what stays is neither staged nor stored.  quiet_fits: both boundaries are whole chunks.
+  template <int ORD = 0>
   __device__ __forceinline__ void store_planes_staged(uint32_t* rows_env, int fd) const {
+    constexpr bool QUIET = (ORD & GVEC_OT_QSTORE) != 0;
+    bool st_own = true, st_vis = true;
+    if constexpr (QUIET) {
+      st_own = any_bit(vch);
+      st_vis = vis_live;
+    }
     uint32_t* stage = reinterpret_cast<uint32_t*>(larmy);
     const bool in = col() < fd;
     uint32_t* g = stage + row() * fd + col();
@@ -1031,8 +1060,8 @@ struct PBoard {
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
       if (in && (k * PPR + row() < MAXP)) {
-        g[(PL::OWN + k * PPR) * fd] = own[k];
-        g[(PL::VIS + k * PPR) * fd] = vis[k];
+        if (st_own) g[(PL::OWN + k * PPR) * fd] = own[k];
+        if (st_vis) g[(PL::VIS + k * PPR) * fd] = vis[k];
       }
     }
 #pragma unroll
@@ -1050,7 +1079,12 @@ struct PBoard {
       if (2 * fd + col() < gap) g[PL::MTN * fd] = mtn;
     }
     wave_lds_fence();
-    flush_stage<GVEC_NT_PLANE>(rows_env, PL::MUTABLE * fd + gap);
+    if constexpr (QUIET) {
+      const int own_c = (MAXP * fd) >> 2;  // chunks of own[]; vis[] is the next own_c
+      flush_stage_but<GVEC_NT_PLANE>(rows_env, PL::MUTABLE * fd + gap, st_own ? own_c : 0, st_vis ? own_c : 2 * own_c);
+    } else {
+      flush_stage<GVEC_NT_PLANE>(rows_env, PL::MUTABLE * fd + gap);
+    }
     store_lists(rows_env, fd);
   }
   // narrow armies (the caller has checked army_fits_narrow): the block's layout is army_store_narrow's
