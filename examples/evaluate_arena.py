@@ -9,7 +9,9 @@ per step (gvec_arena_update), and ratings on the Elo scale fitted to who outlast
 Each positional argument is a checkpoint written by train_ppo_selfplay.py --save; every --random adds an entrant that plays
 uniformly over its legal moves; --playouts K:R:D adds a flat Monte Carlo searcher (search.playout_policy: K candidates, R
 playouts of D turns each per candidate, one launch per step) whose candidates come from the first checkpoint's logits, or
-from a uniform draw when there is no checkpoint.
+from a uniform draw when there is no checkpoint; --halving M:N:D adds a sequential-halving searcher beside it
+(search.HalvingSearch: M Gumbel-top-m candidates, a budget of N playouts per decision spread over the halving rounds, D turns
+deep) with the same prior.  --playout-rollout chooses what both searchers' playouts play.
 Entrants are seated so that each sits in every column (player seat) equally often (arena.balanced_seating), every env contributes exactly --episodes finished games, and nothing synchronises with the host
 between polls.  A multi-player game's pairwise results are treated as independent games by the fit: the ratings rank, their
 error bars are not calibrated.  An example, not part of the measured hot path.
@@ -25,7 +27,7 @@ import torch
 
 from generalsreinforcementlearning_amd.arena import Arena, random_policy, torch_policy
 from generalsreinforcementlearning_amd.features import strategic_features
-from generalsreinforcementlearning_amd.search import PlayoutSearch, playout_policy
+from generalsreinforcementlearning_amd.search import HalvingSearch, PlayoutSearch, playout_policy
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
 
 
@@ -76,12 +78,25 @@ def parse_playouts(text):
     return k, r, d
 
 
+def parse_halving(text):
+    """'M:N:D' -> (candidates in [1, 64], budget, depth), each an int >= 1"""
+    try:
+        m, n, d = (int(x) for x in text.split(":"))
+    except ValueError:
+        raise SystemExit(f"--halving wants M:N:D (candidates:budget:depth), not {text!r}")
+    if min(m, n, d) < 1 or m > 64:
+        raise SystemExit(f"--halving {text}: candidates (at most 64), budget and depth must be at least 1")
+    return m, n, d
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoints", nargs="*", help="files written by train_ppo_selfplay.py --save")
     ap.add_argument("--random", action="count", default=0, help="add an entrant that plays uniformly over its legal moves (repeatable)")
     ap.add_argument("--playouts", metavar="K:R:D", default=None,
                     help="add a playout-search entrant: K candidates, R playouts each, D turns deep; its prior is the first checkpoint")
+    ap.add_argument("--halving", metavar="M:N:D", default=None,
+                    help="add a sequential-halving entrant: M candidates, a budget of N playouts per decision, D turns deep; the same prior")
     ap.add_argument("--playout-rollout", choices=("agent", "bot"), default="agent",
                     help="what the playouts play after the candidate: the random agent, or the scripted opponent's rule on every seat")
     ap.add_argument("--num-envs", type=int, default=1024)
@@ -100,16 +115,22 @@ def main(argv=None):
     krd = parse_playouts(a.playouts) if a.playouts else None
     if krd:
         names.append(("playouts-bot-%d:%d:%d" if a.playout_rollout == "bot" else "playouts-%d:%d:%d") % krd)
+    mnd = parse_halving(a.halving) if a.halving else None
+    if mnd:
+        names.append(("halving-bot-%d:%d:%d" if a.playout_rollout == "bot" else "halving-%d:%d:%d") % mnd)
     if not names:
         raise SystemExit("nothing to evaluate: give checkpoints and / or --random")
     entrants = [load_entrant(p, a.board, dev, a.greedy, a.seed + k) for k, p in enumerate(a.checkpoints)]
     entrants += [random_policy(seed=a.seed + 1000 + k) for k in range(a.random)]
     env = GeneralsSelfPlayVecEnv(a.num_envs, board_width=a.board, board_height=a.board, max_players=a.players, max_turns=a.max_turns,
                                  seed=a.seed, device_outputs=True)
+    prior = load_net(a.checkpoints[0], a.board, dev) if a.checkpoints and (krd or mnd) else None
     if krd:
-        prior = load_net(a.checkpoints[0], a.board, dev) if a.checkpoints else None
         search = PlayoutSearch(env, candidates=krd[0], replicas=krd[1], depth=krd[2], rollout=a.playout_rollout)
         entrants.append(playout_policy(search, net=prior, seed=a.seed + 2000))
+    if mnd:
+        halving = HalvingSearch(env, candidates=mnd[0], budget=mnd[1], depth=mnd[2], rollout=a.playout_rollout)
+        entrants.append(playout_policy(halving, net=prior, seed=a.seed + 3000))
     arena = Arena(env, entrants, names=names)
     steps = arena.run(episodes_per_env=a.episodes, poll_every=a.poll_every, max_steps=a.max_steps)
     res = arena.results()

@@ -170,6 +170,24 @@ class SearchArgs(C.Structure):
 
 
 SEARCH_TERMS, SEARCH_PASS, SEARCH_NONE = 8, -1, -2     # GVEC_SEARCH_* in include/generals_vec.h
+SEARCH_MAX_SLOTS = 64                                  # GVEC_SEARCH_MAX_SLOTS
+
+
+class SearchHalveArgs(C.Structure):
+    """gvec_search_halve_args (include/generals_vec.h): every pointer is device memory; slot may be None (the identity)."""
+    _fields_ = ([(n, C.c_int32) for n in ("n", "m", "k", "replicas", "k_next", "reserved")]
+                + [(n, C.c_void_p) for n in ("terms", "slot", "candidates0", "prior_key")]
+                + [(n, C.c_double) for n in ("win", "loss", "land", "army", "q_lo", "q_inv_range", "c_visit", "c_scale")]
+                + [(n, C.c_void_p) for n in ("sum", "count", "next_slot", "next_candidates")])
+
+
+class SearchPolicyArgs(C.Structure):
+    """gvec_search_policy_args (include/generals_vec.h): every pointer is device memory; logits and value may be None."""
+    _fields_ = ([(n, C.c_int32) for n in ("n", "num_actions", "m", "reserved")]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "candidates0", "sum", "count", "value")]
+                + [(n, C.c_double) for n in ("q_lo", "q_inv_range", "c_visit", "c_scale")]
+                + [(n, C.c_void_p) for n in ("target", "v_mix")])
+
 
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
@@ -213,6 +231,8 @@ SYMBOLS = {
     "gvec_bot_actions": (_i32, [_vp, C.c_uint32, _u64, _i32, _vp, _i32]),
     "gvec_search_playouts": (_i32, [_vp, C.POINTER(SearchArgs)]),
     "gvec_search_playouts_bot": (_i32, [_vp, C.POINTER(SearchArgs), C.c_uint32, _i32]),
+    "gvec_search_halve": (_i32, [_i32, _vp, C.POINTER(SearchHalveArgs)]),
+    "gvec_search_improved_policy": (_i32, [_i32, _vp, C.POINTER(SearchPolicyArgs)]),
     "gvec_counters": (_i32, [_vp, C.POINTER(RolloutStats)]),
     "gvec_step_traffic_bytes": (_i32, [_vp, C.POINTER(C.c_int64)]),
     "gvec_experience_begin": (_i32, [_vp]),

@@ -356,4 +356,9 @@ hipError_t launch_obs_symmetry(const gvec_obs_symmetry_args& a, hipStream_t s);
 // match arena: episode tally per env (gvec_arena.hip; generals_vec.h "match arena")
 hipError_t launch_arena_update(const gvec_arena_args& a, hipStream_t s);
 
+// sequential-halving search: a round's tail and the policy target (gvec_halving.hip; generals_vec.h "sequential-halving search")
+constexpr int SEARCH_POLICY_MAX_ACTIONS = 5 * GVEC_MAX_DIM * GVEC_MAX_DIM;   // the largest row the policy target holds in registers
+hipError_t launch_search_halve(const gvec_search_halve_args& a, hipStream_t s);
+hipError_t launch_search_improved_policy(const gvec_search_policy_args& a, hipStream_t s);
+
 }  // namespace gvec

@@ -12,6 +12,10 @@ Carlo search")
 One HIP launch per evaluation (gvec_search_playouts: one wavefront per playout; the roots are read only and 32 bytes come
 back per playout); proposing the candidates and reducing the terms are a handful of torch calls on [n, K]-sized tensors.
 The playouts see the true state, not the seat's fogged view: a baseline and a teacher, not a fair fogged player.
+
+HalvingSearch spends the same playouts by sequential halving over Gumbel-top-m candidates (one gvec_search_halve launch
+between two playout launches) and gives a policy target over every legal action from completed Q values
+(gvec_search_improved_policy): include/generals_vec.h "sequential-halving search", DESIGN.md section 4.22.
 """
 import ctypes as C
 
@@ -281,6 +285,197 @@ class PlayoutSearch:
         out = torch.zeros((candidates.shape[0], self.num_actions), dtype=torch.float64, device=q.device)
         out.scatter_add_(1, torch.where(on_board, candidates, torch.zeros_like(candidates)), torch.where(on_board, p, torch.zeros_like(p)))
         return out.to(torch.float32)
+
+
+def halving_schedule(candidates, budget):
+    """[(K_r, R_r)] of a sequential-halving search over m = candidates slots: K_0 = m, K_{r+1} = ceil(K_r / 2), T = max(1,
+    ceil(log2 m)) rounds - the last one's better half is the one survivor - and R_r = max(1, budget // (T * K_r)) playouts per
+    column, so that every round spends about budget / T."""
+    m, K, out = int(candidates), int(candidates), []
+    T = max(1, (m - 1).bit_length())
+    for _ in range(T):
+        out.append((K, max(1, int(budget) // (T * K))))
+        K = (K + 1) // 2
+    return out
+
+
+class HalvingSearch:
+    """Sequential halving with Gumbel-top-m candidates and a completed-Q policy target: the root search of Danihelka et al.,
+    "Policy improvement by planning with Gumbel" (ICLR 2022), on PlayoutSearch's playouts.
+
+        search = HalvingSearch(env, candidates=16, budget=64, depth=8)       # 16 x 1, 8 x 2, 4 x 4, 2 x 8 playouts per row
+        actions, found = search.act(mask, logits=logits, seed=step)          # per round: one playout launch, one gvec_search_halve
+        target, v_mix = search.policy_target(logits, mask, found, value)     # softmax(logits + sigma(completed q)) over the legal set
+    """
+
+    def __init__(self, env_or_engine, candidates=16, budget=64, depth=8, score=None, rollout="agent", bot_players=None,
+                 bot_random_permille=0, c_visit=50.0, c_scale=1.0):
+        """candidates m in [1, 64] slots per row, budget >= 1 playouts per row to spread over the rounds (`schedule`; what is
+        spent is `playouts_per_row`), depth, score (a PlayoutScore), rollout, bot_players, bot_random_permille as PlayoutSearch
+        takes them; c_visit and c_scale: the paper's sigma(q) = (c_visit + max visits) * c_scale * q with q on [0, 1]."""
+        from ._lib import SEARCH_MAX_SLOTS
+        for name, v in (("candidates", candidates), ("budget", budget), ("depth", depth)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1, not {v!r}")
+        if candidates > SEARCH_MAX_SLOTS:
+            raise ValueError(f"candidates must be at most {SEARCH_MAX_SLOTS}, not {candidates}")
+        for name, v in (("c_visit", c_visit), ("c_scale", c_scale)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+                raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+        if score is not None and not isinstance(score, PlayoutScore):
+            raise ValueError(f"score must be a PlayoutScore (the kernel takes its four weights), not {type(score).__name__}")
+        self.score = PlayoutScore() if score is None else score
+        s = self.score
+        half = (s.land + s.army) / 2
+        self.q_lo = min(s.loss, -half)
+        if not max(s.win, half) > self.q_lo:
+            raise ValueError("the score has no range: max(win, (land + army) / 2) must exceed min(loss, -(land + army) / 2)")
+        self.q_inv_range = 1.0 / (max(s.win, half) - self.q_lo)
+        self.m, self.budget, self.D = int(candidates), int(budget), int(depth)
+        self.c_visit, self.c_scale = float(c_visit), float(c_scale)
+        self.schedule = halving_schedule(self.m, self.budget)
+        self.playouts_per_row = sum(K * R for K, R in self.schedule)
+        self._rounds = [PlayoutSearch(env_or_engine, candidates=K, replicas=R, depth=depth, score=s, rollout=rollout,
+                                      bot_players=bot_players, bot_random_permille=bot_random_permille) for K, R in self.schedule]
+        first = self._rounds[0]
+        self.env, self.engine, self.num_actions = first.env, first.engine, first.num_actions
+        self.rollout, self.bot_players, self.bot_random_permille = first.rollout, first.bot_players, first.bot_random_permille
+
+    @staticmethod
+    def round_seed(seed, r):
+        """the playout seed of round r of a search called with `seed`"""
+        return ((int(seed) & (2 ** 64 - 1)) + (r + 1) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+    def _stream(self):
+        return C.c_void_p(getattr(self.engine, "_stream", None) or 0)        # where the engine's own launches go
+
+    def propose(self, mask, logits=None, seed=0):
+        """mask bool / uint8 [n, 5 * H * W], logits float [n, 5 * H * W] or None (0 on every legal action) -> (candidates int64
+        [n, m], prior_key float64 [n, m]): Gumbel-top-m, the m legal actions with the largest key = logit + g in that order,
+        g = -log(-log u), u = (h + 0.5) / 2^32 with h the counter hash of (seed, row, action) that PlayoutSearch.propose
+        draws from - a sample of m actions without replacement from softmax(logits).  Rows with fewer than m legal actions
+        are padded with GVEC_SEARCH_NONE (prior_key -inf)."""
+        import torch
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 2 \
+                or mask.shape[1] != self.num_actions:
+            raise ValueError(f"mask must be a bool / uint8 tensor [n, {self.num_actions}]")
+        legal = mask != 0
+        n = int(legal.shape[0])
+        u = _uniform_keys(seed, n, self.num_actions, legal.device) + 0.5 / 4294967296.0      # exact: h has 32 bits
+        keys = -torch.log(-torch.log(u))
+        if logits is not None:
+            if not isinstance(logits, torch.Tensor) or not logits.is_floating_point() or tuple(logits.shape) != tuple(legal.shape):
+                raise ValueError(f"logits must be a floating-point tensor {tuple(legal.shape)}")
+            if logits.device != legal.device:
+                raise ValueError(f"logits is on {logits.device}, mask on {legal.device}")
+            keys = logits.detach().to(torch.float64) + keys
+        keys = torch.where(legal, keys, torch.full_like(keys, -float("inf")))
+        k = min(self.m, self.num_actions)
+        top = torch.topk(keys, k, dim=1)
+        cand = torch.where(torch.isinf(top.values) & (top.values < 0), torch.full_like(top.indices, SEARCH_NONE), top.indices)
+        prior = top.values
+        if k < self.m:
+            cand = torch.cat([cand, torch.full((n, self.m - k), SEARCH_NONE, dtype=torch.int64, device=cand.device)], dim=1)
+            prior = torch.cat([prior, torch.full((n, self.m - k), -float("inf"), dtype=torch.float64, device=cand.device)], dim=1)
+        return cand.contiguous(), prior.contiguous()
+
+    def _halve_args(self, n, K, R, k_next, terms, slot, candidates, prior_key, total, count, next_slot, next_candidates):
+        from ._lib import SearchHalveArgs
+        s = self.score
+        return SearchHalveArgs(n=n, m=self.m, k=K, replicas=R, k_next=k_next, reserved=0, terms=terms.data_ptr(),
+                               slot=None if slot is None else slot.data_ptr(), candidates0=candidates.data_ptr(),
+                               prior_key=prior_key.data_ptr(), win=s.win, loss=s.loss, land=s.land, army=s.army, q_lo=self.q_lo,
+                               q_inv_range=self.q_inv_range, c_visit=self.c_visit, c_scale=self.c_scale, sum=total.data_ptr(),
+                               count=count.data_ptr(), next_slot=next_slot.data_ptr(), next_candidates=next_candidates.data_ptr())
+
+    def search(self, env_ids, players, candidates, prior_key, seed=0):
+        """env_ids int32 [n] (None: envs 0..n-1), players int32 [n], candidates int64 [n, m], prior_key float64 [n, m]:
+        contiguous CUDA tensors on the engine's device -> a dict: sum float64 [n, m] and count int32 [n, m] of every slot's
+        playout scores, q float32 [n, m] (the mean, 0 where there is no count), valid bool [n, m] (count > 0), slot int32 [n]
+        and action int64 [n] (the survivor: its slot and candidates[slot]) and found bool [n] (the survivor has a count).
+        Per round one playout launch (PlayoutSearch.evaluate, under round_seed(seed, r)) and one gvec_search_halve, all on
+        the engine's stream; no host sync."""
+        import torch
+        from ._lib import load
+        first = self._rounds[0]
+        dev = first._device()
+        cand0 = first._check(candidates, "candidates", torch.int64, None, dev)
+        if cand0.dim() != 2 or cand0.shape[1] != self.m:
+            raise ValueError(f"candidates {tuple(cand0.shape)} is not [n, {self.m}]")
+        n = int(cand0.shape[0])
+        first._check(prior_key, "prior_key", torch.float64, (n, self.m), dev)
+        if not prior_key.is_contiguous():
+            raise ValueError("prior_key must be contiguous")
+        total = torch.zeros((n, self.m), dtype=torch.float64, device=dev)
+        count = torch.zeros((n, self.m), dtype=torch.int32, device=dev)
+        cand, slot = cand0, None
+        for r, (K, R) in enumerate(self.schedule):
+            terms = self._rounds[r].evaluate(env_ids, players, cand, self.round_seed(seed, r))
+            k_next = (K + 1) // 2
+            next_slot = torch.empty((n, k_next), dtype=torch.int32, device=dev)
+            next_cand = torch.empty((n, k_next), dtype=torch.int64, device=dev)
+            if n:
+                a = self._halve_args(n, K, R, k_next, terms, slot, cand0, prior_key, total, count, next_slot, next_cand)
+                check(load().gvec_search_halve(dev.index, self._stream(), C.byref(a)), "gvec_search_halve")
+            cand, slot = next_cand, next_slot
+        valid = count > 0
+        q = (total / count.clamp(min=1).to(torch.float64)).to(torch.float32)
+        survivor = slot[:, 0]
+        found = valid.gather(1, survivor.to(torch.int64)[:, None]).squeeze(1) if n else torch.zeros(0, dtype=torch.bool, device=dev)
+        return {"sum": total, "count": count, "q": q, "valid": valid, "slot": survivor, "action": cand[:, 0], "found": found}
+
+    def act(self, mask, logits=None, seed=0, rows=None):
+        """PlayoutSearch.act's signature and row conventions -> (actions int64 [n], info): the surviving candidate; 0 for a
+        row without one (the env refuses it).  info: candidates and prior_key [n, m], and everything search() returns."""
+        import torch
+        dev = self._rounds[0]._device()
+        if isinstance(mask, torch.Tensor) and mask.device != dev:
+            raise ValueError(f"mask is on {mask.device}, the engine on {dev}")
+        cand, prior = self.propose(mask, logits, seed)
+        env_ids, players = self._rounds[0]._rows_to_ids(int(cand.shape[0]), rows)
+        info = self.search(env_ids, players, cand, prior, seed)
+        info.update(candidates=cand, prior_key=prior)
+        ok = info["found"] & (info["action"] >= 0)
+        return torch.where(ok, info["action"], torch.zeros((), dtype=torch.int64, device=dev)), info
+
+    def policy_target(self, logits, mask, info, value=None):
+        """logits float32 [n, A] or None (uniform over the legal set), mask bool / uint8 [n, A], info with candidates, sum and
+        count as act() returns them, value float32 [n] or None (the net's value in score units): contiguous CUDA tensors ->
+        (target float32 [n, A], v_mix float32 [n]): gvec_search_improved_policy, softmax over the legal set of logits +
+        sigma(completed q) - q the playout mean on the visited actions, v_mix elsewhere."""
+        import torch
+        from ._lib import SearchPolicyArgs, load
+        first = self._rounds[0]
+        dev, A = first._device(), self.num_actions
+        first._check(mask, "mask", (torch.bool, torch.uint8), None, dev)
+        if mask.dim() != 2 or mask.shape[1] != A:
+            raise ValueError(f"mask {tuple(mask.shape)} is not [n, {A}]")
+        n = int(mask.shape[0])
+        if logits is not None:
+            first._check(logits, "logits", torch.float32, (n, A), dev)
+        if value is not None:
+            first._check(value, "value", torch.float32, (n,), dev)
+        if not isinstance(info, dict) or not all(k in info for k in ("candidates", "sum", "count")):
+            raise ValueError("info must hold candidates, sum and count, as act() returns them")
+        first._check(info["candidates"], "info['candidates']", torch.int64, (n, self.m), dev)
+        first._check(info["sum"], "info['sum']", torch.float64, (n, self.m), dev)
+        first._check(info["count"], "info['count']", torch.int32, (n, self.m), dev)
+        for name, t in (("mask", mask), ("logits", logits), ("value", value), ("info['candidates']", info["candidates"]),
+                        ("info['sum']", info["sum"]), ("info['count']", info["count"])):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        target = torch.empty((n, A), dtype=torch.float32, device=dev)
+        v_mix = torch.empty((n,), dtype=torch.float32, device=dev)
+        if n == 0:
+            return target, v_mix
+        legal = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        a = SearchPolicyArgs(n=n, num_actions=A, m=self.m, reserved=0, logits=None if logits is None else logits.data_ptr(),
+                             mask=legal.data_ptr(), candidates0=info["candidates"].data_ptr(), sum=info["sum"].data_ptr(),
+                             count=info["count"].data_ptr(), value=None if value is None else value.data_ptr(), q_lo=self.q_lo,
+                             q_inv_range=self.q_inv_range, c_visit=self.c_visit, c_scale=self.c_scale, target=target.data_ptr(),
+                             v_mix=v_mix.data_ptr())
+        check(load().gvec_search_improved_policy(dev.index, self._stream(), C.byref(a)), "gvec_search_improved_policy")
+        return target, v_mix
 
 
 class _PlayoutPolicy:

@@ -371,6 +371,78 @@ int32_t gvec_search_playouts(gvec_handle* h, const gvec_search_args* args);
  * max_players. */
 int32_t gvec_search_playouts_bot(gvec_handle* h, const gvec_search_args* args, uint32_t bot_players, int32_t bot_random_permille);
 
+/* ---- sequential-halving search: what lies between two playout launches, and the policy target ----
+ * The root search of Danihelka et al., "Policy improvement by planning with Gumbel" (ICLR 2022): m candidates per row, drawn
+ * by the caller, are played in rounds; every round's playouts (gvec_search_playouts' terms) are added to a running sum and
+ * count per initial candidate SLOT, and the better part of the round's columns goes on to the next one.  Both entry points
+ * are handle-free: (device, hip_stream, args), every pointer device memory, enqueued on hip_stream, nothing synchronised.
+ * One wavefront per row.
+ *
+ * gvec_search_halve, once per round.  This round played k columns of `replicas` playouts per row; column c < k stands for
+ * the initial slot s = slot[r][c] (slot NULL: s = c, which needs k == m).  The slots of a row are distinct and in [0, m); a
+ * column whose slot is not is left out altogether.  Per row:
+ *   1. for j = 0 .. replicas - 1 in that order, a playout terms[r][c][j] whose `valid` term is non-zero adds its score to
+ *      sum[r][s] and 1 to count[r][s].  The score, in float64 and in this order of operations: `win` if the won term is
+ *      non-zero, else `loss` if the alive term is zero, else
+ *        (land * ratio(t.land, t.land_others) + army * ratio(t.army, t.army_others)) - (land + army) / 2,
+ *      ratio(a, b) = a / (a + b), or 0.5 when a + b == 0.  Slots that no column names keep their sum and count.
+ *   2. nmax = the largest count over the row's m slots after step 1.  A slot with count > 0 has mean = sum / count and
+ *        key = prior_key[r][s] + ((c_visit + nmax) * c_scale) * ((mean - q_lo) * q_inv_range)       (float64, this grouping)
+ *      The caller passes q_lo = min(loss, -(land + army) / 2) and q_inv_range = 1 / (max(win, (land + army) / 2) - q_lo):
+ *      the playout value on [0, 1].
+ *   3. the k columns are ranked: a LIVE column (count > 0 and candidates0[r][s] != GVEC_SEARCH_NONE) before one that is
+ *      not; among live columns the larger key, then the lower slot; among the others the lower slot.  The column of rank
+ *      q < k_next writes next_slot[r][q] = s and next_candidates[r][q] = candidates0[r][s]: a row with fewer than k_next
+ *      live columns carries its padding on, and the playout kernel answers it with invalid rows again.
+ * sum float64 [n][m] and count int32 [n][m] are read and written (the caller zeroes them before the first round);
+ * next_slot int32 [n][k_next] and next_candidates int64 [n][k_next] are written.  No atomics: a row belongs to one
+ * wavefront and a slot to one lane, so the same input gives the same bits.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args or a pointer other than slot
+ * NULL, n < 0, m outside [1, 64], k outside [1, m], k_next outside [1, k], replicas < 1, slot NULL with k != m.  n == 0 is a
+ * no-op that needs no device.
+ *
+ * gvec_search_improved_policy: the policy target from completed Q values over ALL legal actions.  Per row, with S = {i :
+ * mask_i != 0} and x_i = logits_i (0 when logits is NULL: the uniform prior), pi = softmax_S(x):
+ *   V      the slots with count > 0 whose candidate a lies in [0, num_actions) and in S (a visited GVEC_SEARCH_PASS has no
+ *          action index and is left out); q(a) = sum / count, N = the sum of count over V, nmax = the largest count of the
+ *          row's m slots
+ *   v_mix  (value + N * vq) / (1 + N) with vq = sum_V pi(a) q(a) / sum_V pi(a); value NULL: v_mix = vq.  V empty: v_mix =
+ *          value, or 0 without one
+ *   target softmax_S(x_i + ((c_visit + nmax) * c_scale) * ((q_i - q_lo) * q_inv_range)), q_i = q(a) on V and v_mix elsewhere;
+ *          0 outside S; all zeros for a row with S empty; softmax_S(x) itself when V is empty
+ * target float32 [n][num_actions]: EVERY element is written; v_mix float32 [n].  float32 arithmetic with fixed reduction
+ * orders (q(a) is the float64 quotient rounded once); the row is read from HBM once and held in registers.
+ * GVEC_E_INVALID before anything touches a device: args, mask, candidates0, sum, count, target or v_mix NULL, n < 0,
+ * num_actions outside [1, 5 * GVEC_MAX_DIM * GVEC_MAX_DIM], m outside [1, 64].  n == 0 is a no-op that needs no device. */
+#define GVEC_SEARCH_MAX_SLOTS 64
+typedef struct gvec_search_halve_args {
+  int32_t n, m, k, replicas, k_next, reserved;
+  const int32_t* terms;             /* [n][k][replicas][GVEC_SEARCH_TERMS] */
+  const int32_t* slot;              /* [n][k], NULL = identity */
+  const int64_t* candidates0;       /* [n][m] */
+  const double* prior_key;          /* [n][m] */
+  double win, loss, land, army;     /* the score's weights */
+  double q_lo, q_inv_range, c_visit, c_scale;
+  double* sum;                      /* [n][m] in / out */
+  int32_t* count;                   /* [n][m] in / out */
+  int32_t* next_slot;               /* [n][k_next] out */
+  int64_t* next_candidates;         /* [n][k_next] out */
+} gvec_search_halve_args;
+typedef struct gvec_search_policy_args {
+  int32_t n, num_actions, m, reserved;
+  const float* logits;              /* [n][num_actions], NULL = uniform over the legal set */
+  const uint8_t* mask;              /* [n][num_actions] */
+  const int64_t* candidates0;       /* [n][m] */
+  const double* sum;                /* [n][m] */
+  const int32_t* count;             /* [n][m] */
+  const float* value;               /* [n], NULL = none */
+  double q_lo, q_inv_range, c_visit, c_scale;
+  float* target;                    /* [n][num_actions] out */
+  float* v_mix;                     /* [n] out */
+} gvec_search_policy_args;
+int32_t gvec_search_halve(int32_t device, void* hip_stream, const gvec_search_halve_args* args);
+int32_t gvec_search_improved_policy(int32_t device, void* hip_stream, const gvec_search_policy_args* args);
+
 /* ---- internal/experience side channel ------------------------------
  * gvec_experience_begin   = TurnProcessor.captureStateForExperience
  *                           (turn_processor.go:116-121: GameState.Clone before the step):
