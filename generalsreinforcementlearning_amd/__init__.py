@@ -12,7 +12,7 @@ from .env_state import VecEnvState  # noqa: F401
 from .reward import REWARD_TERMS, RewardConfig  # noqa: F401
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer  # noqa: F401
 from .rollout import SelfPlayRolloutBuffer  # noqa: F401
-from .policy_head import MaskedCategoricalHead  # noqa: F401
+from .policy_head import MaskedCategoricalHead, distill_loss  # noqa: F401
 from .features import NUM_STRATEGIC_FEATURES, STRATEGIC_FEATURE_NAMES, strategic_features  # noqa: F401
 from .memory import MEMORY_PLANE_NAMES, NUM_MEMORY_PLANES, ObservationMemory, remembered_observation  # noqa: F401
 from .q_targets import categorical_target, double_q_target, valid_actions_mask_from_observation  # noqa: F401
@@ -22,7 +22,7 @@ from .arena import (Arena, ArenaResult, EpisodeTally, balanced_seating, expected
 from .search import HalvingSearch, PlayoutScore, PlayoutSearch, halving_schedule, playout_policy  # noqa: F401
 
 __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState", "RewardConfig", "REWARD_TERMS",
-           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "strategic_features",
+           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "distill_loss", "strategic_features",
            "NUM_STRATEGIC_FEATURES", "STRATEGIC_FEATURE_NAMES", "ObservationMemory", "remembered_observation", "NUM_MEMORY_PLANES",
            "MEMORY_PLANE_NAMES", "valid_actions_mask_from_observation", "double_q_target", "categorical_target",
            "apply_symmetry", "augment_transition", "inverse_symmetry", "num_symmetries", "random_symmetries",

@@ -95,6 +95,18 @@ class PolicyBackwardArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("logits", "mask", "action", "grad_logp", "grad_entropy", "grad_logits")])
 
 
+class PolicyDistillArgs(C.Structure):
+    """gvec_policy_distill_args (include/generals_vec.h): every pointer is device memory."""
+    _fields_ = ([("rows", C.c_int64), ("num_actions", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "target", "ce", "kl", "entropy")])
+
+
+class PolicyDistillBackwardArgs(C.Structure):
+    """gvec_policy_distill_backward_args: grad_ce, grad_kl and grad_entropy may be None (= zeros)."""
+    _fields_ = ([("rows", C.c_int64), ("num_actions", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("logits", "mask", "target", "grad_ce", "grad_kl", "grad_entropy", "grad_logits")])
+
+
 class ObsFeaturesArgs(C.Structure):
     """gvec_obs_features_args (include/generals_vec.h): obs and out are device memory."""
     _fields_ = ([("rows", C.c_int64)] + [(n, C.c_int32) for n in ("width", "height", "cap", "reserved")]
@@ -265,6 +277,8 @@ SYMBOLS = {
     "gvec_policy_sample": (_i32, [_i32, _vp, C.POINTER(PolicySampleArgs)]),
     "gvec_policy_evaluate": (_i32, [_i32, _vp, C.POINTER(PolicyEvaluateArgs)]),
     "gvec_policy_backward": (_i32, [_i32, _vp, C.POINTER(PolicyBackwardArgs)]),
+    "gvec_policy_distill": (_i32, [_i32, _vp, C.POINTER(PolicyDistillArgs)]),
+    "gvec_policy_distill_backward": (_i32, [_i32, _vp, C.POINTER(PolicyDistillBackwardArgs)]),
     "gvec_obs_features": (_i32, [_i32, _vp, C.POINTER(ObsFeaturesArgs)]),
     "gvec_obs_memory_update": (_i32, [_i32, _vp, C.POINTER(ObsMemoryArgs)]),
     "gvec_obs_valid_mask": (_i32, [_i32, _vp, C.POINTER(ObsValidMaskArgs)]),

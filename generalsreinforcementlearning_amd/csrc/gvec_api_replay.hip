@@ -270,4 +270,20 @@ int32_t gvec_policy_backward(int32_t device, void* hip_stream, const gvec_policy
   ON_DEVICE(device, launch_policy_backward(*a, reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
+int32_t gvec_policy_distill(int32_t device, void* hip_stream, const gvec_policy_distill_args* a) {
+  if (!a) return null_args("gvec_policy_distill");
+  RET_IF(policy_shape("gvec_policy_distill", a->rows, a->num_actions,
+                      a->rows > 0 && (!a->logits || !a->mask || !a->target || !a->ce || !a->kl || !a->entropy)));
+  if (a->rows == 0) return GVEC_OK;
+  ON_DEVICE(device, launch_policy_distill(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+}
+
+int32_t gvec_policy_distill_backward(int32_t device, void* hip_stream, const gvec_policy_distill_backward_args* a) {
+  if (!a) return null_args("gvec_policy_distill_backward");
+  RET_IF(policy_shape("gvec_policy_distill_backward", a->rows, a->num_actions,
+                      a->rows > 0 && (!a->logits || !a->mask || !a->target || !a->grad_logits)));
+  if (a->rows == 0) return GVEC_OK;
+  ON_DEVICE(device, launch_policy_distill_backward(*a, reinterpret_cast<hipStream_t>(hip_stream)));
+}
+
 }  // extern "C"

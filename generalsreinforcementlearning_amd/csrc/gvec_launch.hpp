@@ -338,6 +338,8 @@ hipError_t launch_traj_gather(const gvec_traj_gather_args& a, hipStream_t s);
 hipError_t launch_policy_sample(const gvec_policy_sample_args& a, hipStream_t s);
 hipError_t launch_policy_evaluate(const gvec_policy_evaluate_args& a, hipStream_t s);
 hipError_t launch_policy_backward(const gvec_policy_backward_args& a, hipStream_t s);
+hipError_t launch_policy_distill(const gvec_policy_distill_args& a, hipStream_t s);
+hipError_t launch_policy_distill_backward(const gvec_policy_distill_backward_args& a, hipStream_t s);
 
 // strategic feature planes (gvec_features.hip; generals_vec.h "strategic feature planes")
 hipError_t launch_obs_features(const gvec_obs_features_args& a, hipStream_t s);

@@ -1,5 +1,6 @@
 // gvec_policy.hip — the masked-categorical policy head of on-device PPO: sample (Gumbel-max or greedy), evaluate and
-// backward over rows of A float32 logits + A mask bytes (gvec_policy_* in generals_vec.h).
+// backward over rows of A float32 logits + A mask bytes (gvec_policy_* in generals_vec.h), and the
+// distillation loss of the same rows against a search's soft target, forward and backward (gvec_policy_distill*; §4.23).
 //
 // One wavefront per row, one row per workgroup.  A row of A <= POLICY_STAGE_MAX is read from HBM once: the masked logits
 // x_i = mask_i ? l_i : -inf go to LDS (16 bytes per lane where the row allows it) and every later pass reads LDS.  S, the set
@@ -208,6 +209,100 @@ __global__ __launch_bounds__(64) void policy_backward_kernel(gvec_policy_backwar
 
 inline size_t policy_lds_bytes(int A) { return A <= POLICY_STAGE_MAX ? (size_t)((A + 3 + 3) / 4) * 16 : 0; }
 
+// ---- distillation against a soft target (generals_vec.h "policy distillation") ----
+// The target row, raw: staged behind the logits' LDS image (a second image of policy_lds_bytes(A), its own pad: the target's
+// alignment need not be the logits'), or read from HBM again by every pass.  tau_i is formed where it is used, from x_i and t_i.
+template <bool STAGED>
+struct Target {
+  const float* t;        // STAGED: LDS
+  __device__ __forceinline__ float operator()(int i, float x) const {
+    const float v = t[i];
+    return (x > NEG_INF && v > 0.0f) ? v : 0.0f;    // NaN > 0 is false: dropped with the negatives
+  }
+};
+// Issues the target's loads; the barrier of the open_row that follows publishes them along with the logits.
+template <bool STAGED>
+__device__ __forceinline__ Target<STAGED> open_target(const float* __restrict__ t, int A, int lds_quads) {
+  if (!STAGED) return Target<STAGED>{t};
+  int head, quads;
+  quad_split(t, A, head, quads);
+  const int pad = (4 - head) & 3;
+  float* x = reinterpret_cast<float*>(policy_lds + lds_quads) + pad;
+  const float4* __restrict__ tq = reinterpret_cast<const float4*>(t + head);
+  float4* xq = reinterpret_cast<float4*>(x + head);
+#pragma unroll 4
+  for (int j = lane_id(); j < quads; j += 64) xq[j] = tq[j];
+  const int i0 = lane_id();
+  if (i0 < head) x[i0] = t[i0];
+  const int i1 = head + 4 * quads + lane_id();
+  if (i1 < A) x[i1] = t[i1];
+  return Target<STAGED>{x};
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(64) void policy_distill_kernel(gvec_policy_distill_args P, int lds_quads) {
+  const long long r = blockIdx.x;
+  const int A = P.num_actions;
+  const Target<STAGED> tau = open_target<STAGED>(P.target + (size_t)r * A, A, lds_quads);
+  const Row<STAGED> row = open_row<STAGED>(P.logits + (size_t)r * A, P.mask + (size_t)r * A, A);
+  const RowStats s = row_stats(row, A, row_max(row, A));
+  float c = 0.0f, k = 0.0f;
+  if (!s.dead) {
+    for (int i = lane_id(); i < A; i += 64) {
+      const float v = row(i), t = tau(i, v);
+      if (t > 0.0f) {
+        const float lp = (v - s.m) - s.logz;
+        c = c + t * lp;
+        k = k + t * (logf(t) - lp);
+      }
+    }
+  }
+  c = wave_sum(c);
+  k = wave_sum(k);
+  if (lane_id() == 0) {
+    P.ce[r] = s.dead ? 0.0f : -c;              // one-hot: c is that action's logp, summed with zeros
+    P.kl[r] = s.dead ? 0.0f : k;
+    P.entropy[r] = s.ent;
+  }
+}
+
+template <bool STAGED>
+__device__ __forceinline__ float distill_grad_of(const Row<STAGED>& row, const Target<STAGED>& tau, const RowStats& s, int i, float g,
+                                                 float tsum, float ge) {
+  const float v = row(i);
+  if (s.dead || !(v > NEG_INF)) return 0.0f;
+  const float lp = (v - s.m) - s.logz, p = expf(lp);
+  return g * (tsum * p - tau(i, v)) - (ge * p) * (lp + s.ent);
+}
+template <bool STAGED>
+__global__ __launch_bounds__(64) void policy_distill_backward_kernel(gvec_policy_distill_backward_args P, int lds_quads) {
+  const long long r = blockIdx.x;
+  const int A = P.num_actions;
+  const Target<STAGED> tau = open_target<STAGED>(P.target + (size_t)r * A, A, lds_quads);
+  const Row<STAGED> row = open_row<STAGED>(P.logits + (size_t)r * A, P.mask + (size_t)r * A, A);
+  const RowStats s = row_stats(row, A, row_max(row, A));
+  float tsum = 0.0f;
+  if (!s.dead) {
+    for (int i = lane_id(); i < A; i += 64) tsum = tsum + tau(i, row(i));
+  }
+  tsum = wave_sum(tsum);
+  const float g = (P.grad_ce ? P.grad_ce[r] : 0.0f) + (P.grad_kl ? P.grad_kl[r] : 0.0f);
+  const float ge = P.grad_entropy ? P.grad_entropy[r] : 0.0f;
+  float* __restrict__ out = P.grad_logits + (size_t)r * A;
+  int head, quads;
+  quad_split(out, A, head, quads);
+  float4* oq = reinterpret_cast<float4*>(out + head);
+  for (int j = lane_id(); j < quads; j += 64) {
+    const int i = head + 4 * j;
+    oq[j] = make_float4(distill_grad_of(row, tau, s, i, g, tsum, ge), distill_grad_of(row, tau, s, i + 1, g, tsum, ge),
+                        distill_grad_of(row, tau, s, i + 2, g, tsum, ge), distill_grad_of(row, tau, s, i + 3, g, tsum, ge));
+  }
+  const int i0 = lane_id();
+  if (i0 < head) out[i0] = distill_grad_of(row, tau, s, i0, g, tsum, ge);
+  const int i1 = head + 4 * quads + lane_id();
+  if (i1 < A) out[i1] = distill_grad_of(row, tau, s, i1, g, tsum, ge);
+}
+
 }  // namespace
 
 hipError_t launch_policy_sample(const gvec_policy_sample_args& a, hipStream_t s) {
@@ -235,6 +330,27 @@ hipError_t launch_policy_backward(const gvec_policy_backward_args& a, hipStream_
     hipLaunchKernelGGL(policy_backward_kernel<true>, grid, dim3(64), policy_lds_bytes(a.num_actions), s, a);
   } else {
     hipLaunchKernelGGL(policy_backward_kernel<false>, grid, dim3(64), 0, s, a);
+  }
+  return hipGetLastError();
+}
+// two LDS images per row, logits then target: 41 KB at A = 5120, under the 64 KB a launch may ask for without an attribute
+hipError_t launch_policy_distill(const gvec_policy_distill_args& a, hipStream_t s) {
+  const dim3 grid((unsigned)a.rows);
+  const size_t image = policy_lds_bytes(a.num_actions);
+  if (a.num_actions <= POLICY_STAGE_MAX) {
+    hipLaunchKernelGGL(policy_distill_kernel<true>, grid, dim3(64), 2 * image, s, a, (int)(image / 16));
+  } else {
+    hipLaunchKernelGGL(policy_distill_kernel<false>, grid, dim3(64), 0, s, a, 0);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_policy_distill_backward(const gvec_policy_distill_backward_args& a, hipStream_t s) {
+  const dim3 grid((unsigned)a.rows);
+  const size_t image = policy_lds_bytes(a.num_actions);
+  if (a.num_actions <= POLICY_STAGE_MAX) {
+    hipLaunchKernelGGL(policy_distill_backward_kernel<true>, grid, dim3(64), 2 * image, s, a, (int)(image / 16));
+  } else {
+    hipLaunchKernelGGL(policy_distill_backward_kernel<false>, grid, dim3(64), 0, s, a, 0);
   }
   return hipGetLastError();
 }

@@ -10,11 +10,18 @@ GeneralsSelfPlayVecEnv) gives action 0, logp 0, entropy 0 and zero gradients - n
     actions, logp, entropy = head.sample(policy_logits, buf.valid_actions_mask, seed=step)      # [B, L] each
     new_logp, entropy = head.evaluate(policy_logits, batch["valid_actions_mask"], batch["action"])
 
+Two more train the same logits on a search's policy target: gvec_policy_distill and
+gvec_policy_distill_backward, the masked soft-target cross-entropy / KL and its gradient, sharing the rows' code and rounding.
+
+    ce, kl, entropy = head.distill(policy_logits, batch["valid_actions_mask"], batch["policy_target"])
+    loss = distill_loss(policy_logits, batch["valid_actions_mask"], batch["policy_target"], batch["weight"])
+
 Everything runs on the current torch stream; nothing synchronises with the host.
 """
 import ctypes as C
 
-from ._lib import GvecError, PolicyBackwardArgs, PolicyEvaluateArgs, PolicySampleArgs, check, load
+from ._lib import (GvecError, PolicyBackwardArgs, PolicyDistillArgs, PolicyDistillBackwardArgs, PolicyEvaluateArgs, PolicySampleArgs,
+                   check, load)
 
 
 class MaskedCategoricalHead:
@@ -58,6 +65,33 @@ class MaskedCategoricalHead:
                 return grad, None, None
 
         self._evaluate = _Evaluate
+
+        class _Distill(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, logits, mask, target):
+                rows, A = logits.shape
+                ce, kl, ent = (t.empty(rows, dtype=t.float32, device=dev) for _ in range(3))
+                a = PolicyDistillArgs(rows=rows, num_actions=A, logits=logits.data_ptr(), mask=mask.data_ptr(), target=target.data_ptr(),
+                                      ce=ce.data_ptr(), kl=kl.data_ptr(), entropy=ent.data_ptr())
+                check(L.gvec_policy_distill(dev.index, stream(), C.byref(a)), "gvec_policy_distill")
+                ctx.save_for_backward(logits, mask, target)    # the inputs themselves: p and tau are recomputed from them
+                return ce, kl, ent
+
+            @staticmethod
+            def backward(ctx, grad_ce, grad_kl, grad_entropy):
+                logits, mask, target = ctx.saved_tensors
+                rows, A = logits.shape
+                f32 = lambda g: None if g is None else g.to(dtype=t.float32).contiguous()
+                gc, gk, ge = f32(grad_ce), f32(grad_kl), f32(grad_entropy)
+                ptr = lambda g: None if g is None else g.data_ptr()
+                grad = t.empty_like(logits)                    # every element is written by the kernel
+                a = PolicyDistillBackwardArgs(rows=rows, num_actions=A, logits=logits.data_ptr(), mask=mask.data_ptr(),
+                                              target=target.data_ptr(), grad_ce=ptr(gc), grad_kl=ptr(gk), grad_entropy=ptr(ge),
+                                              grad_logits=grad.data_ptr())
+                check(L.gvec_policy_distill_backward(dev.index, stream(), C.byref(a)), "gvec_policy_distill_backward")
+                return grad, None, None                        # the target is a constant
+
+        self._distill = _Distill
 
     @property
     def bad_actions(self):
@@ -113,3 +147,60 @@ class MaskedCategoricalHead:
             return z.view(lead), z.view(lead)
         logp, ent = self._evaluate.apply(logits, mask, actions)
         return logp.view(lead), ent.view(lead)
+
+    def distill(self, logits, mask, target):
+        """(ce, kl, entropy) of logits [..., A] against a soft target, each of the leading shape; differentiable with respect
+        to logits (the backward is gvec_policy_distill_backward), the target gets no gradient.  target: float32 of the shape
+        of logits, what HalvingSearch.policy_target / SelfPlayRolloutBuffer.gather return; it need not be normalised, and
+        mass on illegal actions, negative and NaN entries are dropped.  ce = -sum tau_i logp_i, kl = sum tau_i (log tau_i -
+        logp_i); a row without a legal action gives zeros and a zero gradient."""
+        _check_distill_inputs(logits, mask, target)            # a ValueError before any library call
+        t = self._t
+        lead, rows, A = self._rows(logits, mask)
+        logits, mask = self._as(logits, t.float32, (rows, A)), self._as(mask, t.uint8, (rows, A))
+        target = self._as(target.detach(), t.float32, (rows, A))
+        if rows == 0:
+            z = logits.sum(-1)
+            return z.view(lead), z.view(lead), z.view(lead)
+        ce, kl, ent = self._distill.apply(logits, mask, target)
+        return ce.view(lead), kl.view(lead), ent.view(lead)
+
+
+def _check_distill_inputs(logits, mask, target):
+    import torch
+    for name, x in (("logits", logits), ("mask", mask), ("target", target)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"distill: {name} must be a torch tensor, not {type(x).__name__}")
+    if logits.dim() < 1:
+        raise ValueError("distill: logits must be [..., A]")
+    if tuple(mask.shape) != tuple(logits.shape):
+        raise ValueError(f"mask {tuple(mask.shape)} and logits {tuple(logits.shape)} must have the same shape")
+    if tuple(target.shape) != tuple(logits.shape):
+        raise ValueError(f"target {tuple(target.shape)} and logits {tuple(logits.shape)} must have the same shape")
+    if target.dtype != torch.float32:
+        raise ValueError(f"target must be float32, not {target.dtype}")
+
+
+_heads = {}
+
+
+def distill_loss(logits, mask, target, weight=None):
+    """The policy loss of search distillation: the `weight`-weighted mean over rows of MaskedCategoricalHead.distill's ce,
+    sum(weight * ce) / max(sum(weight), 1); weight None counts every row once.  `weight` is of the leading shape of logits
+    (SelfPlayRolloutBuffer.gather's batch["weight"]: 0 on rejected positions)."""
+    import torch
+    _check_distill_inputs(logits, mask, target)
+    if weight is not None and tuple(weight.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"weight {tuple(weight.shape)} must have the leading shape {tuple(logits.shape[:-1])} of logits")
+    index = logits.device.index if logits.is_cuda else None    # elsewhere: the current device, as MaskedCategoricalHead() takes it
+    if index is None and torch.cuda.is_available():
+        index = torch.cuda.current_device()
+    head = _heads.get(index)
+    if head is None:
+        head = MaskedCategoricalHead(index)                    # raises without a GPU: there is no host path
+        _heads[index] = head
+    ce, _, _ = head.distill(logits, mask, target)
+    if weight is None:
+        return ce.sum() / max(ce.numel(), 1)
+    w = weight.to(device=ce.device, dtype=torch.float32)
+    return (w * ce).sum() / w.sum().clamp(min=1.0)

@@ -39,6 +39,13 @@ Nothing here synchronises with the host, except minibatches(compact=True): one 8
 memory=ObservationMemory((num_envs, num_learners), H, W) carries the fog-of-war memory planes (memory.py, DESIGN.md section
 4.14) along: every step's update writes straight into slot t + 1 of a store beside the observations', `buf.memory` is the
 current slot's view and every batch has a "memory" entry.  Without it nothing is allocated or launched.
+
+policy_target=True keeps what a search says about every step beside what the actor did: a float32
+target over the 5 * H * W actions of a row and the search's value, given to `step`, returned by `gather` as
+batch["policy_target"] / batch["search_value"] and consumed by MaskedCategoricalHead.distill / distill_loss.  target_store is
+float32 [T, N, 5 * H * W]: one more mask store times four (4 bytes per action where the mask has one; 18.4 MB per step at
+4,096 streams on 15x15).  `buf.policy_target_slot` is slot t's view, for a search that writes there directly.  Without it
+nothing is allocated, launched or added to any batch.
 """
 import ctypes as C
 
@@ -46,7 +53,7 @@ from ._lib import TRAJ_VALID, TrajCompactArgs, TrajGaeArgs, TrajGatherArgs, Traj
 
 
 class SelfPlayRolloutBuffer:
-    def __init__(self, env, horizon, gamma=0.99, gae_lambda=0.95, memory=None):
+    def __init__(self, env, horizon, gamma=0.99, gae_lambda=0.95, memory=None, policy_target=False):
         import torch
         if not getattr(env, "device_outputs", False):
             raise ValueError("SelfPlayRolloutBuffer needs an env built with device_outputs=True")
@@ -57,6 +64,8 @@ class SelfPlayRolloutBuffer:
         want = ((env.num_envs, env.num_learners), env.board_height, env.board_width)
         if memory is not None and (getattr(memory, "rows_shape", None), getattr(memory, "height", None), getattr(memory, "width", None)) != want:
             raise ValueError(f"memory must be an ObservationMemory of rows_shape {want[0]} on a {want[2]}x{want[1]} board")
+        if not isinstance(policy_target, bool):
+            raise ValueError(f"policy_target must be True or False: {policy_target!r}")
         self._t = t = torch
         self.env = env
         self.horizon = T = int(horizon)
@@ -89,6 +98,9 @@ class SelfPlayRolloutBuffer:
         self.mem_store = None if memory is None else z((T + 1, N, 4, nb), t.float32)
         self._rho = self._vt_value = None                               # V-trace's stores: allocated by the first finish_vtrace
         self._vtrace = False
+        self._has_target = policy_target
+        self.target_store = z((T, N, 5 * nb), t.float32) if policy_target else None
+        self.search_value_store = z((T, N), t.float32) if policy_target else None
 
     # ---- collection ---------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -114,6 +126,43 @@ class SelfPlayRolloutBuffer:
     def valid_actions_mask(self):
         return self.mask_store[self._step].view(self._t.bool)
 
+    @property
+    def policy_target_slot(self):
+        """Where the current step's policy target goes [B, L, 5 * H * W]: a view of slot t (None without policy_target=True).
+        A target written here and then handed to `step` is not copied again."""
+        if self.target_store is None:
+            return None
+        if self.full:
+            raise RuntimeError(f"the rollout is full ({self.horizon} steps): there is no slot {self._step}")
+        return self.target_store[self._step].view(self.num_envs, self.num_learners, -1)
+
+    def _take_target(self, policy_target, search_value):
+        """step's two optional arguments, checked: every ValueError comes before anything is launched or stored."""
+        t = self._t
+        if not self._has_target:
+            if policy_target is not None or search_value is not None:
+                raise ValueError("step() got a policy_target / search_value, but the buffer was built with policy_target=False")
+            return None
+        if policy_target is None:
+            raise ValueError("the buffer was built with policy_target=True: step() needs the step's policy_target")
+        A = self.mask_bytes
+        if not isinstance(policy_target, t.Tensor) or policy_target.dtype != t.float32 or policy_target.dim() < 1 \
+                or policy_target.shape[-1] != A or policy_target.numel() != self.num_streams * A:
+            raise ValueError(f"policy_target must be a float32 tensor [{self.num_envs}, {self.num_learners}, {A}]")
+        if search_value is not None and (not isinstance(search_value, t.Tensor) or search_value.numel() != self.num_streams):
+            raise ValueError(f"search_value must be a tensor of {self.num_envs} x {self.num_learners} elements")
+        return policy_target, search_value
+
+    def _store_target(self, k, policy_target, search_value):
+        row = self.target_store[k]
+        same = policy_target.device == row.device and policy_target.data_ptr() == row.data_ptr() and policy_target.is_contiguous()
+        if not same:                                                    # the slot's own view was written in place: nothing to copy
+            row.copy_(policy_target.reshape(row.shape))
+        if search_value is None:
+            self.search_value_store[k].zero_()
+        else:
+            self.search_value_store[k].copy_(search_value.reshape(-1))
+
     def begin(self, obs, info):
         """After env.reset(): slot 0 takes the observation and the mask, every learner is alive."""
         self.obs_store[0].copy_(obs)
@@ -133,14 +182,19 @@ class SelfPlayRolloutBuffer:
             x = t.as_tensor(x, dtype=dtype).to(self._dev).reshape(self.num_streams).contiguous()
         return x
 
-    def step(self, actions, logp, value):
+    def step(self, actions, logp, value, policy_target=None, search_value=None):
         """env.step(actions) with the observation and mask written into slot t + 1, then row t of the small stores in one
         launch.  actions int64, logp / value float32, [B, L] each (CUDA, contiguous: anything else is converted first).
+        On a buffer built with policy_target=True: policy_target float32 [B, L, 5 * H * W] (required) and search_value
+        [B, L] (optional: zeros) go into row t of target_store / search_value_store; `policy_target_slot` itself is not copied.
         Returns the env's tuple."""
+        target = self._take_target(policy_target, search_value)
         k = self._step
         if k >= self.horizon:
             raise RuntimeError(f"the rollout is full ({self.horizon} steps): finish() and next_rollout() come first")
         t = self._t
+        if target is not None:
+            self._store_target(k, *target)
         actions, logp, value = self._as(actions, t.int64), self._as(logp, t.float32), self._as(value, t.float32)
         out = self.env.step(actions, obs_out=self.obs_store[k + 1], mask_out=self.mask_store[k + 1])
         _, reward, terminated, truncated, info = out
@@ -270,6 +324,8 @@ class SelfPlayRolloutBuffer:
                                 "adv": e(m, t.float32), "weight": e(m, t.float32)}
             if self.mem_store is not None:
                 o["memory"] = e((m, 4, env.board_height, env.board_width), t.float32)
+            if self._has_target:
+                o["policy_target"], o["search_value"] = e((m, self.mask_bytes), t.float32), e(m, t.float32)
         return o
 
     def gather(self, pos, normalize=True):
@@ -278,7 +334,8 @@ class SelfPlayRolloutBuffer:
         rows when `normalize`) and weight (1 for a valid row, 0 otherwise) [M].  The tensors are reused by the next gather of
         the same M.  With memory=: also memory [M, 4, H, W], the planes stored at the same positions (a position outside the
         rollout, which `rejected` counts and whose weight is 0, gets those of the nearest row).  After finish_vtrace: also rho [M],
-        fetched the same way."""
+        fetched the same way.  With policy_target=True: also policy_target float32 [M, 5 * H * W] and search_value [M], the
+        rows of target_store / search_value_store at the same (clamped) positions."""
         self._done()
         m = int(pos.numel())
         o = self._outputs(m)
@@ -296,6 +353,12 @@ class SelfPlayRolloutBuffer:
             rows = self.mem_store.view(-1, self.mem_floats)[:self.horizon * self.num_streams]
             self._t.index_select(rows, 0, pos.clamp(0, rows.shape[0] - 1), out=o["memory"].view(m, self.mem_floats))
             batch["memory"] = o["memory"]
+        if self._has_target:
+            rows = self.target_store.view(-1, self.mask_bytes)
+            at = pos.clamp(0, rows.shape[0] - 1)
+            self._t.index_select(rows, 0, at, out=o["policy_target"])
+            self._t.index_select(self.search_value_store.view(-1), 0, at, out=o["search_value"])
+            batch["policy_target"], batch["search_value"] = o["policy_target"], o["search_value"]
         if self._vtrace:
             if "rho" not in o:
                 o["rho"] = self._t.empty(m, dtype=self._t.float32, device=self._dev)

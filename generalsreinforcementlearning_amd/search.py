@@ -438,11 +438,12 @@ class HalvingSearch:
         ok = info["found"] & (info["action"] >= 0)
         return torch.where(ok, info["action"], torch.zeros((), dtype=torch.int64, device=dev)), info
 
-    def policy_target(self, logits, mask, info, value=None):
+    def policy_target(self, logits, mask, info, value=None, out=None):
         """logits float32 [n, A] or None (uniform over the legal set), mask bool / uint8 [n, A], info with candidates, sum and
         count as act() returns them, value float32 [n] or None (the net's value in score units): contiguous CUDA tensors ->
         (target float32 [n, A], v_mix float32 [n]): gvec_search_improved_policy, softmax over the legal set of logits +
-        sigma(completed q) - q the playout mean on the visited actions, v_mix elsewhere."""
+        sigma(completed q) - q the playout mean on the visited actions, v_mix elsewhere.  out: a contiguous float32 [n, A]
+        tensor that takes the target instead of a new one (SelfPlayRolloutBuffer.policy_target_slot, flattened)."""
         import torch
         from ._lib import SearchPolicyArgs, load
         first = self._rounds[0]
@@ -464,7 +465,11 @@ class HalvingSearch:
                         ("info['sum']", info["sum"]), ("info['count']", info["count"])):
             if t is not None and not t.is_contiguous():
                 raise ValueError(f"{name} must be contiguous")
-        target = torch.empty((n, A), dtype=torch.float32, device=dev)
+        if out is not None:
+            first._check(out, "out", torch.float32, (n, A), dev)
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+        target = torch.empty((n, A), dtype=torch.float32, device=dev) if out is None else out
         v_mix = torch.empty((n,), dtype=torch.float32, device=dev)
         if n == 0:
             return target, v_mix

@@ -968,6 +968,43 @@ int32_t gvec_policy_sample(int32_t device, void* hip_stream, const gvec_policy_s
 int32_t gvec_policy_evaluate(int32_t device, void* hip_stream, const gvec_policy_evaluate_args* args);
 int32_t gvec_policy_backward(int32_t device, void* hip_stream, const gvec_policy_backward_args* args);
 
+/* ---- policy distillation: masked soft-target cross-entropy / KL against a search's policy target ----
+ * The loss that trains the prior on what gvec_search_improved_policy wrote.  Same conventions, same rows, same S, m, Z, logp_i,
+ * p_i, H and the same reduction orders as the policy head above (the kernels share its code, operation for operation).
+ * target float32[rows][A] needs no normalisation.  Per row:
+ *   tau_i = target_i where i in S and target_i > 0, otherwise 0: mass on illegal actions, negative and NaN entries are dropped
+ *           (nothing is counted, nothing synchronises);
+ *   Tsum = sum_i tau_i;
+ *   ce = -sum_{tau_i > 0} tau_i * logp_i;
+ *   kl = sum_{tau_i > 0} tau_i * (log tau_i - logp_i), a sum of its own (not ce - H(tau)): >= 0 up to rounding when Tsum = 1;
+ *   entropy = H.
+ * A dead row gives ce = kl = entropy = 0.  A one-hot target at a legal action a gives ce = -logp_a with the bits of
+ * gvec_policy_evaluate; |S| = 1 gives ce = 0; an all-zero target gives ce = kl = 0.
+ * gvec_policy_distill: ce, kl, entropy float32[rows], every element written.
+ * gvec_policy_distill_backward: grad_logits float32[rows][A], EVERY element written, everything recomputed from the inputs.
+ *   With g = grad_ce[r] + grad_kl[r] (d kl / d logits = d ce / d logits: the target is a constant and gets no gradient):
+ *   i in S: g * (Tsum * p_i - tau_i) - (grad_entropy[r] * p_i) * (logp_i + H);  otherwise, and on a dead row, 0.
+ *   grad_ce / grad_kl / grad_entropy float32[rows], each may be NULL (= zeros).  |S| = 1 gives exact zeros.
+ * A row of A <= 5120 reads logits, mask and target from HBM once per kernel (9 A bytes forward, 13 A backward with the
+ * gradient's store); a longer row reads them again in every pass.
+ * GVEC_E_INVALID (with a gvec_last_error message) before anything touches a device: args NULL, num_actions < 1, rows < 0 or
+ *   rows >= 2^31, or rows > 0 and a required pointer NULL.  rows == 0 is a no-op that needs no device. */
+typedef struct gvec_policy_distill_args {
+  int64_t rows;
+  int32_t num_actions, reserved;
+  const float* logits; const uint8_t* mask; const float* target;
+  float* ce; float* kl; float* entropy;
+} gvec_policy_distill_args;
+typedef struct gvec_policy_distill_backward_args {
+  int64_t rows;
+  int32_t num_actions, reserved;
+  const float* logits; const uint8_t* mask; const float* target;
+  const float* grad_ce; const float* grad_kl; const float* grad_entropy;                   /* NULL: zeros */
+  float* grad_logits;
+} gvec_policy_distill_backward_args;
+int32_t gvec_policy_distill(int32_t device, void* hip_stream, const gvec_policy_distill_args* args);
+int32_t gvec_policy_distill_backward(int32_t device, void* hip_stream, const gvec_policy_distill_backward_args* args);
+
 /* ---- strategic feature planes: a pure function of the observation ------------------------------------
  * Five planes a small conv torso cannot compute for itself, from the nine planes of any observation: what a step returned, a
  * replay or rollout minibatch.  Handle-free like the policy head: DEVICE pointers on `device`, enqueued on hip_stream, nothing
