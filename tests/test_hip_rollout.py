@@ -180,8 +180,12 @@ def _assert_gae(reward, value, flags, gamma, lam, ctx):
     return adv, ret, st
 
 
-@pytest.mark.parametrize("T", [1, 2, 128, 512])
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 8192])
+# T = 33 and 95: a full 32-row chunk, then a partial one; N = 16,448: 257 per-wavefront partials, so a thread of the
+# statistics' second stage (stride 256) adds two
+GAE_CASES = [(T, N) for T in (1, 2, 33, 95, 128, 512) for N in (1, 63, 64, 65, 8192)] + [(2, 16448)]
+
+
+@pytest.mark.parametrize("T,N", GAE_CASES, ids=[f"{N}-{T}" for T, N in GAE_CASES])
 def test_gae_against_the_restatement(T, N):
     rng = np.random.default_rng(1000 * T + N)
     reward, value, flags = R.random_rollout(rng, T, N)

@@ -89,6 +89,12 @@ def test_traj_gather_one_wavefront_per_row():
     _traj_gather(_lib(), np.random.default_rng(99), 16384, 17, 5)
 
 
+@pytest.mark.parametrize("M", [5000, 10000])
+def test_traj_gather_two_and_four_wavefronts_per_row(M):
+    """M = 10,000: shift 1; M = 5,000: shift 2 (split_shift: the smallest shift with M << shift >= 16,384)"""
+    _traj_gather(_lib(), np.random.default_rng(M), M, 17, 5)
+
+
 def _nstep_gather(L, rng, k, F):
     """gvec_nstep_gather with n_step 1 (no links: ring[idx] row for row) at all 16 (ring, output) offsets"""
     import torch
@@ -131,6 +137,12 @@ def test_nstep_gather_rows_at_every_alignment(F):
 
 def test_nstep_gather_one_wavefront_per_row():
     _nstep_gather(_lib(), np.random.default_rng(98), 16384, 17)
+
+
+@pytest.mark.parametrize("k", [5000, 10000])
+def test_nstep_gather_two_and_four_wavefronts_per_row(k):
+    """k = 10,000: shift 1; k = 5,000: shift 2"""
+    _nstep_gather(_lib(), np.random.default_rng(k), k, 17)
 
 
 # ---- the one-workgroup scan ----------------------------------------------------------------------------------------------
@@ -177,7 +189,7 @@ def test_compact_at_the_scan_s_group_counts(total, groups):
     assert got[0] == -7 and np.array_equal(got[1:1 + want.size], want) and (got[1 + want.size:] == -7).all()
 
 
-@pytest.mark.parametrize("workers,groups", [(64, 1), (65, 2), (65536, 1024), (65537, 1025)])
+@pytest.mark.parametrize("workers,groups", [(64, 1), (65, 2), (5000, 79), (10000, 157), (65536, 1024), (65537, 1025)])   # 5,000 / 10,000: the copy's shift 2 / 1
 def test_pool_collect_at_the_scan_s_group_counts(workers, groups):
     """One gvec_pool_collect step with obs_floats = 1 from a ring that is about to wrap: the ring against RingModel (the host
     restatement of tests/test_nstep_replay.py), the result rows against the over-workers in ascending order."""

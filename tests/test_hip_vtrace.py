@@ -87,8 +87,11 @@ def _assert_vtrace(reward, value, flags, lt, lb, gamma, lam, rho_bar, c_bar, ctx
 
 
 # ---- 1. the kernel against the restatement -------------------------------------------------------------------------------
-@pytest.mark.parametrize("T", [1, 2, 33, 128])
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 8192])
+# N = 16,448: 257 per-wavefront partials, so a thread of the statistics' second stage (stride 256) adds two
+VTRACE_CASES = [(T, N) for T in (1, 2, 33, 128) for N in (1, 63, 64, 65, 8192)] + [(2, 16448)]
+
+
+@pytest.mark.parametrize("T,N", VTRACE_CASES, ids=[f"{N}-{T}" for T, N in VTRACE_CASES])
 def test_vtrace_against_the_restatement(T, N):
     rng = np.random.default_rng(1000 * T + N)
     reward, value, flags = R.random_rollout(rng, T, N)
