@@ -2,6 +2,7 @@
 // buffer access, and the helpers of gvec_handle.hpp that every host unit calls.  The entry points of each subsystem are in
 // gvec_api_<subsystem>.hip (DESIGN.md "Translation units").  Plain HIP runtime only (no torch, no CPU fallback): every
 // compute entry point launches gfx950 kernels and fails with GVEC_E_NO_DEVICE when there is no GPU.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <new>
@@ -67,6 +68,9 @@ StepArgs base_args(const gvec_handle* h) {
   a.pool_seed_hi = (uint32_t)(h->pool_seed >> 32);
   a.env_base = h->env_base;
   if (h->cfg.auto_reset && h->pool_size > 0) a.flags |= KF_AUTORESET;
+  // update_stats sums narrow envs' armies with 24-bit multiplies: a turn can merge MAXP armies of 65,535 on one tile
+  // before production adds a rate to it, so a rate above 2^24 - 1 - 8 * 65,535 takes the 32-bit sums and no ordinary path
+  if (std::max(a.prod_general, std::max(a.prod_city, a.prod_normal)) > 0xFFFFFF - 8 * 65535) a.flags |= KF_BIGRATE;
   return a;
 }
 

@@ -259,6 +259,7 @@ struct VariantGeom {
 constexpr uint32_t KF_AGENT = 1u;      // sample actions on device instead of reading them
 constexpr uint32_t KF_EMIT = 2u;       // write legal-action masks
 constexpr uint32_t KF_AUTORESET = 4u;  // re-deal finished envs from the pool
+constexpr uint32_t KF_BIGRATE = 32u;   // a production rate so large that one turn takes a narrow army past 24 bits (host: base_args)
 constexpr uint32_t KF_LMVALID = 16u;   // args.legal already holds the masks of the current state
 
 struct StepArgs {

@@ -194,7 +194,7 @@ __device__ __forceinline__ ArmyRef gym_load_turn(Turn<K::MAXP, K::NSLOT>& b, con
   b.lscr = scratch;
   const ArmyRef army_env = army_ref<K::NSLOT>(A.army16, A.army32, env);
   load_turn<true, lean_half_last(K::NSLOT, K::ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * K::ROW_DW, army_env, K::FD, A.zeros);
-  b.small = !(b.hflags & HF_WIDE);
+  b.small = !(b.hflags & HF_WIDE) && !(A.flags & KF_BIGRATE);
   return army_env;
 }
 // The turn (step_kernel's body): an env that is over or `rs` is re-dealt; every other one plays the on-device agent's moves

@@ -109,7 +109,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (step_waves<MAXP, NSLOT>())) 
   } else {
     load_turn<true, lean_half_last(NSLOT, ODD)>(b, A.hdr + (size_t)env * HDR_DW, A.rows + (size_t)env * ROW_DW, army_env, FD, A.zeros);
   }
-  b.small = !(b.hflags & HF_WIDE);  // one turn from armies <= 65535: every sum of the turn stays below 2^23
+  // one turn from armies <= 65535 at a rate below KF_BIGRATE's: every army of the turn stays below 2^24 (update_stats' mad24)
+  b.small = !(b.hflags & HF_WIDE) && !(A.flags & KF_BIGRATE);
   const bool emit = (A.flags & KF_EMIT) != 0u;
   uint32_t m[B::NR][4];
   uint32_t err = 0u;

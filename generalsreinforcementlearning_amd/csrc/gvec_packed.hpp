@@ -351,16 +351,18 @@ struct PBoard {
   // counted: the env is live, its armies are in narrow form, its lists equal its ownership (lists_match() holds without
   // looking: load_lists copies them), its stats are in sync, V holds at most a tile per player and stays below the
   // fog's threshold (P <= N / 10), the board has few special tiles, and the turn about to be played is not turn 0 -
-  // nor, with NOGROW, a growth turn.  turn_step<ORD> and its phases fold exactly these facts; whatever the turn itself
+  // nor, with NOGROW, a growth turn - and no production rate is large enough to take a narrow army past the 24 bits the
+  // path's sums read (KF_BIGRATE, set by the host).  turn_step<ORD> and its phases fold exactly these facts; whatever the turn itself
   // brings about (two moves on one tile, an elimination, an abort, an army beyond u16) stays a run-time test there.
   // tests/_ordinary_turn.py restates it.
   // turn t is a growth turn (production_manager.go:27).  interval_magic = ceil(2^32 / interval) (host): t % interval
   // without the vector unit's float reciprocal (a scalar `%` by a run-time value compiles to v_cvt / v_rcp / v_mul / v_cvt +
   // 20 scalar instructions).  q = mulhi(t, magic) is floor(t / interval) or one more while t * interval < 2^32; beyond
-  // that the plain `%`.
+  // that the plain `%`.  Interval 1 has no 32-bit magic (2^32 wraps to 0, and no magic gives q == t): it takes the `%`
+  // branch with every interval of 65,536 and more: (interval - 2) < 0xFFFE as unsigned leaves 2 .. 65,535 on the multiply.
   static __device__ __forceinline__ bool growth_turn(int t, int interval, uint32_t interval_magic) {
     bool g;
-    if ((uint32_t)t < 0x10000u && (uint32_t)interval < 0x10000u) {
+    if ((uint32_t)t < 0x10000u && (uint32_t)(interval - 2) < 0xFFFEu) {
       const uint32_t q = __umulhi((uint32_t)t, interval_magic);  // wave-uniform operands: s_mul_hi_u32
       int32_t r = t - (int32_t)(q * (uint32_t)interval);
       r = r < 0 ? r + interval : r;
@@ -373,7 +375,7 @@ struct PBoard {
   template <int ORD>
   __device__ __forceinline__ bool ordinary_turn(const StepArgs& A) const {
     constexpr uint32_t need = HF_SYNC | HF_VSMALL | HF_FEWSPECIAL, bar = HF_DONE | HF_WIDE | HF_LDIFF;
-    bool ord = (hflags & (need | bar)) == need && turn >= 0 && 10 * P <= N;
+    bool ord = (hflags & (need | bar)) == need && turn >= 0 && 10 * P <= N && !(A.flags & KF_BIGRATE);
     if constexpr ((ORD & GVEC_OT_NOGROW) != 0) ord = ord && !growth_turn(turn + 1, A.interval, A.interval_magic);
     return ord;
   }

@@ -6,13 +6,14 @@ restated once in Python: the envs whose next turn the kernel plays on its straig
     the turn about to be played is not turn 0                       turn >= 0 before the increment
     V stays below the fog's threshold                               P <= N / 10
     not a growth turn (GVEC_ORDTURN bit 4)                          (turn + 1) % interval != 0
+    no production rate that takes a narrow army past 24 bits        max rate <= 0xFFFFFF - 8 * 65,535 (KF_BIGRATE, gvec_api.hip)
 
 `ordinary(flags, state)` takes the header flags of a device batch (tests/_state_forms.py header_flags) or the ones
 `FlagModel` keeps for an oracle batch.  The first three flags and HF_FEWSPECIAL are functions of the state
 (tests/_state_forms.py states them); HF_SYNC and HF_VSMALL are the turn engine's own bookkeeping and no part of the exported
 state, so the model follows them from turn to turn by the rules gvec_packed.hpp gives:
 
-    HF_VSMALL  set by every turn that is played, cleared by a turn with an elimination (tile turnover)
+    HF_VSMALL  set by every turn that is played, cleared by a turn with an elimination (tile turnover: a general was captured)
     HF_SYNC    set by every stats pass; cleared by an aborted turn without an elimination (armies moved, no pass followed); a
                turn that changed no tile runs no pass and leaves it as it was
     both       set by the initial setup of a reset; a re-dealt env takes its pool board's (set, like a reset's)
@@ -25,17 +26,20 @@ HF_VSMALL = 32
 NEED = F.HF_SYNC | HF_VSMALL | F.HF_FEWSPECIAL
 BAR = F.HF_DONE | F.HF_WIDE | F.HF_LDIFF
 NOGROW = True   # GVEC_ORDTURN bit 4 of the shipped default
+BIG_RATE = 0xFFFFFF - 8 * 65535   # above it the engine plays no ordinary turn: the stats pass sums armies with 24-bit multiplies
 
 
-def ordinary(flags, st, interval=25, nogrow=NOGROW):
+def ordinary(flags, st, interval=25, nogrow=NOGROW, prod=(1, 1, 1)):
     """bool[n]: the envs whose NEXT per-turn launch takes the ordinary path.  flags: header flags (H_DIMS >> 24);
-    st: game_state / read_state with turn, players, width, height."""
+    st: game_state / read_state with turn, players, width, height; interval, prod: the engine's production config."""
     flags = np.asarray(flags, np.int64)
     turn = st["turn"].astype(np.int64)
     n = st["width"].astype(np.int64) * st["height"]
     o = ((flags & (NEED | BAR)) == NEED) & (turn >= 0) & (10 * st["players"].astype(np.int64) <= n)
     if nogrow:
         o &= (turn + 1) % interval != 0
+    if max(prod) > BIG_RATE:
+        o &= False
     return o
 
 
@@ -67,7 +71,10 @@ class FlagModel:
         """err, st: what the turn returned and left"""
         was_done = self.prev["done"].astype(bool)
         played = ~was_done
-        elim = st["alive"].astype(np.int64).sum(axis=1) < self.prev["alive"].astype(np.int64).sum(axis=1)
+        # an elimination order: a player's general was captured.  Fewer players alive shows most of them, not all: two players
+        # who take each other's general in one turn are both turned over and both alive again after the stats pass
+        taken = ((self.prev["type"] == 1) & (self.prev["owner"] >= 0) & (st["owner"] != self.prev["owner"])).any(axis=1)
+        elim = taken | (st["alive"].astype(np.int64).sum(axis=1) < self.prev["alive"].astype(np.int64).sum(axis=1))
         aborted = np.asarray(err) != 0
         touched = st["changed"].astype(bool).any(axis=1)
         sync = (self.book & F.HF_SYNC) != 0

@@ -130,13 +130,14 @@ def age_batch(target, seed, env_begin=0, n=None, period=AGED_KINDS + 2, turn_off
         target.write_state(out, lo)
 
 
-def aged_pair(g, mw, mh, maxp, sizes, seed, fog=True, warm=8, warm_permille=80):
+def aged_pair(g, mw, mh, maxp, sizes, seed, fog=True, warm=8, warm_permille=80, prod=(1, 1, 1), interval=25):
     """A VecEngine and an oracle dealt the same boards and pool, `warm` lock-step turns with invalid moves, then aged.
-    g: the loaded package; None: the oracle alone, played and aged the same way (the engine returned is None)."""
+    g: the loaded package; None: the oracle alone, played and aged the same way (the engine returned is None).
+    prod, interval: the production config of both."""
     army, owner, typ, ws, hs, ps = H.gen_boards(seed, sizes, mw, mh)
     B = len(sizes)
-    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=fog, auto_reset=True) if g is not None else None
-    ora = O.OracleBatch(B, mw, mh, maxp, fog=fog)
+    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=fog, auto_reset=True, production=prod, normal_growth_interval=interval) if g is not None else None
+    ora = O.OracleBatch(B, mw, mh, maxp, fog=fog, prod=prod, interval=interval)
     pool = min(16, B)
     for e in (eng, ora) if eng is not None else (ora,):
         e.reset(army, owner, typ, ws, hs, ps)

@@ -52,26 +52,31 @@ def g():
     return g
 
 
-def variant_pair(g, maxp, slots, parity, B=8):
-    """engine (None without g) and oracle on the smallest boards that select the variant, reset: turn 0"""
-    mw, mh, (army, owner, typ, w, h, p) = variant_boards(maxp, slots, parity, B, BOARD_SEEDS.get((maxp, slots, parity), 300 + slots))
-    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=True) if g is not None else None
-    ora = O.OracleBatch(B, mw, mh, maxp, fog=True)
+def variant_pair(g, maxp, slots, parity, B=8, prod=(1, 1, 1), interval=25, seed=None, deal=None):
+    """engine (None without g) and oracle on the smallest boards that select the variant, reset: turn 0.
+    prod, interval: the production config of both; seed: another board seed; deal(army, owner, typ, w, h, p) -> the same six,
+    changed before the reset (tests/_production_cases.py hands the cities out)"""
+    seed = BOARD_SEEDS.get((maxp, slots, parity), 300 + slots) if seed is None else seed
+    mw, mh, boards = variant_boards(maxp, slots, parity, B, seed)
+    army, owner, typ, w, h, p = boards if deal is None else deal(*boards)
+    eng = g.VecEngine(B, mw, mh, maxp, fog_of_war=True, production=prod, normal_growth_interval=interval) if g is not None else None
+    ora = O.OracleBatch(B, mw, mh, maxp, fog=True, prod=prod, interval=interval)
     for e in (eng, ora) if eng is not None else (ora,):
         e.reset(army, owner, typ, w, h, p)
     return eng, ora
 
 
-def lockstep(eng, ora, model, turns, seed, permille, ctx, acts_of=None, auto_reset=False):
+def lockstep(eng, ora, model, turns, seed, permille, ctx, acts_of=None, auto_reset=False, prod=(1, 1, 1), interval=25, watch=None):
     """H.run_lockstep's loop, a turn at a time: error code, masks and the full state every turn, and before every turn the
     device's own header flags against the model's (tests/_ordinary_turn.py) - which envs take the ordinary path.
-    eng None: the oracle alone.  Returns (ordinary env-turns, live env-turns)."""
+    eng None: the oracle alone.  prod, interval: the production config both were built with.  watch(before, after): called
+    with the oracle's states around every turn.  Returns (ordinary env-turns, live env-turns)."""
     n_ord = n_live = 0
     for k in range(turns):
         live = ~model.prev["done"].astype(bool)
-        o = T.ordinary(model.flags(), model.prev)
+        o = T.ordinary(model.flags(), model.prev, interval=interval, prod=prod)
         if eng is not None:
-            dev = T.ordinary(F.header_flags(eng), model.prev)
+            dev = T.ordinary(F.header_flags(eng), model.prev, interval=interval, prod=prod)
             assert np.array_equal(dev[live], o[live]), f"{ctx} turn {k}: the device's flags make envs {np.flatnonzero((dev != o) & live)[:8]} ordinary = {dev[(dev != o) & live][:8]}, the model says otherwise"
         n_ord, n_live = n_ord + int((o & live).sum()), n_live + int(live.sum())
         acts = ora.agent_actions(seed, permille) if acts_of is None else acts_of(k)
@@ -82,6 +87,8 @@ def lockstep(eng, ora, model, turns, seed, permille, ctx, acts_of=None, auto_res
             assert np.array_equal(herr, oerr), f"{ctx} turn {k}: err differs in envs {np.flatnonzero(herr != oerr)[:8]}: hip={herr[herr != oerr][:8]} ora={oerr[herr != oerr][:8]}"
             assert np.array_equal(hbits, obits), f"{ctx} turn {k}: legal mask differs in envs {np.unique(np.argwhere(hbits != obits)[:, 0])[:8]}"
             H.assert_states_equal(eng.game_state(), st, f"{ctx} after turn {k + 1}")
+        if watch is not None:
+            watch(model.prev, st)
         model.step(oerr, st, auto_reset)
     return n_ord, n_live
 
@@ -93,15 +100,15 @@ def variant_run(g, maxp, slots, parity):
     return lockstep(eng, ora, T.FlagModel(st), 60, 5, 20, f"<{maxp},{slots},{parity}>")
 
 
-def aged_run(g, maxp, slots, parity, seed, permille):
+def aged_run(g, maxp, slots, parity, seed, permille, prod=(1, 1, 1), interval=25, watch=None):
     B = 12
     mw, mh, sizes = H.variant_batch(maxp, slots, parity, B)
-    eng, ora = F.aged_pair(g, mw, mh, maxp, sizes, seed)
+    eng, ora = F.aged_pair(g, mw, mh, maxp, sizes, seed, prod=prod, interval=interval)
     st = ora.read_state()
     assert F.wide_envs(st).any() and F.desynced_envs(st).any(), "the aged batch holds neither form"
     model = T.FlagModel(st)
     model.imported()
-    out = lockstep(eng, ora, model, 30, seed, permille, f"aged <{maxp},{slots},{parity}>", auto_reset=True)
+    out = lockstep(eng, ora, model, 30, seed, permille, f"aged <{maxp},{slots},{parity}>", auto_reset=True, prod=prod, interval=interval, watch=watch)
     if eng is not None:
         F.check_flag_invariants(eng, eng.game_state(), f"aged <{maxp},{slots},{parity}>")
     return out

@@ -36,11 +36,11 @@ def _assert_terms_equal(got, want, ctx=""):
                              f"kernel {got[i, k, j].tolist()} reference {want[i, k, j].tolist()} ({SR.TERMS})")
 
 
-def _twins(mw, mh, maxp, sizes, fog=True, board_seed=3):
+def _twins(mw, mh, maxp, sizes, fog=True, board_seed=3, prod=(1, 1, 1), interval=25):
     import generalsreinforcementlearning_amd as g
     boards = H.gen_boards(board_seed, sizes, mw, mh)
-    eng = g.VecEngine(len(sizes), mw, mh, maxp, fog_of_war=fog)
-    ora = O.OracleBatch(len(sizes), mw, mh, maxp, fog=fog)
+    eng = g.VecEngine(len(sizes), mw, mh, maxp, fog_of_war=fog, production=prod, normal_growth_interval=interval)
+    ora = O.OracleBatch(len(sizes), mw, mh, maxp, fog=fog, prod=prod, interval=interval)
     eng.reset(*boards)
     ora.reset(*boards)
     return eng, ora

@@ -29,14 +29,15 @@ def _z(shape, dt):
 class Players:
     """One handle driven by gvec_gym_step_players for the learners of bit set `bits`."""
 
-    def __init__(self, w, h, P, fog, bits, max_turns, pool=16):
+    def __init__(self, w, h, P, fog, bits, max_turns, pool=16, production=(1, 1, 1), normal_growth_interval=25):
         import torch
         import generalsreinforcementlearning_amd as g
         from generalsreinforcementlearning_amd._lib import check
         self.check, self.w, self.h, self.P, self.bits, self.max_turns = check, w, h, P, bits, max_turns
         self.ids = [p for p in range(P) if (bits >> p) & 1]
         L, n = len(self.ids), w * h
-        self.e = g.VecEngine(B, w, h, P, fog_of_war=fog, auto_reset=True, stream=torch.cuda.current_stream().cuda_stream)
+        self.e = g.VecEngine(B, w, h, P, fog_of_war=fog, auto_reset=True, stream=torch.cuda.current_stream().cuda_stream,
+                             production=production, normal_growth_interval=normal_growth_interval)
         self.e.reset_generated(77)
         self.e.build_board_pool(pool, 5)
         self.turn, self.resetting = _z(B, torch.int64), _z(B, torch.uint8)

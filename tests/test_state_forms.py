@@ -92,13 +92,14 @@ def test_per_turn_agent_step_on_aged_envs(maxp, slots, parity):
 
 # ---- 2. gym, one learner: gvec_gym_step == the four-call composition --------------------------------------------------
 class _GymSide:
-    def __init__(self, g, w, h, P, fog, B, max_turns, seed):
+    def __init__(self, g, w, h, P, fog, B, max_turns, seed, production=(1, 1, 1), normal_growth_interval=25):
         import torch
         from generalsreinforcementlearning_amd._lib import check
         dev = torch.device("cuda")
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.check, self.B, self.max_turns, n = check, B, max_turns, w * h
-        self.e = g.VecEngine(B, w, h, P, fog_of_war=fog, auto_reset=True, stream=torch.cuda.current_stream().cuda_stream)
+        self.e = g.VecEngine(B, w, h, P, fog_of_war=fog, auto_reset=True, stream=torch.cuda.current_stream().cuda_stream,
+                             production=production, normal_growth_interval=normal_growth_interval)
         self.e.reset_generated(77 + seed)
         self.e.build_board_pool(16, 5)
         self.e.rollout(8, seed, 80, fused=False, want_stats=False)      # lists that differ from ownership
@@ -126,16 +127,24 @@ class _GymSide:
 def test_gym_step_equals_the_four_call_composition_on_aged_envs(w, h, P, fog):
     """gvec_gym_step (gym_step_kernel) against gvec_agent_actions -> gvec_gym_actions -> gvec_step -> gvec_gym_finish_step
     on a twin aged identically: every output bit for bit every step, flags after every launch, the states at the end."""
+    tally, seen = gym_composition_run(w, h, P, fog)
+    tally.assert_all_seen(f"gym {w}x{h}")
+    assert seen["trunc"] > 0 and seen["reset"] > 0, seen
+
+
+def gym_composition_run(w, h, P, fog, steps=100, production=(1, 1, 1), normal_growth_interval=25):
+    """the comparison itself, under a production config -> (the forms met, the truncations and re-deals met)"""
     import torch
     g = _gpu()
     from generalsreinforcementlearning_amd._lib import check
     B, max_turns, n = 64, 40, w * h
-    one, four = _GymSide(g, w, h, P, fog, B, max_turns, 3), _GymSide(g, w, h, P, fog, B, max_turns, 3)
+    cfg = dict(production=production, normal_growth_interval=normal_growth_interval)
+    one, four = _GymSide(g, w, h, P, fog, B, max_turns, 3, **cfg), _GymSide(g, w, h, P, fog, B, max_turns, 3, **cfg)
     H.assert_states_equal(one.e.game_state(), four.e.game_state(), "twins")
     rng = np.random.default_rng(8)
     tally = F.FormsTally()
     seen = {"trunc": 0, "reset": 0, "reset_wide": 0}
-    for k in range(100):
+    for k in range(steps):
         mask = one.mask.cpu().numpy().astype(bool)
         acts = np.array([rng.choice(np.flatnonzero(m)) if m.any() else 0 for m in mask], np.int64)
         if k % 3 == 0:
@@ -177,8 +186,7 @@ def test_gym_step_equals_the_four_call_composition_on_aged_envs(w, h, P, fog):
         seen["trunc"] += int(a["truncated"].sum()); seen["reset"] += int(rs.sum()); seen["reset_wide"] += int((rs & wide_before).sum())
         one.resetting.copy_(one.out["needs_reset"])
         four.resetting.copy_(four.out["needs_reset"])
-    tally.assert_all_seen(f"gym {w}x{h}")
-    assert seen["trunc"] > 0 and seen["reset"] > 0, seen
+    return tally, seen
 
 
 @pytest.mark.gpu
@@ -244,24 +252,29 @@ def test_vec_env_equals_numpy_restatement_on_aged_twins(w, h, P, fog):
 def test_self_play_every_learner_on_aged_envs(w, h, P, fog):
     """gvec_gym_step_players / gvec_gym_observe_players with every player a learner against the numpy restatement per
     learner and the oracle turn (tests/test_selfplay_env.py's protocol), on envs aged after a warm-up with invalid moves."""
+    self_play_run(w, h, P, fog).assert_all_seen(f"self-play {w}x{h}")
+
+
+def self_play_run(w, h, P, fog, steps=70, production=(1, 1, 1), normal_growth_interval=25):
+    """the comparison itself, under a production config -> the forms met"""
     import test_selfplay_env as SP
     from generalsreinforcementlearning_amd.vec_engine import ACTION_DTYPE
     _gpu()
     B, max_turns, n = SP.B, 30, w * h
-    sp = SP.Players(w, h, P, fog, (1 << P) - 1, max_turns)
+    sp = SP.Players(w, h, P, fog, (1 << P) - 1, max_turns, production=production, normal_growth_interval=normal_growth_interval)
     ids, L, eng = sp.ids, len(sp.ids), sp.e
     eng.rollout(8, 12, 80, fused=False, want_stats=False)
     F.age_batch(eng, 12)
     sp.check(eng.L.gvec_gym_observe_players(eng.h, sp.bits, sp.turn.data_ptr(), max_turns, sp.obs.data_ptr(), sp.mask.data_ptr(),
                                             sp.out["reward"].data_ptr(), sp.done0.data_ptr(), sp.out["winner"].data_ptr()))
-    ora = O.OracleBatch(B, w, h, P, fog=fog)
+    ora = O.OracleBatch(B, w, h, P, fog=fog, prod=production, interval=normal_growth_interval)
     st = eng.game_state()
     ora.reset(st["army"], st["owner"], st["type"], st["width"], st["height"], st["players"])   # the envs write_state fills
     rng = np.random.default_rng(11)
     prev = SP._stats(eng.game_state())
     turn = np.zeros(B, np.int64)
     tally = F.FormsTally()
-    for k in range(70):
+    for k in range(steps):
         st0 = eng.game_state()
         rs = sp.resetting.cpu().numpy().astype(bool)
         masks0 = []
@@ -289,7 +302,7 @@ def test_self_play_every_learner_on_aged_envs(w, h, P, fog):
         tally.add(st1)
         prev = cur
         sp.next_step()
-    tally.assert_all_seen(f"self-play {w}x{h}")
+    return tally
 
 
 # ---- 4. the stream's tile updates (army in bits 32-63 of each row) ----------------------------------------------------
