@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from generalsreinforcementlearning_amd.policy_head import MaskedCategoricalHead, distill_loss
 from generalsreinforcementlearning_amd.rollout import SelfPlayRolloutBuffer
-from generalsreinforcementlearning_amd.search import HalvingSearch
+from generalsreinforcementlearning_amd.search import HalvingSearch, TreeSearch
 from generalsreinforcementlearning_amd.selfplay_env import GeneralsSelfPlayVecEnv
 
 from evaluate_arena import parse_halving
@@ -55,6 +55,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--halving", metavar="M:N:D", default="8:32:8",
                     help="the acting search: M Gumbel-top-m candidates, a budget of N playouts per decision, D turns deep")
+    ap.add_argument("--search", choices=("halving", "tree"), default="halving",
+                    help="halving: the one-ply search; tree: TreeSearch, M root slots and N simulations with a tree below the root, "
+                         "the network ranking the moves of the inner nodes too")
     ap.add_argument("--playout-rollout", choices=("agent", "bot"), default="agent",
                     help="who plays the playouts' turns: the random agent, or the scripted expander bot in every seat")
     ap.add_argument("--bot-random-permille", type=int, default=0,
@@ -72,7 +75,11 @@ def main(argv=None):
                                  seed=a.seed, device_outputs=True)
     B, L = env.num_envs, env.num_learners
     m, n, d = parse_halving(a.halving)
-    search = HalvingSearch(env, candidates=m, budget=n, depth=d, rollout=a.playout_rollout, bot_random_permille=a.bot_random_permille)
+    if a.search == "tree":
+        search = TreeSearch(env, candidates=m, simulations=n, depth=d, rollout=a.playout_rollout, bot_random_permille=a.bot_random_permille,
+                            prior_fn=lambda obs, mask: net(obs.view(-1, *obs_shape))[0])
+    else:
+        search = HalvingSearch(env, candidates=m, budget=n, depth=d, rollout=a.playout_rollout, bot_random_permille=a.bot_random_permille)
     buf = SelfPlayRolloutBuffer(env, horizon=a.horizon, gamma=a.gamma, gae_lambda=a.gae_lambda, policy_target=True)
     head = MaskedCategoricalHead(dev)
     current = lambda: buf.obs.view(B * L, *obs_shape)

@@ -19,7 +19,7 @@ from .q_targets import categorical_target, double_q_target, valid_actions_mask_f
 from .symmetry import apply_symmetry, augment_transition, inverse_symmetry, num_symmetries, random_symmetries  # noqa: F401
 from .arena import (Arena, ArenaResult, EpisodeTally, balanced_seating, expected_score, fit_elo, random_policy,  # noqa: F401
                     torch_policy)
-from .search import HalvingSearch, PlayoutScore, PlayoutSearch, halving_schedule, playout_policy  # noqa: F401
+from .search import HalvingSearch, PlayoutScore, PlayoutSearch, TreeSearch, halving_schedule, playout_policy  # noqa: F401
 
 __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", "make_actions", "unpack_legal_bits", "VecEnvState", "RewardConfig", "REWARD_TERMS",
            "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "SelfPlayRolloutBuffer", "MaskedCategoricalHead", "distill_loss", "strategic_features",
@@ -27,4 +27,4 @@ __all__ = ["VecEngine", "GvecError", "lib", "load", "lib_path", "ACTION_DTYPE", 
            "MEMORY_PLANE_NAMES", "valid_actions_mask_from_observation", "double_q_target", "categorical_target",
            "apply_symmetry", "augment_transition", "inverse_symmetry", "num_symmetries", "random_symmetries",
            "Arena", "ArenaResult", "EpisodeTally", "balanced_seating", "expected_score", "fit_elo", "random_policy", "torch_policy",
-           "PlayoutScore", "PlayoutSearch", "playout_policy", "HalvingSearch", "halving_schedule"]
+           "PlayoutScore", "PlayoutSearch", "playout_policy", "HalvingSearch", "halving_schedule", "TreeSearch"]

@@ -201,6 +201,32 @@ class SearchPolicyArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("target", "v_mix")])
 
 
+class Tree(C.Structure):
+    """gvec_tree (include/generals_vec.h): the node-major device arrays of n trees of `nodes` nodes with num_slots child slots."""
+    _fields_ = ([(n, C.c_int32) for n in ("n", "nodes", "num_slots", "reserved")]
+                + [(n, C.c_void_p) for n in ("child_action", "child_logit", "child_node", "child_count", "child_sum", "node_value",
+                                             "node_status", "node_parent", "node_slot")])
+
+
+class TreeSelectArgs(C.Structure):
+    """gvec_tree_select_args: slot may be None (the identity)."""
+    _fields_ = ([("tree", Tree), ("k", C.c_int32), ("reserved", C.c_int32), ("slot", C.c_void_p)]
+                + [(n, C.c_double) for n in ("q_lo", "q_inv_range", "c_visit", "c_scale")]
+                + [(n, C.c_void_p) for n in ("leaf_node", "leaf_slot", "leaf_action", "leaf_depth")])
+
+
+class TreeBackupArgs(C.Structure):
+    """gvec_tree_backup_args: net_value may be None."""
+    _fields_ = ([("tree", Tree), ("k", C.c_int32), ("replicas", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("leaf_node", "leaf_slot", "new_node", "terms", "status", "net_value")]
+                + [(n, C.c_double) for n in ("value_weight", "win", "loss", "land", "army")])
+
+
+TREE_NOT_EXPANDED, TREE_DEAD = -1, -2                  # child_node of an edge without a node
+TREE_IN_USE, TREE_TERMINAL = 1, 2                      # node_status bits
+EXPAND_STORED, EXPAND_OVER, EXPAND_DEAD = 1, 2, 4      # gvec_search_expand's status bits
+
+
 # flag bits of a rollout row (GVEC_TRAJ_* in include/generals_vec.h)
 TRAJ_VALID, TRAJ_TERMINAL, TRAJ_CUT = 1, 2, 4
 
@@ -245,6 +271,9 @@ SYMBOLS = {
     "gvec_search_playouts_bot": (_i32, [_vp, C.POINTER(SearchArgs), C.c_uint32, _i32]),
     "gvec_search_halve": (_i32, [_i32, _vp, C.POINTER(SearchHalveArgs)]),
     "gvec_search_improved_policy": (_i32, [_i32, _vp, C.POINTER(SearchPolicyArgs)]),
+    "gvec_search_expand": (_i32, [_vp, C.POINTER(SearchArgs), C.c_uint32, _i32, _vp, _vp, _vp]),
+    "gvec_tree_select": (_i32, [_i32, _vp, C.POINTER(TreeSelectArgs)]),
+    "gvec_tree_backup": (_i32, [_i32, _vp, C.POINTER(TreeBackupArgs)]),
     "gvec_counters": (_i32, [_vp, C.POINTER(RolloutStats)]),
     "gvec_step_traffic_bytes": (_i32, [_vp, C.POINTER(C.c_int64)]),
     "gvec_experience_begin": (_i32, [_vp]),

@@ -18,12 +18,12 @@ OUT = os.path.join(PKG, "libgvec_hip.so")
 # one subsystem, one unit (DESIGN.md "Translation units"); tests/test_kernel_asm.py checks that every csrc/*.hip and *.hpp is listed here
 SRCS = ["gvec_kernels.hip", "gvec_gym.hip", "gvec_experience.hip", "gvec_state.hip", "gvec_stream.hip", "gvec_mapgen.hip",
         "gvec_per.hip", "gvec_traj.hip", "gvec_nstep.hip", "gvec_policy.hip", "gvec_features.hip", "gvec_memory.hip",
-        "gvec_qtarget.hip", "gvec_symmetry.hip", "gvec_arena.hip", "gvec_search.hip", "gvec_halving.hip",
+        "gvec_qtarget.hip", "gvec_symmetry.hip", "gvec_arena.hip", "gvec_search.hip", "gvec_halving.hip", "gvec_tree.hip",
         # the C ABI, host only: an edit to an entry point's checks recompiles no kernel
         "gvec_api.hip", "gvec_api_engine.hip", "gvec_api_state.hip", "gvec_api_experience.hip", "gvec_api_gym.hip", "gvec_api_replay.hip",
         "gvec_api_obs.hip", "gvec_api_halving.hip"]
 DEPS = ["gvec_device.hpp", "gvec_packed.hpp", "gvec_launch.hpp", "gvec_handle.hpp", "gvec_dispatch.hpp", "gvec_turn.hpp", "gvec_gym_emit.hpp", "gvec_collect.hpp",
-        "gvec_waves.hpp", "gvec_rows.hpp", "gvec_bot.hpp",
+        "gvec_waves.hpp", "gvec_rows.hpp", "gvec_bot.hpp", "gvec_search.hpp", "gvec_playout_score.hpp",
         "go_rand_cooked.inc", os.path.join(ROOT, "include", "generals_vec.h")]
 HOST_DEPS = ["gvec_handle.hpp"]  # included by the gvec_api* units alone: an edit to it recompiles no kernel either
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",

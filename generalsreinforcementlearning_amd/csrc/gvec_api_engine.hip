@@ -557,4 +557,85 @@ int32_t gvec_search_playouts_bot(gvec_handle* h, const gvec_search_args* args, u
   return GVEC_OK;
 }
 
+int32_t gvec_search_expand(gvec_handle* h, const gvec_search_args* args, uint32_t bot_players, int32_t bot_random_permille, gvec_handle* dst,
+                           const int32_t* child_envs, int32_t* status) {
+  static const char* fn = "gvec_search_expand";
+  const auto seats_above = [&](int maxp) {
+    if (maxp >= 32 || (bot_players >> maxp) == 0u) return (int32_t)GVEC_OK;
+    set_err("%s: bot_players names a seat at or above max_players", fn);
+    return (int32_t)GVEC_E_INVALID;
+  };
+  const auto tail = [&] {
+    if (bot_random_permille < 0 || bot_random_permille > 1000) {
+      set_err("%s: bot_random_permille must be in [0, 1000]", fn);
+      return (int32_t)GVEC_E_INVALID;
+    }
+    return seats_above(GVEC_MAX_PLAYERS);
+  };
+  if (const int32_t rc = search_check(fn, h, args, tail)) return rc;
+  if (const int32_t rc = seats_above(h->maxp)) return rc;
+  if (h->sharded() || (dst && dst->sharded())) return sharded::unsupported(fn);
+  if (dst) {   // what gvec_copy_envs asks of a pair of handles: the same variant, plane stride, army block and rules
+    const gvec_config &dc = dst->cfg, &sc = h->cfg;
+    const char* field = dc.device != sc.device ? "device"
+                        : dc.max_width != sc.max_width ? "max_width"
+                        : dc.max_height != sc.max_height ? "max_height"
+                        : dc.max_players != sc.max_players ? "max_players"
+                        : dc.prod_general != sc.prod_general ? "prod_general"
+                        : dc.prod_city != sc.prod_city ? "prod_city"
+                        : dc.prod_normal != sc.prod_normal ? "prod_normal"
+                        : dc.normal_growth_interval != sc.normal_growth_interval ? "normal_growth_interval"
+                        : nullptr;
+    if (field) {
+      set_err("%s: the handles differ in %s", fn, field);
+      return GVEC_E_INVALID;
+    }
+  }
+  if (args->num_roots == 0) return GVEC_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  StepArgs a;
+  SearchArgs g;
+  search_launch_args(h, args, a, g);
+  SearchKeepArgs e;
+  memset(&e, 0, sizeof e);
+  e.child_envs = child_envs;
+  e.status = status;
+  if (dst) {
+    e.hdr = dst->d_hdr;
+    e.rows = dst->d_rows;
+    e.army16 = dst->d_army16;
+    e.army32 = dst->d_army32;
+    e.num_envs = dst->cfg.num_envs;
+  }
+  // ordered after the work already enqueued on dst's stream; dst's next call waits for the launch in turn
+  const bool cross = dst && dst != h && dst->stream != h->stream;
+  hipEvent_t ev = nullptr;
+  if (cross) {
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t w = hipEventRecord(ev, dst->stream);
+    if (w == hipSuccess) w = hipStreamWaitEvent(h->stream, ev, 0);
+    if (w != hipSuccess) {
+      (void)hipEventDestroy(ev);
+      HIPCHK(w);
+    }
+  }
+  hipError_t rc;
+  if (bot_players == 0u && bot_random_permille == 0) {
+    rc = launch_search_expand(h->var, a, g, e, h->stream);
+  } else {
+    BotArgs bot;
+    bot.players = bot_players;
+    bot.random_permille = bot_random_permille;
+    rc = launch_search_expand_bot(h->var, a, g, bot, e, h->stream);
+  }
+  if (cross) {
+    if (rc == hipSuccess) rc = hipEventRecord(ev, h->stream);
+    if (rc == hipSuccess) rc = hipStreamWaitEvent(dst->stream, ev, 0);
+    (void)hipEventDestroy(ev);  // released once the recorded work completes
+  }
+  HIPCHK(rc);
+  if (dst) dst->legal_valid = false;   // the per-turn agent samples from d_legal: the stored envs' rows of it are stale
+  return GVEC_OK;
+}
+
 }  // extern "C"

@@ -451,6 +451,41 @@ __device__ __forceinline__ double wave_sum(double x) {
   for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
   return x;
 }
+// ... in float64 and on counts, under names of their own (an overload would capture the existing calls with int arguments):
+// the tree walks of gvec_tree.hip
+__device__ __forceinline__ double wave_max_f64(double x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double o = __shfl_xor(x, off, 64);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ int wave_max_int(int x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int o = __shfl_xor(x, off, 64);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ int wave_sum_int(int x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
+  return x;
+}
+// the greatest float64 value, the lowest index among equals: every lane ends with the same index
+__device__ __forceinline__ int wave_argmax_index(double v, int idx) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(idx, off, 64);
+    const bool take = ov > v || (ov == v && oi < idx);
+    v = take ? ov : v;
+    idx = take ? oi : idx;
+  }
+  return idx;
+}
 // the greatest value, the lowest index among equals; every lane ends with the same pair
 __device__ __forceinline__ void wave_argmax(float& v, int& idx) {
 #pragma unroll

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "gvec_launch.hpp"
+#include "gvec_playout_score.hpp"
 #include "gvec_waves.hpp"
 
 namespace gvec {
@@ -35,18 +36,7 @@ __device__ __forceinline__ int wave_max_count(int x) {
 }
 
 // ---- gvec_search_halve ----
-// PlayoutScore.__call__ (search.py) operation for operation; the build's -ffp-contract=off keeps the products and sums apart
-__device__ __forceinline__ double playout_ratio(double mine, double others) {
-  const double den = mine + others;
-  return den != 0.0 ? mine / den : 0.5;
-}
-__device__ __forceinline__ double playout_score(const gvec_search_halve_args& P, const int32_t* __restrict__ t) {
-  const double shaped = (P.land * playout_ratio((double)t[4], (double)t[6]) + P.army * playout_ratio((double)t[5], (double)t[7])) -
-                        (P.land + P.army) / 2.0;
-  const double lost = t[2] == 0 ? P.loss : shaped;
-  return t[3] != 0 ? P.win : lost;
-}
-
+// the score of a playout: playout_score of gvec_playout_score.hpp
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void search_halve_kernel(gvec_search_halve_args P) {
   const int r = wave_item();
   if (r >= P.n) return;                          // the whole wave leaves: everything below is wave-uniform control flow

@@ -155,6 +155,19 @@ struct SearchArgs {
 hipError_t launch_search(const Variant& v, const StepArgs& a, const SearchArgs& g, hipStream_t s);
 // ... with the seats of bot.players on the scripted opponent's rule in every playout turn (gvec_search_playouts_bot)
 hipError_t launch_search_bot(const Variant& v, const StepArgs& a, const SearchArgs& g, const BotArgs& bot, hipStream_t s);
+// gvec_search_expand: the same playouts, and replica 0's board after its first turn kept as env child_envs[i][k] of the
+// destination arrays (hdr null: nothing is kept).  The arrays share a's variant, plane stride and army block.
+struct SearchKeepArgs {
+  uint32_t* hdr;
+  uint32_t* rows;
+  uint32_t* army16;
+  int32_t* army32;
+  const int32_t* child_envs;  // [n][K] or null = i * K + k
+  int32_t* status;            // [n][K] or null
+  int32_t num_envs;           // of the destination
+};
+hipError_t launch_search_expand(const Variant& v, const StepArgs& a, const SearchArgs& g, const SearchKeepArgs& e, hipStream_t s);
+hipError_t launch_search_expand_bot(const Variant& v, const StepArgs& a, const SearchArgs& g, const BotArgs& bot, const SearchKeepArgs& e, hipStream_t s);
 
 // internal/experience side channel
 struct ExperienceArgs {
@@ -362,5 +375,8 @@ hipError_t launch_arena_update(const gvec_arena_args& a, hipStream_t s);
 constexpr int SEARCH_POLICY_MAX_ACTIONS = 5 * GVEC_MAX_DIM * GVEC_MAX_DIM;   // the largest row the policy target holds in registers
 hipError_t launch_search_halve(const gvec_search_halve_args& a, hipStream_t s);
 hipError_t launch_search_improved_policy(const gvec_search_policy_args& a, hipStream_t s);
+// gvec_tree_select / gvec_tree_backup (gvec_tree.hip)
+hipError_t launch_tree_select(const gvec_tree_select_args& a, hipStream_t s);
+hipError_t launch_tree_backup(const gvec_tree_backup_args& a, hipStream_t s);
 
 }  // namespace gvec

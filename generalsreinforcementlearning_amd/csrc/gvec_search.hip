@@ -1,9 +1,11 @@
 // gvec_search.hip — flat Monte Carlo search (gvec_search_playouts, gvec_search_playouts_bot): one
 // wavefront per playout loads a root board read-only, plays one candidate action for one seat, then random-agent turns - or
 // turns in which named seats play the scripted opponent's rule (gvec_bot.hpp) - and writes back eight numbers instead of a
-// board.
+// board.  gvec_search_expand's pair of kernels (gvec_tree.hip) is the same playout that also keeps the board after
+// its first turn; what all four share is gvec_search.hpp.
 #include "gvec_bot.hpp"
 #include "gvec_dispatch.hpp"
+#include "gvec_search.hpp"
 #include "gvec_turn.hpp"
 
 namespace gvec {
@@ -20,52 +22,10 @@ namespace gvec {
 //   turns 1 .. depth - 1: rollout_kernel's inner loop.  A finished game ends the playout; it is never re-dealt.
 //   terms[v][8]: valid, turns, alive, won, land, army, land_others, army_others - the counts from the sources the gym
 //           kernels use (turn_tile_counts, army_counts)
-// What the two kernels share is the helpers below; only the turn loop differs.  They take and return plain values: a helper
+// What the two kernels share is the helpers of gvec_search.hpp; only the turn loop differs.  They take and return plain values: a helper
 // that returns the row through references, or one that holds the two early returns, compiles search_kernel to other
 // instructions than before (all 18 instantiations), and these do not.
 
-// playout v's root i (returned) and candidate k
-__device__ __forceinline__ int search_root_index(const SearchArgs& S, int v, int& k) {
-  const int per_root = S.num_candidates * S.replicas;
-  const int i = v / per_root;
-  k = (v - i * per_root) / S.replicas;
-  return i;
-}
-__device__ __forceinline__ int search_root_env(const SearchArgs& S, int i) { return S.root_envs ? uni(S.root_envs[i]) : i; }
-__device__ __forceinline__ long long search_candidate(const SearchArgs& S, int i, int k) {
-  return (long long)uni64((uint64_t)S.candidates[(size_t)i * S.num_candidates + k]);
-}
-// an INVALID row: all zeros, nothing is played
-__device__ __forceinline__ void search_invalid_row(int32_t* out, int lane) {
-  if (lane < GVEC_SEARCH_TERMS) out[lane] = 0;
-}
-// the seat is one the board has, and alive (alive implies below the env's player count)
-template <int MAXP>
-__device__ __forceinline__ bool search_seat_ok(uint32_t alive, int pl) {
-  return pl >= 0 && pl < MAXP && ((alive >> (pl & 31)) & 1u) != 0u;
-}
-// the candidate's ActVec meta: the pass plays no move
-__device__ __forceinline__ uint32_t search_meta(bool pass, bool half) { return pass ? 0u : (16u | (half ? 32u : 0u)); }
-// turn 0 (cand: this lane is the seat's, on turn 0): the seat's slot is the candidate
-template <typename AV>
-__device__ __forceinline__ void search_override(AV& av, bool cand, uint32_t c_meta, int from, int tt) {
-  av.meta = cand ? c_meta : av.meta;
-  av.ft = cand ? from : av.ft;
-  av.tt = cand ? tt : av.tt;
-}
-// the eight terms of the board as the playout left it after t turns
-template <int MAXP, int NSLOT>
-__device__ __forceinline__ void search_terms(const Turn<MAXP, NSLOT>& b, int32_t* out, int seat, int lane, int t) {
-  const uint32_t tcl = turn_tile_counts(b), acl = army_counts<MAXP>(b);
-  const bool other = lane < MAXP && lane != seat;
-  const uint32_t land = rdlane(tcl, seat), army = rdlane(acl, seat);
-  const uint32_t land_others = wave_sum(other ? tcl : 0u), army_others = wave_sum(other ? acl : 0u);
-  const bool over = (b.hflags & HF_DONE) != 0u;
-  const uint32_t alive = (b.alive >> seat) & 1u, won = (over && gym_winner(over, b.P, b.alive) == seat) ? 1u : 0u;
-  const uint32_t val = lane == 0 ? 1u : lane == 1 ? (uint32_t)t : lane == 2 ? alive : lane == 3 ? won : lane == 4 ? land : lane == 5 ? army
-                       : lane == 6 ? land_others : army_others;
-  if (lane < GVEC_SEARCH_TERMS) out[lane] = (int32_t)val;
-}
 template <int MAXP, int NSLOT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>())) void search_kernel(StepArgs A, SearchArgs S) {
   __shared__ int32_t army_shadow[WAVES_PER_BLOCK][NSLOT * 64];
@@ -174,12 +134,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (rollout_waves<MAXP, NSLOT>()
     b.template legal_planes<false>(m);
   }
   search_terms<MAXP, NSLOT>(b, out, seat, lane, t);
-}
-
-static StepArgs search_keyed(const StepArgs& in) {
-  StepArgs keyed = in;
-  keyed.env_base = 0;   // the playout index is the key, whichever handle the roots live in
-  return with_seed_bases(keyed);
 }
 
 hipError_t launch_search(const Variant& v, const StepArgs& in, const SearchArgs& g, hipStream_t s) {

@@ -483,6 +483,328 @@ class HalvingSearch:
         return target, v_mix
 
 
+def search_expand_device(engine, num_roots, candidates_ptr, root_players_ptr, terms_ptr, num_candidates, replicas, depth, seed=0,
+                         root_envs_ptr=None, bot_players=0, bot_random_permille=0, dst=None, child_envs_ptr=None, status_ptr=None):
+    """gvec_search_expand on device memory: search_playouts_device's playouts, and replica 0's board after its first turn
+    kept as env child_envs[i][k] (None: i * K + k) of the VecEngine `dst` (None: nothing is kept); status int32 [n][K]."""
+    a = SearchArgs(num_roots=int(num_roots), num_candidates=int(num_candidates), replicas=int(replicas), depth=int(depth),
+                   root_envs=root_envs_ptr, root_players=root_players_ptr, candidates=candidates_ptr, seed=int(seed) & (2 ** 64 - 1),
+                   terms=terms_ptr)
+    if not 0 <= int(bot_players) < 2 ** 32:
+        raise ValueError(f"bot_players must be a mask of seats below 32, not {bot_players!r}")
+    check(engine.L.gvec_search_expand(engine.h, C.byref(a), int(bot_players), int(bot_random_permille), None if dst is None else dst.h,
+                                      child_envs_ptr, status_ptr), "gvec_search_expand")
+
+
+class TreeSearch:
+    """The search of Danihelka et al. with a tree below the root: sequential halving over the
+    Gumbel-top-m root slots, the deterministic argmax(pi' - N / (1 + sum N)) rule at every node below, one node expanded per
+    simulation, the values backed up along the path.  Every node's board stays resident in a scratch engine.
+
+        search = TreeSearch(env, candidates=16, simulations=64, depth=8)     # 15 waves of 16, 8, 8, 4 ... columns per row
+        actions, found = search.act(mask, logits=logits, seed=step)          # per wave: select, expand, observe, backup, copy
+        target, v_mix = search.policy_target(logits, mask, found, value)
+        arena = Arena(env, [playout_policy(search, net), bot_policy()])
+
+    Round r of halving_schedule(candidates, simulations) runs R_r waves over its K_r surviving root slots; a wave is
+    gvec_tree_select, gvec_search_expand (the parents' node envs as roots, under HalvingSearch.round_seed(seed, wave)),
+    the priors of the new nodes (the gym observation of the dense frontier the children were stored in) and
+    gvec_tree_backup, then gvec_copy_envs of the children into their node envs - whose range check is the one stream
+    synchronisation a wave costs."""
+
+    def __init__(self, env_or_engine, candidates=16, simulations=64, depth=8, replicas=1, children=None, prior_fn=None, value_weight=0.0,
+                 score=None, rollout="agent", bot_players=None, bot_random_permille=0, c_visit=50.0, c_scale=1.0):
+        """candidates m in [1, 64] root slots, simulations >= 1 expansions per row to spread over the rounds (what is spent is
+        `simulations_per_row`), depth and replicas: every expansion is `replicas` playouts of at most `depth` turns from the
+        parent; children C in [candidates, 64] slots per node (None: candidates); prior_fn(obs, mask) -> logits [rows, A] or
+        (logits, value [rows] in score units) for the new nodes (None: logit 0 on every legal action); value_weight w in [0, 1]
+        mixes that value into a node's estimate, (1 - w) * playout mean + w * value; the rest as HalvingSearch takes it."""
+        from ._lib import SEARCH_MAX_SLOTS
+        for name, v in (("simulations", simulations), ("replicas", replicas)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1, not {v!r}")
+        self._halving = HalvingSearch(env_or_engine, candidates=candidates, budget=simulations, depth=depth, score=score, rollout=rollout,
+                                      bot_players=bot_players, bot_random_permille=bot_random_permille, c_visit=c_visit, c_scale=c_scale)
+        if children is None:
+            children = candidates
+        if isinstance(children, bool) or not isinstance(children, (int, np.integer)) or not candidates <= children <= SEARCH_MAX_SLOTS:
+            raise ValueError(f"children must be an int in [candidates = {candidates}, {SEARCH_MAX_SLOTS}], not {children!r}")
+        if isinstance(value_weight, bool) or not isinstance(value_weight, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= value_weight <= 1.0:
+            raise ValueError(f"value_weight must be a number in [0, 1], not {value_weight!r}")
+        if prior_fn is not None and not callable(prior_fn):
+            raise ValueError("prior_fn must be callable: prior_fn(obs, mask) -> logits or (logits, value)")
+        if value_weight > 0 and prior_fn is None:
+            raise ValueError("value_weight > 0 needs a prior_fn that returns (logits, value)")
+        h = self._halving
+        self.m, self.C, self.R, self.D = int(candidates), int(children), int(replicas), int(depth)
+        self.simulations, self.prior_fn, self.value_weight = int(simulations), prior_fn, float(value_weight)
+        self.score, self.q_lo, self.q_inv_range, self.c_visit, self.c_scale = h.score, h.q_lo, h.q_inv_range, h.c_visit, h.c_scale
+        self.env, self.engine, self.num_actions = h.env, h.engine, h.num_actions
+        self.rollout, self.bot_players, self.bot_random_permille = h.rollout, h.bot_players, h.bot_random_permille
+        self.schedule = h.schedule                             # [(K_r, R_r)]: R_r waves of K_r columns
+        self.waves = sum(R for _, R in self.schedule)
+        self.simulations_per_row = sum(K * R for K, R in self.schedule)
+        self.nodes = 1 + self.simulations_per_row
+        self.playouts_per_row = self.simulations_per_row * self.R     # what HalvingSearch calls the same count
+        self.max_turns = int(getattr(self.env, "max_turns", 500))
+        self._slots = PlayoutSearch(env_or_engine, candidates=self.C, replicas=1, depth=1)      # propose() for a node's slots
+        self._tree_engine = self._frontier = None
+        self._rows = 0
+
+    round_seed = staticmethod(HalvingSearch.round_seed)
+
+    def propose(self, mask, logits=None, seed=0):
+        """HalvingSearch.propose: the root's Gumbel-top-m slots and their prior keys"""
+        return self._halving.propose(mask, logits, seed)
+
+    # ---- the scratch engines ---------------------------------------------------------------------------------------------
+    def _engines(self, n):
+        """(tree engine of n * nodes envs - node j of row r is env j * n + r -, frontier of n * candidates envs): created
+        on first use, again when a call brings more rows"""
+        if self._tree_engine is None or n > self._rows:
+            from .vec_engine import VecEngine
+            e = self.engine
+            for old in (self._tree_engine, self._frontier):
+                if old is not None:
+                    old.close()
+            kw = dict(fog_of_war=e.fog_of_war, device=e.device, production=e.production, normal_growth_interval=e.normal_growth_interval,
+                      stream=getattr(e, "_stream", None), lib=e.L)
+            self._tree_engine = VecEngine(n * self.nodes, e.max_w, e.max_h, e.max_p, **kw)
+            self._frontier = VecEngine(n * self.m, e.max_w, e.max_h, e.max_p, **kw)
+            self._rows = n
+        return self._tree_engine, self._frontier
+
+    def close(self):
+        for e in (self._tree_engine, self._frontier):
+            if e is not None:
+                e.close()
+        self._tree_engine = self._frontier = None
+        self._rows = 0
+
+    def new_tree(self, n, device):
+        """the nine node-major tensors of n empty trees (include/generals_vec.h gvec_tree)"""
+        import torch
+        from ._lib import TREE_NOT_EXPANDED
+        N, Cn = self.nodes, self.C
+        return {"child_action": torch.full((N, n, Cn), SEARCH_NONE, dtype=torch.int64, device=device),
+                "child_logit": torch.zeros((N, n, Cn), dtype=torch.float32, device=device),
+                "child_node": torch.full((N, n, Cn), TREE_NOT_EXPANDED, dtype=torch.int32, device=device),
+                "child_count": torch.zeros((N, n, Cn), dtype=torch.int32, device=device),
+                "child_sum": torch.zeros((N, n, Cn), dtype=torch.float64, device=device),
+                "node_value": torch.zeros((N, n), dtype=torch.float64, device=device),
+                "node_status": torch.zeros((N, n), dtype=torch.int32, device=device),
+                "node_parent": torch.zeros((N, n), dtype=torch.int32, device=device),
+                "node_slot": torch.zeros((N, n), dtype=torch.int32, device=device)}
+
+    def _tree_struct(self, tree, n):
+        from ._lib import Tree
+        return Tree(n=n, nodes=self.nodes, num_slots=self.C, reserved=0, **{k: v.data_ptr() for k, v in tree.items()})
+
+    # ---- the four steps of a wave (the GPU tests drive them one by one) ----------------------------------------------------
+    def select(self, tree, slot):
+        """slot int32 [n, K] -> (leaf_node, leaf_slot int32 [n, K], leaf_action int64 [n, K], leaf_depth int32 [n, K])"""
+        import torch
+        from ._lib import TreeSelectArgs, load
+        n, K = int(slot.shape[0]), int(slot.shape[1])
+        dev = slot.device
+        out = [torch.empty((n, K), dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.int64, torch.int32)]
+        a = TreeSelectArgs(tree=self._tree_struct(tree, n), k=K, reserved=0, slot=slot.data_ptr(), q_lo=self.q_lo, q_inv_range=self.q_inv_range,
+                           c_visit=self.c_visit, c_scale=self.c_scale, leaf_node=out[0].data_ptr(), leaf_slot=out[1].data_ptr(),
+                           leaf_action=out[2].data_ptr(), leaf_depth=out[3].data_ptr())
+        check(load().gvec_tree_select(dev.index, self._halving._stream(), C.byref(a)), "gvec_tree_select")
+        return tuple(out)
+
+    def expand(self, n, players, leaf_node, leaf_action, seed):
+        """the playouts of one wave from the parents' node envs, the children stored in the frontier's envs r * K + c ->
+        (terms int32 [n, K, R, 8], status int32 [n, K])"""
+        import torch
+        tree_e, frontier = self._engines(n)
+        K, dev = int(leaf_node.shape[1]), leaf_node.device
+        rows = torch.arange(n, dtype=torch.int64, device=dev)[:, None]
+        root_envs = (leaf_node.to(torch.int64) * n + rows).to(torch.int32).reshape(-1).contiguous()
+        seats = players.repeat_interleave(K).contiguous()
+        cand = leaf_action.reshape(n * K, 1).contiguous()
+        terms = torch.empty((n, K, self.R, SEARCH_TERMS), dtype=torch.int32, device=dev)
+        status = torch.empty((n, K), dtype=torch.int32, device=dev)
+        search_expand_device(tree_e, n * K, cand.data_ptr(), seats.data_ptr(), terms.data_ptr(), 1, self.R, self.D, seed, root_envs.data_ptr(),
+                             self.bot_players, self.bot_random_permille, dst=frontier, status_ptr=status.data_ptr())
+        return terms, status
+
+    def observe(self, n, K, players, turn_count):
+        """(obs float32 [n * K, 9, stride], mask uint8 [n * K, A]) of the frontier's first n * K envs, each from the seat of
+        its row; turn_count int64 [n, K].  The frontier is observed once per seat that searches (gvec_gym_observe)."""
+        import torch
+        _, frontier = self._engines(n)
+        dev, B, stride = players.device, frontier.B, int(frontier.stride)
+        turns = torch.zeros((B,), dtype=torch.int64, device=dev)
+        turns[:n * K] = turn_count.reshape(-1)
+        if self.env is not None:
+            seats = [int(p) for p in (self.env._learner_ids() if hasattr(self.env, "_learner_ids") else getattr(self.env, "player_ids", [0]))]
+        else:
+            seats = list(range(int(self.engine.max_p)))
+        seat_of = players.repeat_interleave(K)
+        obs = mask = None
+        for p in sorted(set(seats)):
+            o = torch.empty((B, 9, stride), dtype=torch.float32, device=dev)
+            k = torch.empty((B, 5 * stride), dtype=torch.uint8, device=dev)
+            check(frontier.L.gvec_gym_observe(frontier.h, p, turns.data_ptr(), self.max_turns, o.data_ptr(), k.data_ptr(), None, None, None),
+                  "gvec_gym_observe")
+            o, k = o[:n * K], k[:n * K]
+            if obs is None:
+                obs, mask = o, k
+            else:
+                mine = seat_of == p
+                obs, mask = torch.where(mine[:, None, None], o, obs), torch.where(mine[:, None], k, mask)
+        return obs, mask
+
+    def priors(self, obs, mask, seed):
+        """-> (slots int64 [rows, C], logits float32 [rows, C], value float32 [rows] or None): a new node's slots are its
+        top-C legal actions by prior_fn's logits (PlayoutSearch.propose's hash order under `seed` without a prior_fn)"""
+        import torch
+        logits = value = None
+        if self.prior_fn is not None:
+            with torch.no_grad():
+                out = self.prior_fn(obs, mask)
+            logits, value = (out[0], out[1]) if isinstance(out, (tuple, list)) else (out, None)
+            logits = logits.reshape(mask.shape).to(torch.float32)
+            if value is not None:
+                value = value.reshape(-1).to(torch.float32).contiguous()
+        slots = self._slots.propose(mask, logits, seed)
+        if logits is None:
+            return slots, torch.zeros(slots.shape, dtype=torch.float32, device=slots.device), None
+        got = logits.gather(1, slots.clamp(min=0))
+        return slots, torch.where(slots >= 0, got, torch.zeros_like(got)).contiguous(), value
+
+    def backup(self, tree, leaf_node, leaf_slot, new_node, terms, status, net_value=None):
+        from ._lib import TreeBackupArgs, load
+        n, K = int(leaf_node.shape[0]), int(leaf_node.shape[1])
+        s = self.score
+        use = net_value is not None and self.value_weight > 0
+        a = TreeBackupArgs(tree=self._tree_struct(tree, n), k=K, replicas=self.R, leaf_node=leaf_node.data_ptr(), leaf_slot=leaf_slot.data_ptr(),
+                           new_node=new_node.data_ptr(), terms=terms.data_ptr(), status=status.data_ptr(),
+                           net_value=net_value.data_ptr() if use else None, value_weight=self.value_weight if use else 0.0,
+                           win=s.win, loss=s.loss, land=s.land, army=s.army)
+        check(load().gvec_tree_backup(leaf_node.device.index, self._halving._stream(), C.byref(a)), "gvec_tree_backup")
+
+    def rank(self, tree, n, K, slot, prior_key, k_next):
+        """the round's K columns ranked as gvec_search_halve ranks them from the root's sums and counts (all-zero terms add
+        nothing) -> (next_slot int32 [n, k_next], next_candidates int64 [n, k_next])"""
+        import torch
+        from ._lib import SearchHalveArgs, load
+        dev, s = slot.device, self.score
+        zeros = torch.zeros((n, K, 1, SEARCH_TERMS), dtype=torch.int32, device=dev)
+        next_slot = torch.empty((n, k_next), dtype=torch.int32, device=dev)
+        next_cand = torch.empty((n, k_next), dtype=torch.int64, device=dev)
+        a = SearchHalveArgs(n=n, m=self.C, k=K, replicas=1, k_next=k_next, reserved=0, terms=zeros.data_ptr(), slot=slot.data_ptr(),
+                            candidates0=tree["child_action"][0].data_ptr(), prior_key=prior_key.data_ptr(), win=s.win, loss=s.loss,
+                            land=s.land, army=s.army, q_lo=self.q_lo, q_inv_range=self.q_inv_range, c_visit=self.c_visit,
+                            c_scale=self.c_scale, sum=tree["child_sum"][0].data_ptr(), count=tree["child_count"][0].data_ptr(),
+                            next_slot=next_slot.data_ptr(), next_candidates=next_cand.data_ptr())
+        check(load().gvec_search_halve(dev.index, self._halving._stream(), C.byref(a)), "gvec_search_halve")
+        return next_slot, next_cand
+
+    def start(self, env_ids, players, candidates, prior_key):
+        """the tree of a new search: node 0 a copy of the root envs (which stay read-only), its slots the candidates ->
+        (tree, prior key padded to [n, C])"""
+        import torch
+        n, dev = int(candidates.shape[0]), candidates.device
+        tree_e, _ = self._engines(n)
+        mix = getattr(self.engine, "agent_mix", None)             # the playouts draw under the root engine's mix, as
+        if mix is not None and mix != getattr(tree_e, "agent_mix", None):   # HalvingSearch's do on the root engine itself
+            tree_e.set_agent_mix(*mix)
+        tree = self.new_tree(n, dev)
+        tree["child_action"][0, :, :self.m] = candidates
+        tree["node_status"][0] = 1
+        key = torch.full((n, self.C), -float("inf"), dtype=torch.float64, device=dev)
+        key[:, :self.m] = prior_key
+        src = torch.arange(n, dtype=torch.int32, device=dev) if env_ids is None else env_ids
+        tree_e.copy_envs(torch.arange(n, dtype=torch.int32, device=dev), src, n=n, src=self.engine)
+        return tree, key
+
+    def keep(self, n, new_node):
+        """the wave's children, the frontier's envs r * K + c, into their node envs new_node * n + r (gvec_copy_envs)"""
+        import torch
+        tree_e, frontier = self._engines(n)
+        K, dev = int(new_node.shape[1]), new_node.device
+        rows = torch.arange(n, dtype=torch.int64, device=dev)[:, None]
+        dst = (new_node.to(torch.int64) * n + rows).to(torch.int32).reshape(-1)
+        tree_e.copy_envs(dst, torch.arange(n * K, dtype=torch.int32, device=dev), n=n * K, src=frontier)
+
+    def search(self, env_ids, players, candidates, prior_key, seed=0, turn_count=None):
+        """HalvingSearch.search's arguments (turn_count int64 [n]: the rows' gym turn counts, for the observations' turn
+        plane; None: 0) -> what it returns, from the root's slots, plus nodes_used int32 [n] (the root included) and `tree`,
+        the node-major tensors."""
+        import torch
+        first = self._halving._rounds[0]
+        dev = first._device()
+        cand0 = first._check(candidates, "candidates", torch.int64, None, dev)
+        if cand0.dim() != 2 or cand0.shape[1] != self.m:
+            raise ValueError(f"candidates {tuple(cand0.shape)} is not [n, {self.m}]")
+        n = int(cand0.shape[0])
+        first._check(prior_key, "prior_key", torch.float64, (n, self.m), dev)
+        first._check(players, "players", torch.int32, (n,), dev)
+        if env_ids is not None:
+            first._check(env_ids, "env_ids", torch.int32, (n,), dev)
+        if turn_count is not None:
+            first._check(turn_count, "turn_count", torch.int64, (n,), dev)
+        if n * self.nodes >= 2 ** 31 or n * self.m * self.R >= 2 ** 31:
+            raise ValueError(f"{n} rows of {self.nodes} nodes do not fit a scratch engine")
+        if n == 0:
+            tree = self.new_tree(0, dev)
+            empty = torch.zeros((0,), dtype=torch.int32, device=dev)
+            return {"sum": tree["child_sum"][0], "count": tree["child_count"][0], "q": torch.zeros((0, self.m), dtype=torch.float32, device=dev),
+                    "valid": torch.zeros((0, self.m), dtype=torch.bool, device=dev), "slot": empty, "action": empty.to(torch.int64),
+                    "found": empty.to(torch.bool), "nodes_used": empty, "tree": tree}
+        tree, key = self.start(env_ids, players, cand0, prior_key)
+        turn0 = torch.zeros((n,), dtype=torch.int64, device=dev) if turn_count is None else turn_count
+        slot = torch.arange(self.m, dtype=torch.int32, device=dev).repeat(n, 1).contiguous()
+        cand, wave, used = cand0, 0, 1
+        for K, R in self.schedule:
+            for _ in range(R):
+                wave_seed = self.round_seed(seed, wave)
+                leaf_node, leaf_slot, leaf_action, leaf_depth = self.select(tree, slot)
+                terms, status = self.expand(n, players, leaf_node, leaf_action, wave_seed)
+                obs, mask = self.observe(n, K, players, turn0[:, None] + leaf_depth.to(torch.int64) + 1)
+                slots, logits, value = self.priors(obs, mask, wave_seed)
+                new_node = (used + torch.arange(K, dtype=torch.int32, device=dev)).repeat(n, 1).contiguous()
+                at = (new_node.to(torch.int64) * n + torch.arange(n, dtype=torch.int64, device=dev)[:, None]).reshape(-1)
+                tree["child_action"].view(-1, self.C)[at] = slots
+                tree["child_logit"].view(-1, self.C)[at] = logits
+                self.backup(tree, leaf_node, leaf_slot, new_node, terms, status, None if value is None else value.reshape(n, K).contiguous())
+                self.keep(n, new_node)
+                wave, used = wave + 1, used + K
+            slot, cand = self.rank(tree, n, K, slot, key, (K + 1) // 2)
+        total, count = tree["child_sum"][0, :, :self.m].contiguous(), tree["child_count"][0, :, :self.m].contiguous()
+        valid = count > 0
+        q = (total / count.clamp(min=1).to(torch.float64)).to(torch.float32)
+        survivor = slot[:, 0]
+        found = valid.gather(1, survivor.to(torch.int64)[:, None]).squeeze(1)
+        return {"sum": total, "count": count, "q": q, "valid": valid, "slot": survivor, "action": cand[:, 0], "found": found,
+                "nodes_used": (tree["node_status"] & 1).sum(dim=0).to(torch.int32), "tree": tree}
+
+    def act(self, mask, logits=None, seed=0, rows=None):
+        """HalvingSearch.act's signature and row conventions -> (actions int64 [n], info): the surviving root slot's action;
+        0 for a row without one.  info: candidates and prior_key [n, m], and everything search() returns."""
+        import torch
+        first = self._halving._rounds[0]
+        dev = first._device()
+        if isinstance(mask, torch.Tensor) and mask.device != dev:
+            raise ValueError(f"mask is on {mask.device}, the engine on {dev}")
+        cand, prior = self.propose(mask, logits, seed)
+        env_ids, players = first._rows_to_ids(int(cand.shape[0]), rows)
+        turns = getattr(self.env, "_d_turn", None)
+        turn_count = None if turns is None else turns.reshape(-1).to(torch.int64).index_select(0, env_ids.to(torch.int64))
+        info = self.search(env_ids, players, cand, prior, seed, turn_count)
+        info.update(candidates=cand, prior_key=prior)
+        ok = info["found"] & (info["action"] >= 0)
+        return torch.where(ok, info["action"], torch.zeros((), dtype=torch.int64, device=dev)), info
+
+    def policy_target(self, logits, mask, info, value=None, out=None):
+        """HalvingSearch.policy_target on the root's slots (gvec_search_improved_policy)"""
+        return self._halving.policy_target(logits, mask, info, value, out)
+
+
 class _PlayoutPolicy:
     """An Arena entrant: search.act on the rows it is seated at (Arena binds them), the prior from net or uniform."""
 

@@ -298,6 +298,7 @@ class VecEngine:
         (45875, 19661) are the rates of the reference's game.GenerateRandomActions (demo_helpers.go:20,44);
         (0, 0) always plays a full move, uniform over the legal ones."""
         check(self.L.gvec_set_agent_mix(self.h, int(noop_per_65536), int(half_per_65536)), "gvec_set_agent_mix")
+        self.agent_mix = (int(noop_per_65536), int(half_per_65536))      # what a scratch engine of this one has to play under
 
     def counters(self):
         """Lifetime counters summed over all envs: turns actually played, aborted turns (H5), games finished."""

@@ -443,6 +443,100 @@ typedef struct gvec_search_policy_args {
 int32_t gvec_search_halve(int32_t device, void* hip_stream, const gvec_search_halve_args* args);
 int32_t gvec_search_improved_policy(int32_t device, void* hip_stream, const gvec_search_policy_args* args);
 
+/* ---- tree search below the root: the full search of Danihelka et al. - sequential halving at the
+ * root, the deterministic argmax(pi' - N / (1 + sum N)) rule at every node below it, one node expanded per simulation, values
+ * backed up along the path.  The board of every node stays resident as an env of a scratch handle.
+ *
+ * gvec_search_expand: a playout launch that also KEEPS THE BOARD AFTER ITS FIRST TURN.  terms are exactly those of
+ * gvec_search_playouts - of gvec_search_playouts_bot when bot_players or bot_random_permille is non-zero - on the same
+ * arguments: the playout index, the key, the candidate decode, the invalid rows, the read-only roots and the depth turns.
+ * On top, for every (root i, candidate k), replica 0's board as it stands after the playout's first turn is written into
+ * env child_envs[i][k] of dst (child_envs device int32 [n][K]; NULL: env i*K + k).  Nothing is stored for a pair whose
+ * entry is below 0 or at or above dst's num_envs (checked on the device, no host sync), for an invalid row, or when dst is
+ * NULL - the call is then the plain playout launch.  status int32 [n][K], may be NULL: bit 0 a board was stored, bit 1 the
+ * game is over after the first turn, bit 2 the seat is not alive after it; 0 for an invalid row.
+ * Written to the destination env: the header except the slot's lifetime counters, which stay dst's own; the whole planes
+ * block, types and lists included; the armies in the narrow or the wide form as every store picks it.  dst's legal-mask
+ * buffer, error codes, recorded actions, gym baseline and experience rows are not touched.  The stored env equals env
+ * (i*K + k)*R of gvec_search_playouts' own composition - the scratch handle of n*K*R copies, gvec_agent_actions(seed, 0)
+ * (+ gvec_bot_actions), the candidate in the seat's slot, gvec_step - read after that first gvec_step: every field of
+ * gvec_read_state, and every later call on dst behaves as if the env had always held that state.
+ * dst must match h as gvec_copy_envs requires (plain handles, the same device, max dims and production constants):
+ * GVEC_E_INVALID with the field named otherwise, and nothing is launched.  dst == h is allowed as long as no child env is
+ * a root env of the same call (undefined otherwise, as for gvec_copy_envs).  Enqueued on h's stream, ordered after the work
+ * already enqueued on dst's; dst's next call waits for it.  The other errors are gvec_search_playouts_bot's.
+ *
+ * The tree of row r < n has `nodes` nodes, node 0 the root, every node num_slots = C <= 64 child slots.  All arrays are
+ * device memory and NODE-MAJOR ([nodes][n][C] and [nodes][n]), so that the root's slice is the [n][C] gvec_search_halve and
+ * gvec_search_improved_policy take.  child_action GVEC_SEARCH_NONE marks an empty slot; child_node -1 = not expanded,
+ * -2 = dead, else a node id; node_status bit 0 in use, bit 1 terminal.  A slot is OPEN when its action is not NONE and its
+ * node is not dead.  Both entry points are handle-free: (device, hip_stream, args).
+ *
+ * gvec_tree_select: k columns per row, column c starting at root slot slot[r][c] (NULL: c, needs k == C; the slots of a
+ * row are distinct).  A root slot outside [0, C) or a dead root edge gives leaf (0, -1).  A root edge that is not expanded
+ * is the leaf (0, slot).  Otherwise the walk descends: at a terminal node, a node without an open slot or a node id
+ * outside [0, nodes) it stops with leaf_slot = -1; at any other node u it picks a slot and stops there if that edge is not
+ * expanded.  The pick, float64 over the open slots of u with N_c the slot's count, sumN their sum, nmax their maximum:
+ *   pi = softmax(child_logit) (the maximum subtracted), q_c = sum_c / N_c where N_c > 0,
+ *   v_mix = node_value[u] when sumN == 0, else (node_value[u] + sumN * (sum_{N>0} pi_c q_c / sum_{N>0} pi_c)) / (1 + sumN),
+ *   qhat_c = q_c on visited slots, v_mix elsewhere,
+ *   z_c = logit_c + ((c_visit + nmax) * c_scale) * ((qhat_c - q_lo) * q_inv_range)      (gvec_search_halve's grouping)
+ *   pi' = softmax(z); the slot is argmax of pi'_c - N_c / (1 + sumN), the lowest slot on a tie.
+ * Outputs [n][k]: leaf_node, leaf_slot, leaf_action (child_action of the leaf edge: the candidate to hand to
+ * gvec_search_expand; GVEC_SEARCH_NONE when leaf_slot is -1) and leaf_depth (the leaf node's distance from the root).
+ * The kernel reads the tree only.  One wavefront per (row, column), lane = slot; the sums are fixed butterflies.
+ *
+ * gvec_tree_backup: per column with leaf_slot >= 0, g = the mean PlayoutScore (gvec_search_halve's, operation for
+ * operation) of the valid replicas of terms[r][c], added in order and divided once; with net_value, g = (1 - value_weight)
+ * * g + value_weight * (double)net_value[r][c], in that order.  If bit 0 of status[r][c] is clear or no replica is valid
+ * the leaf edge becomes dead (child_node -2) and nothing is added.  Otherwise the edge gets new_node[r][c] and that node
+ * node_value = g, node_status = 1 | (status & 6 ? 2 : 0), its parent and slot.  A column that stopped at a terminal node
+ * (leaf_slot -1, node_status bit 1, not the root) takes g = that node's node_value and starts at its parent edge.  From
+ * that edge up to node 0, inclusive, child_sum += g and child_count += 1.  Every other column, and one whose leaf or
+ * new_node is outside the tree, changes nothing.  Distinct root slots mean disjoint subtrees: no atomics, the same input
+ * gives the same bits.  One wavefront per row, lane = column.
+ * GVEC_E_INVALID with a message, before anything touches a device: args or a required pointer NULL (slot and net_value
+ * may be), n < 0, num_slots outside [1, 64], k outside [1, num_slots] (select: slot NULL with k != num_slots), nodes < 1
+ * or nodes * n at or above 2^31, replicas < 1, a non-zero reserved.  n == 0 is a no-op that needs no device. */
+int32_t gvec_search_expand(gvec_handle* h, const gvec_search_args* args, uint32_t bot_players, int32_t bot_random_permille,
+                           gvec_handle* dst, const int32_t* child_envs, int32_t* status);
+typedef struct gvec_tree {
+  int32_t n, nodes, num_slots, reserved;
+  int64_t* child_action;            /* [nodes][n][C] */
+  float* child_logit;               /* [nodes][n][C] */
+  int32_t* child_node;              /* [nodes][n][C] */
+  int32_t* child_count;             /* [nodes][n][C] */
+  double* child_sum;                /* [nodes][n][C] */
+  double* node_value;               /* [nodes][n] */
+  int32_t* node_status;             /* [nodes][n] */
+  int32_t* node_parent;             /* [nodes][n] */
+  int32_t* node_slot;               /* [nodes][n] */
+} gvec_tree;
+typedef struct gvec_tree_select_args {
+  gvec_tree tree;
+  int32_t k, reserved;
+  const int32_t* slot;              /* [n][k], NULL = identity */
+  double q_lo, q_inv_range, c_visit, c_scale;
+  int32_t* leaf_node;               /* [n][k] out */
+  int32_t* leaf_slot;               /* [n][k] out */
+  int64_t* leaf_action;             /* [n][k] out */
+  int32_t* leaf_depth;              /* [n][k] out */
+} gvec_tree_select_args;
+typedef struct gvec_tree_backup_args {
+  gvec_tree tree;
+  int32_t k, replicas;
+  const int32_t* leaf_node;         /* [n][k] */
+  const int32_t* leaf_slot;         /* [n][k] */
+  const int32_t* new_node;          /* [n][k] */
+  const int32_t* terms;             /* [n][k][replicas][GVEC_SEARCH_TERMS] */
+  const int32_t* status;            /* [n][k] */
+  const float* net_value;           /* [n][k], NULL = none */
+  double value_weight;
+  double win, loss, land, army;     /* the score's weights */
+} gvec_tree_backup_args;
+int32_t gvec_tree_select(int32_t device, void* hip_stream, const gvec_tree_select_args* args);
+int32_t gvec_tree_backup(int32_t device, void* hip_stream, const gvec_tree_backup_args* args);
+
 /* ---- internal/experience side channel ------------------------------
  * gvec_experience_begin   = TurnProcessor.captureStateForExperience
  *                           (turn_processor.go:116-121: GameState.Clone before the step):
